@@ -103,6 +103,40 @@ def memory_plan(B, params, pe, B_, steps, warmup, nfl, n_entries, transfers, rrb
             "transfer_leg_batches": nt, "transfer_leg_batch_GB": round(tot(small) / 1e9, 1), "reference_GB": round(ref_b / 1e9, 1)}
 
 
+DUMP_UNITS = 1 << 15   # --dump-outputs: units of the last timed step whose records are written (a fixed, seeded sample; about 18 MB for C3)
+
+
+def dump_outputs(d, bt, first, n, pe, np):
+    """--dump-outputs DIR: the records the last timed step returned to its caller (PairAlign.results: pairs, both mates' class counts and
+    the per-class pair counts; SingleAlign.results: hits and class counts) for a fixed, seeded sample of its n units starting at unit `first`
+    of batch `bt`: DIR/<record>.<field>.npy per field (a mate's hit one level down: pair.a.loc), DIR/n_pairs_by_class.npy and the sampled unit
+    numbers DIR/unit.npy; float64 for 32-bit fields and the unit numbers, float32 for narrower ones"""
+    os.makedirs(d, exist_ok=True)
+    u = first + np.sort(np.random.default_rng(20251015).choice(n, min(n, DUMP_UNITS), replace=False))
+    arrays = {"unit": u}
+    if pe:
+        out, ca, cb, npairs = bt.results()
+        recs = {"pair": out[u], "counts_a": ca[u], "counts_b": cb[u]}
+        arrays["n_pairs_by_class"] = npairs[u]
+    else:
+        hits, cc = bt.results()
+        recs = {"hit": hits[u], "counts": cc[u]}
+
+    def fields(prefix, r):
+        for f in r.dtype.names:
+            if f.endswith("_"):   # padding
+                continue
+            if r[f].dtype.names:
+                fields(prefix + "." + f, r[f])
+            else:
+                arrays[prefix + "." + f] = r[f]
+    for k, r in recs.items():
+        fields(k, r)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v.astype(np.float64 if v.dtype.itemsize >= 4 else np.float32))
+    return {"dir": d, "units": int(u.size), "arrays": len(arrays)}
+
+
 def algorithmic_bytes(c, n_reads):
     """8*N_lookup + sum_cand(4 + 8*W_c) + 80*N_orient + 16 per read"""
     n_lookup, n_cand, sum_w, n_orient = (int(x) for x in c[:4])
@@ -174,6 +208,8 @@ def main():
     ap.add_argument("--work-counters", type=int, default=0, help="0 (default): the timed region runs as the command line does, with the work counters off (bsx_batch_set_work_counters: the scan "
                     "kernels skip the early-out classification that only the counters need; records identical) and the counters of the SURVEY 8(d) formula come from a counted "
                     "pass over the same resident steps afterwards; 1: the timed region itself is counted")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the records the last timed step computed (a fixed, seeded "
+                    "sample of its units, DUMP_UNITS) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -285,6 +321,10 @@ def main():
     dt = time.perf_counter() - t0
     counters = sum(bt.counters().astype(np.float64) for bt in batches)   # (with the work counters off: completed by the counted pass below)
     heavy_last = [int(batch.heavy_units()), int(batch.redo_units())]
+    dumped = None
+    if args.dump_outputs and rank == 0:   # (step i ran on batch (i - warmup) % in_flight, slot i % ring)
+        last = args.warmup + args.steps - 1
+        dumped = dump_outputs(args.dump_outputs, batches[(last - args.warmup) % nfl], (last % ring) * B_, B_, pe, np)
     # per-kernel evidence comes from a serial replay (one batch, control and scan passes strictly alternating): with batches in
     # flight the launches of different batches overlap and their durations say nothing about one kernel
     pools = [bt.pool_sizes() for bt in batches]
@@ -401,6 +441,8 @@ def main():
         # scan order serves most of those bytes from L2 — and can exceed 1.  `hbm_traffic` is what the memory system really moved.
         "roofline": roofline_block(dk, bound, achieved, traffic, traffic_note, hbm, k_ms, kernel_ms, heavy_last, alg_bytes_launch, counters, n_reads_rank, args, pmc_j, serial, np),
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if world == 1 and not args.profile_serial:
         out["workload_shape"] = workload_shape(ref, counters, args.steps, B_, reads_per_unit, heavy_last[0])
     if serial_err:

@@ -1,6 +1,7 @@
 """ctypes binding of oracle/_ref/libbsmapref.so — the REAL reference objects behind our white-box
 harness (oracle/ref_harness.cpp).  TEST INFRASTRUCTURE ONLY.  The library exists only where
-`make -C oracle ref` has run (needs /root/reference); tests skip when it is absent.
+`make -C oracle ref` has run (needs the reference's sources); the golden generators under tests/golden/ use it, and the
+suite reads what they recorded.
 """
 import ctypes as C
 import os

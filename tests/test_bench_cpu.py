@@ -86,3 +86,53 @@ def test_roofline_block_is_flat_short_and_priced_against_the_microbenchmark():
     # a control-bound config names the control kernel
     serial["stage_ms"].update(k_hctrl=400.0)
     assert BN.roofline_block(dk, "x", 1.0, None, "none", None, 224.0, [448.0], (37000, 0), 4e12, [1.0] * 17, 1 << 23, args, None, serial, np)["binding_kernel"] == "k_hctrl"
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_last_steps_records(tmp_path):
+    """--dump-outputs: the sampled units lie in the given step's slot, every field comes out exact (locations above 2^24 included),
+    two dumps of the same records are identical, and a full C3 step stays under 64 MB"""
+    import numpy as np
+    import bsmap_amd as B
+    n_step, n_total, first = 50_000, 200_000, 100_000
+    units = np.arange(n_total)
+
+    class PE:
+        def results(self):
+            out = np.zeros(n_total, B.PAIR_DTYPE)
+            out["a_loc"] = 3_000_000_000 - units
+            out["insert"] = -(units % 977)
+            out["b"]["loc"] = units * 7
+            ca, cb = np.zeros(n_total, B.CC_DTYPE), np.zeros(n_total, B.CC_DTYPE)
+            ca["n_hit"][:, 3] = units % 65521
+            npairs = np.zeros((n_total, 31), np.uint16)
+            npairs[:, 30] = units % 3
+            return out, ca, cb, npairs
+
+    class SE:
+        def results(self):
+            hits, cc = np.zeros(n_total, B.HIT_DTYPE), np.zeros(n_total, B.CC_DTYPE)
+            hits["loc"] = units + (1 << 30)
+            cc["n_chit"][:, 15] = units % 1000
+            return hits, cc
+
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    r = BN.dump_outputs(d1, PE(), first, n_step, True, np)
+    BN.dump_outputs(d2, PE(), first, n_step, True, np)
+    u = np.load(os.path.join(d1, "unit.npy")).astype(np.int64)
+    assert r["units"] == u.size == BN.DUMP_UNITS and np.all(np.diff(u) > 0) and u[0] >= first and u[-1] < first + n_step
+    assert np.array_equal(np.load(os.path.join(d1, "pair.a_loc.npy")), 3_000_000_000 - u)
+    assert np.array_equal(np.load(os.path.join(d1, "pair.insert.npy")), -(u % 977))
+    assert np.array_equal(np.load(os.path.join(d1, "pair.b.loc.npy")), u * 7) and not np.load(os.path.join(d1, "pair.a.loc.npy")).any()
+    assert np.array_equal(np.load(os.path.join(d1, "counts_a.n_hit.npy"))[:, 3], u % 65521)
+    assert np.array_equal(np.load(os.path.join(d1, "n_pairs_by_class.npy"))[:, 30], u % 3)
+    assert not any("pad" in f for f in os.listdir(d1))
+    names = sorted(os.listdir(d1))
+    assert names == sorted(os.listdir(d2)) and len(names) == r["arrays"]
+    for f in names:
+        a, b = np.load(os.path.join(d1, f)), np.load(os.path.join(d2, f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert sum(os.path.getsize(os.path.join(d1, f)) for f in names) < 64 << 20
+    BN.dump_outputs(d1 + "se", SE(), 0, n_step, False, np)
+    u = np.load(os.path.join(d1 + "se", "unit.npy")).astype(np.int64)
+    assert u[-1] < n_step and np.array_equal(np.load(os.path.join(d1 + "se", "hit.loc.npy")), u + (1 << 30))
+    assert np.array_equal(np.load(os.path.join(d1 + "se", "counts.n_chit.npy"))[:, 15], u % 1000)
