@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bsmap_amd", "csrc")
 EXE = os.path.join(ROOT, "bsmap_amd", "bsmap_asan")
 
-pytestmark = pytest.mark.skipif(shutil.which("g++") is None or not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs g++ and hipcc (libbsx.so is linked)")
+pytestmark = [pytest.mark.skipif(shutil.which("g++") is None or not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs g++ and hipcc (libbsx.so is linked)"),
+              pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="a GPU is present: the sanitizer build would start the HIP runtime and map for real, and a host-sanitizer binary must never touch a device")]
 
 
 @pytest.fixture(scope="module")

@@ -7,6 +7,8 @@ Parity at this size:
   * WHOLE batches (131 072 units of C2 / C3, 65 536 of C2 -n 1 / C4 / C5) re-aligned by the oracle's batch driver on the host
     cores against the ORACLE-BUILT reference + index: every record field and the four work counters; C5 also in exact mode
     against the oracle's `-p 1` state; a summary goes to gpurun_out/validate/r04_validate_<cfg>.json (copied into profiles/);
+  * bench steps (test_blocks_of_a_bench_sized_batch_equal_the_oracle, test_bench_step_equals_the_oracle): one step of bench.py's own size, pools and
+    reads per mode (C2 / C3 / C4 / C5), blocks of it and deferred units from every round of the heavy pipeline re-aligned by the oracle (wholebatch.py);
   * idempotence: the same batch twice gives byte-identical records and counters;
   * partition invariance: aligning in two halves equals aligning the whole batch;
   * path invariance: results do not depend on which units go through the heavy pipeline (default threshold vs none);
@@ -190,45 +192,22 @@ def test_blocks_of_a_bench_sized_batch_equal_the_oracle(big, oracle, oracle_wgbs
     if oracle_wgbs.base is None:
         oracle_wgbs.check(ref, "c3")
     oref = oracle_wgbs.ref_for(KW)
-    NB, BLK, NBLK = 1 << 22, 4096, 32
-    L = B.lib()
-    u, t = B.default_heavy_limits(B.make_params(**KW), NB, True)
-    L.bsx_set_heavy_limits(u, t)
+    M, NB, _, limits = W.bench_mode("pe")
+    assert M["kw"] == KW and NB == 1 << 22
+    BLK, NBLK = 4096, 32
+    pa = W.bench_batch(ref, "pe", NB)
     try:
-        pa = B.PairAlign(ref, NB).set_work_counters(False)
-    finally:
-        L.bsx_set_heavy_limits(0, 0)
-    try:
-        pa.synth_reads(NB, 144, seed=3)
-        t0 = time.time()
-        pa.Do_Batch()
-        t_gpu = time.time() - t0
-        out, ca, cb, npairs = pa.results()
-        heavy = int(pa.heavy_units())
-        hlist = np.sort(pa.heavy_list().astype(np.int64))
-        b1, o1 = pa.download_reads(0)
-        b2, o2 = pa.download_reads(1)
+        pa.synth_reads(NB, M["L"], seed=3, kind=M["kind"])
+        # the deferred units carry 97 % of the step's candidates: the comparison has to hold a good number of them — those that fall into the blocks,
+        # and 256 more taken evenly from the deferred list, each re-aligned alone
+        bad_all, info = W.bench_step_blocks(oracle, oref, pa, "pe", 0, n_blocks=NBLK, blk=BLK)
     finally:
         pa.close()
-    bad_all, t_cpu, placed = {}, 0.0, 0
-    # the deferred units carry 97 % of the step's candidates: the comparison has to hold a good number of them — those that fall into the blocks, and 256 more
-    # taken evenly from the deferred list, each re-aligned alone (the pick RNG is a function of the unit's own index)
-    spans = [(k * (NB // NBLK) + 17 * k, k * (NB // NBLK) + 17 * k + BLK) for k in range(NBLK)]   # (not on any power-of-two grid)
-    in_blocks = int(sum(np.searchsorted(hlist, hi) - np.searchsorted(hlist, lo) for lo, hi in spans))
-    extra = [int(u) for u in hlist[:: max(1, len(hlist) // 256)][:256] if not any(lo <= u < hi for lo, hi in spans)]
-    assert len(hlist) == heavy and in_blocks >= 1000 and len(extra) >= 200, (len(hlist), heavy, in_blocks, len(extra))
-    for lo, hi in spans + [(u, u + 1) for u in extra]:
-        t0 = time.time()
-        ores, _ = oracle.pe_batch(oref, b1[int(o1[lo]):int(o1[hi])], (o1[lo:hi + 1] - o1[lo]).copy(), b2[int(o2[lo]):int(o2[hi])], (o2[lo:hi + 1] - o2[lo]).copy(),
-                                  first_index=lo, threads=W.usable_cpus())
-        t_cpu += time.time() - t0
-        bad, info = W.compare_pe(ores, out[lo:hi], ca[lo:hi], cb[lo:hi], npairs[lo:hi], KW["v"] + 1)
-        placed += info["paired_out"]
-        for f, n in bad.items():
-            bad_all[f] = bad_all.get(f, 0) + n
-    W.record("bench_step_c3", dict(units_in_batch=NB, units_compared=BLK * NBLK + len(extra), blocks=NBLK, heavy_units=heavy, deferred_units_compared=in_blocks + len(extra), paired_out=placed, oracle_s=round(t_cpu, 1), do_batch_s=round(t_gpu, 3),
-                                   mismatching_fields=bad_all, options=KW, work_counters=False, reference="oracle-built from the genome text"))
-    assert heavy > NB // 200 and placed > 0.95 * BLK * NBLK
+    W.record("bench_step_c3", info)
+    heavy = info["heavy_units"]
+    assert info["deferred_in_blocks"] >= 1000 and info["deferred_alone"] >= 200, info
+    assert info["pool_sizes"] == list(limits), info
+    assert heavy > NB // 200 and info["paired_out"] > 0.95 * BLK * NBLK
     assert not bad_all, bad_all
 
 
@@ -287,22 +266,25 @@ OTHER = {
 
 
 @pytest.fixture(scope="module", params=sorted(OTHER))
-def other(request):
-    cfg = OTHER[request.param]
+def other(request, oracle, oracle_wgbs):
+    name = request.param
+    cfg = OTHER[name]
     ref = B.RefSeq(B.make_params(**cfg["kw"])).synthetic(HG38, seed=38).CreateIndex()
     al = (B.PairAlign if cfg["pe"] else B.SingleAlign)(ref, cfg["n"])
     al.synth_reads(cfg["n"], cfg["L"], seed=17, kind=cfg["kind"])
     al.Do_Batch()
     res = tuple(x.copy() for x in al.results())
     cnt = al.counters().copy()
-    HEAVY[request.param] = (int(al.heavy_units()), int(al.redo_units()))   # of THIS run
-    yield request.param, cfg, ref, al, res, cnt
+    HEAVY[name] = (int(al.heavy_units()), int(al.redo_units()))   # of THIS run
+    oref = _oracle_ref(name, cfg, ref, oracle, oracle_wgbs)   # (built once for the tests of this config: C4's from the genome text is the costly one)
+    yield name, cfg, ref, al, res, cnt, oref
+    oref.free()
     al.close()
     ref.close()
 
 
 def test_other_configs_closure_idempotence_partition(other):
-    name, cfg, ref, al, res, cnt = other
+    name, cfg, ref, al, res, cnt, _ = other
     n = cfg["n"]
     assert int(cnt[4]) == n
     assert ref.n_words > 190_000_000 and ref.n_entries > (1_000_000 if name == "c4" else 1_400_000_000)
@@ -349,48 +331,102 @@ def _oracle_ref(name, cfg, ref, oracle, oracle_wgbs):
     return oracle_wgbs.ref_for(kw)
 
 
-def test_other_configs_whole_batch_equals_oracle(other, oracle, oracle_wgbs):
+def test_other_configs_whole_batch_equals_oracle(other, oracle):
     """every unit of the batch re-aligned by the oracle's batch driver against the oracle's OWN build of reference + index from
     the 3.1 GB genome text (WGBS and RRBS alike; the device's copy is compared with it first) — every record field and the four
     work counters; C5 also in exact mode (bsx_batch_set_leak_exact) against the oracle's `-p 1` state (leak_mode 1)"""
     import wholebatch as W
-    name, cfg, ref, al, res, cnt = other
+    name, cfg, ref, al, res, cnt, oref = other
     kw, n = cfg["kw"], cfg["n"]
     nclass = kw.get("v", 2) + 1
     quals = cfg["kind"] == 1
-    oref = _oracle_ref(name, cfg, ref, oracle, oracle_wgbs)
+    ores, ocnt, t_cpu = W.run_oracle(oracle, oref, al, cfg["pe"], quals, n)
+    if cfg["pe"]:
+        bad, info = W.compare_pe(ores, res[0], res[1], res[2], res[3], nclass)
+    else:
+        bad, info = W.compare_se(ores, res[0], res[1], nclass)
+    rec = dict(info, units=n, oracle_s=round(t_cpu, 1), counters_gpu=[int(x) for x in cnt[:4]], counters_oracle=ocnt, mismatching_fields=bad,
+               options={k: v for k, v in kw.items()}, heavy_units=HEAVY[name][0], redo_units=HEAVY[name][1],
+               reference="oracle-built from the genome text")
+    if name == "c5":   # the only BASELINE config whose reads leak planner state ((len - I + 1) % S == 0 after trimming)
+        ex = B.PairAlign(ref, n).set_leak_exact()
+        try:
+            ex.synth_reads(n, cfg["L"], seed=17, kind=cfg["kind"])
+            ex.Do_Batch()
+            eres = ex.results()
+            ecnt = [int(x) for x in ex.counters()[:4]]
+        finally:
+            ex.close()
+        lres, lcnt, t_leak = W.run_oracle(oracle, oref, al, True, True, n, leak_mode=1)
+        ebad, _ = W.compare_pe(lres, eres[0], eres[1], eres[2], eres[3], nclass)
+        S, I = kw["s"], kw["I"]
+        leaky = sum(int((((lres[m]["len"] - I + 1) % S == 0) & (lres[m]["filtered"] == 0)).sum()) for m in ("a", "b"))
+        differ = int((eres[0].tobytes() != res[0].tobytes()))
+        rec["exact_mode"] = dict(oracle_s=round(t_leak, 1), counters_gpu=ecnt, counters_oracle=lcnt, mismatching_fields=ebad, leaky_reads=leaky,
+                                 records_differ_from_default_mode=bool(differ))
+        W.record(name, rec)
+        assert leaky > n // 50
+        assert not ebad, ebad
+        assert ecnt == lcnt
+    else:
+        W.record(name, rec)
+    assert not bad, bad
+    assert [int(x) for x in cnt[:4]] == ocnt
+
+
+BENCH_STEP = {"c2": "se", "c4": "rrbs", "c5": "trim"}   # this module's config -> bench.py's mode
+
+
+@pytest.mark.parametrize("other", sorted(BENCH_STEP), indirect=True)
+def test_bench_step_equals_the_oracle(other, oracle):
+    """bench.py's own regime for C2 / C4 / C5: a batch that holds two of the mode's steps (reads as the bench's ring makes them: seed 3, unit ids
+    from 0), created under the mode's starting pools with the work counters off, runs its SECOND step (unit ids at and above the step size reach
+    the pick RNG and the mate indexing).  32 blocks of 4 096 units and ~256 deferred units taken evenly over the deferred list are re-aligned by
+    the oracle against its own reference + index: every record field.  The test also shows that it ran the bench's regime: the pools as
+    started, several rounds of deferred units (C4: at least 10; C5: at least 2) with compared units in every round.  C2 and C5 then run the same
+    step on as many batches at once as the bench keeps in flight: byte-identical records.  (C4 is left out there: three RRBS batches plan 0.88
+    of the device.)"""
+    import threading
+    import wholebatch as W
+    name, cfg, ref, _, _, _, oref = other
+    mode = BENCH_STEP[name]
+    M, units, nfl, limits = W.bench_mode(mode)
+    assert M["kw"] == cfg["kw"] and M["pe"] == cfg["pe"] and M["L"] == cfg["L"] and M["kind"] == cfg["kind"]
+    batches = [W.bench_batch(ref, mode, 2 * units)]
     try:
-        ores, ocnt, t_cpu = W.run_oracle(oracle, oref, al, cfg["pe"], quals, n)
-        if cfg["pe"]:
-            bad, info = W.compare_pe(ores, res[0], res[1], res[2], res[3], nclass)
-        else:
-            bad, info = W.compare_se(ores, res[0], res[1], nclass)
-        rec = dict(info, units=n, oracle_s=round(t_cpu, 1), counters_gpu=[int(x) for x in cnt[:4]], counters_oracle=ocnt, mismatching_fields=bad,
-                   options={k: v for k, v in kw.items()}, heavy_units=HEAVY[name][0], redo_units=HEAVY[name][1],
-                   reference="oracle-built from the genome text")
-        if name == "c5":   # the only BASELINE config whose reads leak planner state ((len - I + 1) % S == 0 after trimming)
-            ex = B.PairAlign(ref, n).set_leak_exact()
-            try:
-                ex.synth_reads(n, cfg["L"], seed=17, kind=cfg["kind"])
-                ex.Do_Batch()
-                eres = ex.results()
-                ecnt = [int(x) for x in ex.counters()[:4]]
-            finally:
-                ex.close()
-            lres, lcnt, t_leak = W.run_oracle(oracle, oref, al, True, True, n, leak_mode=1)
-            ebad, _ = W.compare_pe(lres, eres[0], eres[1], eres[2], eres[3], nclass)
-            S, I = kw["s"], kw["I"]
-            leaky = sum(int((((lres[m]["len"] - I + 1) % S == 0) & (lres[m]["filtered"] == 0)).sum()) for m in ("a", "b"))
-            differ = int((eres[0].tobytes() != res[0].tobytes()))
-            rec["exact_mode"] = dict(oracle_s=round(t_leak, 1), counters_gpu=ecnt, counters_oracle=lcnt, mismatching_fields=ebad, leaky_reads=leaky,
-                                     records_differ_from_default_mode=bool(differ))
-            W.record(name, rec)
-            assert leaky > n // 50
-            assert not ebad, ebad
-            assert ecnt == lcnt
-        else:
-            W.record(name, rec)
-        assert not bad, bad
-        assert [int(x) for x in cnt[:4]] == ocnt
+        batches[0].synth_reads(2 * units, M["L"], seed=3, kind=M["kind"])
+        bad, info = W.bench_step_blocks(oracle, oref, batches[0], mode, units)
+        if mode != "rrbs":
+            lone = [x[units:2 * units].tobytes() for x in batches[0].results()]
+            for _ in range(nfl - 1):
+                batches.append(W.bench_batch(ref, mode, 2 * units))
+                batches[-1].synth_reads(2 * units, M["L"], seed=3, kind=M["kind"])
+
+            def work(j):
+                batches[j].run_range(units, units, sync=True)
+
+            th = [threading.Thread(target=work, args=(j,)) for j in range(1, nfl)]
+            for t in th:
+                t.start()
+            work(0)
+            for t in th:
+                t.join()
+            info["in_flight"] = dict(batches=nfl, pool_sizes=[list(b.pool_sizes()) for b in batches], heavy_units=[int(b.heavy_units()) for b in batches],
+                                     identical=[[x[units:2 * units].tobytes() for x in b.results()] == lone for b in batches])
     finally:
-        oref.free()
+        for b in batches:
+            b.close()
+    W.record(f"bench_step_{name}", info)
+    assert info["pool_sizes"] == list(limits), (info["pool_sizes"], limits)   # halved pools: not the bench's regime
+    heavy, rounds = info["heavy_units"], info["rounds"]
+    assert info["rounds_covered"] == rounds, info["deferred_compared_per_round"]
+    if mode == "rrbs":
+        assert heavy > units // 2 and rounds >= 10, (heavy, rounds)
+    if mode == "trim":
+        assert rounds >= 2, (heavy, rounds)
+    assert info["deferred_units_compared"] >= 1000, info["deferred_units_compared"]
+    placed = info["paired_out" if M["pe"] else "placed"] / info["units_compared"]
+    assert placed > {"se": 0.85, "rrbs": 0.8, "trim": 0.9}[mode], placed   # (the levels of test_other_configs_closure_idempotence_partition)
+    assert not bad, bad
+    if mode != "rrbs":
+        assert all(info["in_flight"]["identical"]), info["in_flight"]
