@@ -10,6 +10,12 @@ ranks / wall time of the K timed steps (max over ranks).  --mode se | rrbs | tri
   python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: spawns the N ranks itself, see launch_ranks)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU, reads sharded)
   python bench.py --profile-serial                      (profiling: no two kernels overlap; see profiles/README.md)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line.  Everything else the
+line can carry needs runs of its own and is behind --full: the serial replay and the counted pass behind `roofline`,
+`workload_shape`, the measured memory ceilings, `cpu_baseline`, `value_incl_transfers`, `sensitivity`, `end_to_end` and
+`other_configs`.  The --cpu-seconds, --e2e-pairs, --transfer-steps, --sensitivity and --other-configs options shape those legs
+under --full and do nothing without it.
 """
 import argparse
 import hashlib
@@ -188,11 +194,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--pairs-per-step", type=int, default=0, help="units (pairs, or single reads) per step; 0 = the mode's default (MODE_DEFAULTS: 2^22 for C3)")
     ap.add_argument("--genome", default="hg38", help="hg38 (3.09 Gbp synthetic, the bench config) or a fraction like 0.05 for quick checks")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of each cpu_baseline sample (0 = skip)")
-    ap.add_argument("--e2e-pairs", type=int, default=16 << 20, help="pairs of the end-to-end CLI run (FASTQ -> SAM in /dev/shm) reported beside the metric; 0 = skip")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: target CPU time of each cpu_baseline sample (0 = skip)")
+    ap.add_argument("--e2e-pairs", type=int, default=16 << 20, help="--full: pairs of the end-to-end CLI run (FASTQ -> SAM, files in shared memory) reported beside the metric; 0 = skip")
     ap.add_argument("--in-flight", type=int, default=0, help="batches in flight per GPU (host threads, one device batch each): the main kernel and the "
                     "latency-bound tail of one batch overlap the scan passes of the other; 1 = strictly one Do_Batch at a time; 0 = the mode's default (MODE_DEFAULTS)")
-    ap.add_argument("--transfer-steps", type=int, default=-1, help="steps of the PCIe-inclusive leg (upload -> Do_Batch -> results per step); -1 = as many as --steps (the same window length as the metric's), 0 = skip")
+    ap.add_argument("--transfer-steps", type=int, default=-1, help="--full: steps of the PCIe-inclusive leg (upload -> Do_Batch -> results per step); -1 = as many as --steps (the same window length as the metric's), 0 = skip")
     ap.add_argument("--waves-per-cu", type=int, default=0)
     ap.add_argument("--heavy-limits", default="", help="tuning: units per round,scan-task pool of the heavy pipeline")
     ap.add_argument("--heavy-threshold", type=int, default=0, help="tuning: candidate-list length that defers a unit to the heavy pipeline (0 = library default)")
@@ -201,15 +207,18 @@ def main():
                     "strictly alternate), no CPU / end-to-end / transfer legs — no two kernels overlap, so per-kernel durations add up to at most the step time")
     ap.add_argument("--exact", action="store_true", help="run with bsx_batch_set_leak_exact (the single-threaded reference's planner state for every read): "
                     "the line then includes the pre-pass that finds that state (k_leak_meta / k_leak_resolve)")
-    ap.add_argument("--sensitivity", type=int, default=1, help="1: also run the workload on two variants of the synthetic genome (microsatellite share halved; no repeat "
+    ap.add_argument("--sensitivity", type=int, default=1, help="--full: 1: also run the workload on two variants of the synthetic genome (microsatellite share halved; no repeat "
                     "elements) — the headline depends on the generator's repeat content; 0 = skip")
-    ap.add_argument("--other-configs", type=int, default=1, help="1 (with the default mode, one GPU): after the metric's own config, run BASELINE's other single-GPU configs (C2, C4, C5) "
+    ap.add_argument("--other-configs", type=int, default=1, help="--full: 1 (with the default mode, one GPU): after the metric's own config, run BASELINE's other single-GPU configs (C2, C4, C5) "
                     "for a few steps each in child processes and report them under other_configs — parity-test cases, not the metric")
     ap.add_argument("--work-counters", type=int, default=0, help="0 (default): the timed region runs as the command line does, with the work counters off (bsx_batch_set_work_counters: the scan "
-                    "kernels skip the early-out classification that only the counters need; records identical) and the counters of the SURVEY 8(d) formula come from a counted "
-                    "pass over the same resident steps afterwards; 1: the timed region itself is counted")
+                    "kernels skip the early-out classification that only the counters need; records identical) and, with --full, the counters of the SURVEY 8(d) formula come from a "
+                    "counted pass over the same resident steps afterwards; 1: the timed region itself is counted")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the records the last timed step computed (a fixed, seeded "
                     "sample of its units, DUMP_UNITS) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run what takes runs of its own: the serial replay and the counted pass "
+                    "(roofline, workload_shape), the memory probe, the CPU baseline, the PCIe-inclusive leg, the sensitivity variants, the end-to-end "
+                    "command line and the other configs (each as its own option says); off: the line carries the headline, its config and nothing else")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -273,7 +282,7 @@ def main():
     n_total = B_ * ring
     nfl = max(1, args.in_flight)
     Align = B.PairAlign if pe else B.SingleAlign
-    plan = memory_plan(B, B.make_params(**kw), pe, B_, args.steps, args.warmup, nfl, int(ref.n_entries), args.transfer_steps != 0 and world == 1, bool(kw.get("D")), float(sum(lens)), limits=(u_, t_))
+    plan = memory_plan(B, B.make_params(**kw), pe, B_, args.steps, args.warmup, nfl, int(ref.n_entries), args.full and args.transfer_steps != 0 and world == 1, bool(kw.get("D")), float(sum(lens)), limits=(u_, t_))
     t0 = time.time()
     batches = [Align(ref, n_total) for _ in range(nfl)]
     for bt in batches:
@@ -319,7 +328,7 @@ def main():
     run_steps(args.warmup, args.warmup + args.steps)
     sync_all()
     dt = time.perf_counter() - t0
-    counters = sum(bt.counters().astype(np.float64) for bt in batches)   # (with the work counters off: completed by the counted pass below)
+    counters = sum(bt.counters().astype(np.float64) for bt in batches)   # (with the work counters off, --full completes them by the counted pass below; 4-6 and 16 are exact either way)
     heavy_last = [int(batch.heavy_units()), int(batch.redo_units())]
     dumped = None
     if args.dump_outputs and rank == 0:   # (step i ran on batch (i - warmup) % in_flight, slot i % ring)
@@ -348,7 +357,7 @@ def main():
         return {"ms_per_step": wall, "event_ms_per_do_batch": float(np.mean(ms)), "scan_ms": sc, "stage_ms": stage}
 
     counted = None
-    if nfl > 1 and world == 1 and args.steps >= 2:
+    if args.full and nfl > 1 and world == 1 and args.steps >= 2:
         try:   # (a diagnostic leg must never cost the line)
             sb = batch   # alone on the device now: one batch in flight, one unit group — control and scan passes alternate strictly
             sb.run_range(0, B_, sync=True)
@@ -359,7 +368,7 @@ def main():
         except Exception as e:
             serial = None
             serial_err = str(e)[:300]
-    if not args.work_counters and not args.profile_serial:
+    if args.full and not args.work_counters and not args.profile_serial:
         # The counted pass: every resident step once more, alone on the device, with the work counters on.  A step's counters are a pure
         # function of its reads, so the timed region's counters are the sum over its steps of their slots' — the numerator of the SURVEY 8(d)
         # formula — and the same two steps as above give the scan kernel's time WITH the classification (A/B on this box, same minute).
@@ -392,34 +401,7 @@ def main():
             dist.destroy_process_group()
         return
     value = n_reads_rank * world / dt_max
-    alg_bytes_launch = algorithmic_bytes(counters, n_reads_rank) / args.steps
-    # device time of one Do_Batch: HIP events on the batch's stream; with several batches in flight their kernels share the
-    # GPU, so the step time that counts is the wall time per step of the timed region
-    k_ms = float(np.mean(kernel_ms)) if nfl == 1 else dt_max / args.steps * 1e3
-    achieved = alg_bytes_launch / (k_ms * 1e-3) / 1e9
     sha = lib_sha16()
-    traffic, traffic_note, pmc_j = None, "no PMC summary for this build (profiles/pmc_latest.json is from another libbsx.so)", None
-    pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-    if os.path.exists(pmc) and args.mode == "pe":
-        try:
-            pj = json.load(open(pmc))
-            if pj.get("lib_sha16") == sha:
-                traffic, traffic_note, pmc_j = pj.get("hbm_bytes_per_launch"), f"profiles/{pj.get('tag')}_pmc.json (same libbsx.so, serial mode)", pj
-        except Exception:
-            pass
-    step_s = k_ms * 1e-3
-    wc = bool(args.work_counters)
-    dk = dominant_kernel(serial["counters"], serial["scan_ms"], 2, 1, args.mode == "rrbs", args.mode, wc, B_) if serial else dominant_kernel(counters, scan_ms, args.steps, nfl, args.mode == "rrbs", args.mode, wc, B_)
-    hbm = None
-    if pmc_j:  # what the memory system really moved per step (FETCH_SIZE raw and with the guide's gfx950 x2 rule for wide reads, WRITE_SIZE)
-        raw = pmc_j["fetch_bytes_per_step_raw"] + pmc_j["write_bytes_per_step"]
-        x2 = pmc_j["fetch_bytes_per_step_x2_gfx950"] + pmc_j["write_bytes_per_step"]
-        hbm = {"raw_GBps": raw / step_s / 1e9, "x2_corrected_GBps": x2 / step_s / 1e9, "frac_of_peak_raw": raw / step_s / 1e9 / HBM_PEAK_GBS,
-               "frac_of_peak_x2": x2 / step_s / 1e9 / HBM_PEAK_GBS, "bytes_per_step_raw": raw, "bytes_per_step_x2": x2,
-               "note": "measured HBM bytes of one step (PMC passes, serial mode) over the wall time of a step in the timed region"}
-    bound = "VALU issue and the gathers (texture addresser) of the scan kernel, random 64-byte requests of k_align; NOT HBM bandwidth"
-    if hbm:
-        bound += " (HBM carries %.2f-%.2f of its peak)" % (hbm["frac_of_peak_raw"], hbm["frac_of_peak_x2"])
     out = {
         "metric": M["metric"], "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -434,77 +416,107 @@ def main():
                    "records_flagged_BSX_F_LIMIT": int(tot_counters[16]) if len(tot_counters) > 16 else None,   # (the one capacity deviation from the reference, include/bsx.h: counted, 0)
                    "aligned_fraction": float((2 * tot_counters[6] + tot_counters[5]) / max(1.0, n_reads_rank * world)) if pe
                    else float(tot_counters[5] / max(1.0, n_reads_rank * world))},
+    }
+    if args.full:
+        alg_bytes_launch = algorithmic_bytes(counters, n_reads_rank) / args.steps
+        # device time of one Do_Batch: HIP events on the batch's stream; with several batches in flight their kernels share the
+        # GPU, so the step time that counts is the wall time per step of the timed region
+        k_ms = float(np.mean(kernel_ms)) if nfl == 1 else dt_max / args.steps * 1e3
+        achieved = alg_bytes_launch / (k_ms * 1e-3) / 1e9
+        traffic, traffic_note, pmc_j = None, "no PMC summary for this build (profiles/pmc_latest.json is from another libbsx.so)", None
+        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+        if os.path.exists(pmc) and args.mode == "pe":
+            try:
+                pj = json.load(open(pmc))
+                if pj.get("lib_sha16") == sha:
+                    traffic, traffic_note, pmc_j = pj.get("hbm_bytes_per_launch"), f"profiles/{pj.get('tag')}_pmc.json (same libbsx.so, serial mode)", pj
+            except Exception:
+                pass
+        step_s = k_ms * 1e-3
+        wc = bool(args.work_counters)
+        dk = dominant_kernel(serial["counters"], serial["scan_ms"], 2, 1, args.mode == "rrbs", args.mode, wc, B_) if serial else dominant_kernel(counters, scan_ms, args.steps, nfl, args.mode == "rrbs", args.mode, wc, B_)
+        hbm = None
+        if pmc_j:  # what the memory system really moved per step (FETCH_SIZE raw and with the guide's gfx950 x2 rule for wide reads, WRITE_SIZE)
+            raw = pmc_j["fetch_bytes_per_step_raw"] + pmc_j["write_bytes_per_step"]
+            x2 = pmc_j["fetch_bytes_per_step_x2_gfx950"] + pmc_j["write_bytes_per_step"]
+            hbm = {"raw_GBps": raw / step_s / 1e9, "x2_corrected_GBps": x2 / step_s / 1e9, "frac_of_peak_raw": raw / step_s / 1e9 / HBM_PEAK_GBS,
+                   "frac_of_peak_x2": x2 / step_s / 1e9 / HBM_PEAK_GBS, "bytes_per_step_raw": raw, "bytes_per_step_x2": x2,
+                   "note": "measured HBM bytes of one step (PMC passes, serial mode) over the wall time of a step in the timed region"}
+        bound = "VALU issue and the gathers (texture addresser) of the scan kernel, random 64-byte requests of k_align; NOT HBM bandwidth"
+        if hbm:
+            bound += " (HBM carries %.2f-%.2f of its peak)" % (hbm["frac_of_peak_raw"], hbm["frac_of_peak_x2"])
         # The roofline of the dominant kernel against the unit that binds it: `achieved` = candidates per second of k_hscan measured live (HIP events
         # on its stream, device counters), `frac` = the utilisation of its busiest unit (counter passes of this kernel under profiles/), `peak` =
         # achieved / frac — the rate at which that unit would be saturated.  The SURVEY 8(d) formula (algorithmic bytes of a step over its
         # wall time against the HBM peak) is kept under `formula_rate`: it is a rate of ALGORITHMIC bytes, not HBM utilisation — the sorted
         # scan order serves most of those bytes from L2 — and can exceed 1.  `hbm_traffic` is what the memory system really moved.
-        "roofline": roofline_block(dk, bound, achieved, traffic, traffic_note, hbm, k_ms, kernel_ms, heavy_last, alg_bytes_launch, counters, n_reads_rank, args, pmc_j, serial, np),
-    }
+        out["roofline"] = roofline_block(dk, bound, achieved, traffic, traffic_note, hbm, k_ms, kernel_ms, heavy_last, alg_bytes_launch, counters, n_reads_rank, args, pmc_j, serial, np)
     if dumped:
         out["dump_outputs"] = dumped
-    if world == 1 and not args.profile_serial:
-        out["workload_shape"] = workload_shape(ref, counters, args.steps, B_, reads_per_unit, heavy_last[0])
-    if serial_err:
-        out["roofline"]["serial_replay"] = {"error": serial_err}
-    if counted:
-        if "error" in counted:
-            out["roofline"]["with_work_counters"] = counted
-        else:
-            ck = dominant_kernel(counted["counters"], counted["scan_ms"], 2, 1, args.mode == "rrbs", args.mode, True, B_) or {}
-            out["roofline"]["with_work_counters"] = {"serial_ms_per_step": counted["ms_per_step"], "scan_kernel_ms_per_step": ck.get("ms_per_step"), "scan_kernel_candidates_per_s": ck.get("candidates_per_s"),
-                                                     "note": "the same two serial steps with bsx_batch_set_work_counters(1): the scan kernels also classify every candidate by the reference's two early-outs "
-                                                             "(align.h:189-197) — what the parity suite runs, and where the counters of formula_rate come from; the timed region and dominant_kernel run without"}
-    if serial:
-        out["roofline"]["serial_replay"] = {"ms_per_step": serial["ms_per_step"], "event_ms_per_do_batch": serial["event_ms_per_do_batch"],
-                                            "note": "two steps with one batch in flight and one unit group after the timed region: the source of dominant_kernel"}
-    if world == 1 and not args.profile_serial:
-        try:  # measured ceilings of this device beside the spec peak
-            pm = B.probe_memory(local_rank, 4 << 30, 1 << 30)
-            out["roofline"]["peak_measured"] = {"stream_read_GBps": pm["stream_read"], "stream_copy_GBps": pm["stream_copy"],
-                                                "gather16_GBps": pm["gather16"], "gather16_Gloads_per_s": pm["gather16_Gloads_per_s"],
-                                                "frac_of_stream_read": achieved / pm["stream_read"],
-                                                "note": "gather16 = 16-byte loads at random 4-byte-aligned addresses in a 1 GiB window (each moves a 64-byte sector): "
-                                                        "the access pattern of the scan; its rate does not improve for windows down to 64 MiB (profiles/r02e_probe_sweep.json)"}
-            try:
-                fr = fabric_requests(args.mode, wc, B_, out["ms_per_step"], serial["ms_per_step"] if serial else None, pm["gather16_Gloads_per_s"])
-                if fr:
-                    out["roofline"]["fabric_requests"] = fr
+    if args.full:
+        if world == 1 and not args.profile_serial:
+            out["workload_shape"] = workload_shape(ref, counters, args.steps, B_, reads_per_unit, heavy_last[0])
+        if serial_err:
+            out["roofline"]["serial_replay"] = {"error": serial_err}
+        if counted:
+            if "error" in counted:
+                out["roofline"]["with_work_counters"] = counted
+            else:
+                ck = dominant_kernel(counted["counters"], counted["scan_ms"], 2, 1, args.mode == "rrbs", args.mode, True, B_) or {}
+                out["roofline"]["with_work_counters"] = {"serial_ms_per_step": counted["ms_per_step"], "scan_kernel_ms_per_step": ck.get("ms_per_step"), "scan_kernel_candidates_per_s": ck.get("candidates_per_s"),
+                                                         "note": "the same two serial steps with bsx_batch_set_work_counters(1): the scan kernels also classify every candidate by the reference's two early-outs "
+                                                                 "(align.h:189-197) — what the parity suite runs, and where the counters of formula_rate come from; the timed region and dominant_kernel run without"}
+        if serial:
+            out["roofline"]["serial_replay"] = {"ms_per_step": serial["ms_per_step"], "event_ms_per_do_batch": serial["event_ms_per_do_batch"],
+                                                "note": "two steps with one batch in flight and one unit group after the timed region: the source of dominant_kernel"}
+        if world == 1 and not args.profile_serial:
+            try:  # measured ceilings of this device beside the spec peak
+                pm = B.probe_memory(local_rank, 4 << 30, 1 << 30)
+                out["roofline"]["peak_measured"] = {"stream_read_GBps": pm["stream_read"], "stream_copy_GBps": pm["stream_copy"],
+                                                    "gather16_GBps": pm["gather16"], "gather16_Gloads_per_s": pm["gather16_Gloads_per_s"],
+                                                    "frac_of_stream_read": achieved / pm["stream_read"],
+                                                    "note": "gather16 = 16-byte loads at random 4-byte-aligned addresses in a 1 GiB window (each moves a 64-byte sector): "
+                                                            "the access pattern of the scan; its rate does not improve for windows down to 64 MiB (profiles/r02e_probe_sweep.json)"}
+                try:
+                    fr = fabric_requests(args.mode, wc, B_, out["ms_per_step"], serial["ms_per_step"] if serial else None, pm["gather16_Gloads_per_s"])
+                    if fr:
+                        out["roofline"]["fabric_requests"] = fr
+                except Exception as e:
+                    out["roofline"]["fabric_requests"] = {"error": str(e)[:200]}
             except Exception as e:
-                out["roofline"]["fabric_requests"] = {"error": str(e)[:200]}
-        except Exception as e:
-            out["roofline"]["peak_measured"] = {"error": str(e)[:200]}
-    if world == 1 and args.cpu_seconds > 0:
-        try:
-            out["cpu_baseline"] = cpu_baseline(ref, batch, pe, kw, args.cpu_seconds, min(args.warmup, ring - 1) * B_, M["kind"] == 1)
-        except Exception as e:
-            out["cpu_baseline"] = {"error": str(e)[:300]}
-    if args.transfer_steps < 0:
-        args.transfer_steps = args.steps
-    if world == 1 and args.transfer_steps > 0:
-        try:
-            t_slots = min(ring, args.transfer_steps, args.steps)
-            host_reads = [(batch.download_reads(m), batch.download_quals(m) if M["kind"] == 1 else None) for m in range(2 if pe else 1)]
-            for bt in batches:   # (the leg's own batches need the room)
-                bt.close()
-            nt = plan["transfer_leg_batches"]
-            vt = incl_transfers(B, ref, host_reads, Align, pe, B_, min(args.transfer_steps, args.steps), nt, reads_per_unit, t_slots, wc)
-            del host_reads
-            # SURVEY 8(d)'s window is "first batch submitted -> last result returned"; `value` keeps reads and records in HBM (the contract's
-            # definition): the same steps with the PCIe legs inside the window, and how far the two are apart
-            vt["vs_resident"] = vt["value"] / value
-            out["value_incl_transfers"] = vt
-        except Exception as e:
-            out["value_incl_transfers"] = {"error": str(e)[:300]}
+                out["roofline"]["peak_measured"] = {"error": str(e)[:200]}
+        if world == 1 and args.cpu_seconds > 0:
+            try:
+                out["cpu_baseline"] = cpu_baseline(ref, batch, pe, kw, args.cpu_seconds, min(args.warmup, ring - 1) * B_, M["kind"] == 1)
+            except Exception as e:
+                out["cpu_baseline"] = {"error": str(e)[:300]}
+        if args.transfer_steps < 0:
+            args.transfer_steps = args.steps
+        if world == 1 and args.transfer_steps > 0:
+            try:
+                t_slots = min(ring, args.transfer_steps, args.steps)
+                host_reads = [(batch.download_reads(m), batch.download_quals(m) if M["kind"] == 1 else None) for m in range(2 if pe else 1)]
+                for bt in batches:   # (the leg's own batches need the room)
+                    bt.close()
+                nt = plan["transfer_leg_batches"]
+                vt = incl_transfers(B, ref, host_reads, Align, pe, B_, min(args.transfer_steps, args.steps), nt, reads_per_unit, t_slots, wc)
+                del host_reads
+                # SURVEY 8(d)'s window is "first batch submitted -> last result returned"; `value` keeps reads and records in HBM (the contract's
+                # definition): the same steps with the PCIe legs inside the window, and how far the two are apart
+                vt["vs_resident"] = vt["value"] / value
+                out["value_incl_transfers"] = vt
+            except Exception as e:
+                out["value_incl_transfers"] = {"error": str(e)[:300]}
     for bt in batches:
         bt.close()
     ref.close()
-    if world == 1 and args.mode == "pe" and args.sensitivity and not real_fa and not args.profile_serial:
-        out["sensitivity"] = sensitivity(B, Align, kw, lens, read_len, B_, nfl, M["kind"], value)
-    if world == 1 and args.mode == "pe" and args.e2e_pairs > 0:
-        out["end_to_end"] = end_to_end(args.e2e_pairs, args.genome)
-    if world == 1 and args.mode == "pe" and args.other_configs and not args.profile_serial and not args.exact:
-        out["other_configs"] = other_configs(args)
+    if args.full:
+        if world == 1 and args.mode == "pe" and args.sensitivity and not real_fa and not args.profile_serial:
+            out["sensitivity"] = sensitivity(B, Align, kw, lens, read_len, B_, nfl, M["kind"], value)
+        if world == 1 and args.mode == "pe" and args.e2e_pairs > 0:
+            out["end_to_end"] = end_to_end(args.e2e_pairs, args.genome)
+        if world == 1 and args.mode == "pe" and args.other_configs and not args.profile_serial and not args.exact:
+            out["other_configs"] = other_configs(args)
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -785,12 +797,13 @@ def sensitivity(B, Align, kw, lens, read_len, B_, nfl, kind, headline):
 
 def other_configs(args):
     """BASELINE.json's other single-GPU configs, each in a child process of its own (this process has released its device memory): the same
-    timed region as the metric's (inputs in HBM, barrier + synchronize on both sides), fewer steps, none of the side legs.  A child that fails
+    timed region as the metric's (inputs in HBM, barrier + synchronize on both sides), fewer steps, --full for the replays behind its roofline
+    but none of the side legs.  A child that fails
     is reported with its return code and the end of its stderr, and tried once more with two batches in flight."""
     import subprocess
     res = {}
     for mode in ("se", "rrbs", "trim"):
-        base = [sys.executable, os.path.abspath(__file__), "--mode", mode, "--steps", "6", "--warmup", "3", "--genome", str(args.genome),
+        base = [sys.executable, os.path.abspath(__file__), "--mode", mode, "--steps", "6", "--warmup", "3", "--genome", str(args.genome), "--full",
                 "--cpu-seconds", "0", "--transfer-steps", "0", "--e2e-pairs", "0", "--other-configs", "0"]
         if getattr(args, "units_given", False):   # (otherwise every mode runs its own default step size)
             base += ["--pairs-per-step", str(args.pairs_per_step)]

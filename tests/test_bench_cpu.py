@@ -63,6 +63,21 @@ def test_other_configs_runs_every_other_mode_in_a_child(monkeypatch):
     assert res["C5"]["failed_attempts"][0]["rc"] == -9
 
 
+def test_side_legs_are_behind_full_and_the_other_configs_children_ask_for_it(monkeypatch):
+    """a plain run prints the headline alone: --full (off by default) turns on the legs with runs of their own, and the other_configs
+    children, whose roofline the parent copies, pass it themselves"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout
+    calls = []
+
+    def fake_run(cmd, capture_output, text, timeout):
+        calls.append(cmd)
+        return types.SimpleNamespace(stdout="", stderr="no line", returncode=1)
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    BN.other_configs(types.SimpleNamespace(genome="0.05", pairs_per_step=1 << 16, units_given=True))
+    assert len(calls) == 6 and all("--full" in c for c in calls)
+
+
 def test_roofline_block_is_flat_short_and_priced_against_the_microbenchmark():
     """the driver's record keeps scalars and the first 120 characters of a string: `bound` fits, `frac` = achieved / peak with the peak taken from the
     microbenchmark's ceiling of the kernel's inner word (not from achieved / utilisation), instructions per evaluation and the per-kernel serial times are top-level"""

@@ -20,7 +20,7 @@ KW = dict(s=16, v=6, I=4, m=28, x=500, S=1, r=1, pairend=1)
 
 def _bench(env_extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--genome", FRACTION, "--steps", "2", "--warmup", "1", "--pairs-per-step", "65536", "--cpu-seconds", "0",
-           "--e2e-pairs", "0", "--transfer-steps", "0", "--sensitivity", "0", "--other-configs", "0"]
+           "--e2e-pairs", "0", "--transfer-steps", "0", "--sensitivity", "0", "--other-configs", "0", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, **env_extra))
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

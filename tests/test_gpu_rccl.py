@@ -13,7 +13,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--gpus", "1", "--genome", "0.02", "--pairs-per-step", "65536", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--e2e-pairs", "0", "--transfer-steps", "0",
-        "--sensitivity", "0", "--other-configs", "0", "--work-counters", "1"]
+        "--sensitivity", "0", "--other-configs", "0", "--work-counters", "1", "--full"]
 
 
 def _line(out):

@@ -1,9 +1,9 @@
 # GPU box: the default bench line (C3, all legs) and the C2 / C4 / C5 lines.  usage: bash tools/bench_all.sh <tag>
 TAG=${1:-r02}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
-timeout 1200 python3 bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "default rc=$?"
+timeout 1200 python3 bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "default rc=$?"
 for m in se rrbs trim; do
-  timeout 900 python3 bench.py --mode $m --e2e-pairs 0 > $O/${TAG}_bench_$m.json 2> $O/${TAG}_bench_$m.err; echo "$m rc=$?"
+  timeout 900 python3 bench.py --full --mode $m --e2e-pairs 0 > $O/${TAG}_bench_$m.json 2> $O/${TAG}_bench_$m.err; echo "$m rc=$?"
 done
 python3 - <<PY
 import json

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 i=0
 for e in "$@"; do
   i=$((i+1))
-  env $e timeout 600 python3 bench.py --mode $M --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --steps 6 --warmup 2 --in-flight $NF > $O/b_$i.json 2> $O/b_$i.err
+  env $e timeout 600 python3 bench.py --full --mode $M --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --steps 6 --warmup 2 --in-flight $NF > $O/b_$i.json 2> $O/b_$i.err
   python3 -c "
 import json
 try:

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 i=0
 for a in "$@"; do
   i=$((i+1))
-  timeout 600 python3 bench.py --cpu-seconds 0 --e2e-pairs 0 $a > $O/${TAG}_$i.json 2> $O/${TAG}_$i.err
+  timeout 600 python3 bench.py --full --cpu-seconds 0 --e2e-pairs 0 $a > $O/${TAG}_$i.json 2> $O/${TAG}_$i.err
   python3 - <<PY
 import json
 try:

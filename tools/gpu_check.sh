@@ -3,7 +3,7 @@ TAG=${1:-chk}; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 cd $R
 timeout 1500 python3 -m pytest tests -m gpu -x -q "$@" > $O/${TAG}_pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/${TAG}_pytest.log
-timeout 600 python3 bench.py --profile-serial --steps 3 --warmup 1 > $O/${TAG}_bench_serial.json 2> $O/${TAG}_bench_serial.err; echo "serial rc=$?"
+timeout 600 python3 bench.py --full --profile-serial --steps 3 --warmup 1 > $O/${TAG}_bench_serial.json 2> $O/${TAG}_bench_serial.err; echo "serial rc=$?"
 python3 - <<PY
 import json
 try:

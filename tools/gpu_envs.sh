@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 i=0
 for e in "$@"; do
   i=$((i+1))
-  env $e timeout 600 python3 bench.py --profile-serial --steps 3 --warmup 1 > $O/${TAG}_$i.json 2> $O/${TAG}_$i.err
+  env $e timeout 600 python3 bench.py --full --profile-serial --steps 3 --warmup 1 > $O/${TAG}_$i.json 2> $O/${TAG}_$i.err
   python3 - <<PY
 import json
 try:

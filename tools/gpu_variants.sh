@@ -3,7 +3,7 @@ TAG=$1; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R
 for v in default "$@"; do
   if [ $v = default ]; then unset BSX_LIB; else export BSX_LIB=$R/bsmap_amd/libbsx_$v.so; fi
-  timeout 600 python3 bench.py --profile-serial --steps 3 --warmup 1 > $O/${TAG}_$v.json 2> $O/${TAG}_$v.err
+  timeout 600 python3 bench.py --full --profile-serial --steps 3 --warmup 1 > $O/${TAG}_$v.json 2> $O/${TAG}_$v.err
   python3 - <<PY
 import json
 try:

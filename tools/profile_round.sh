@@ -12,8 +12,8 @@ export BSX_PROFILE_MODE=pe BSX_PROFILE_WORK_COUNTERS=0 BSX_PROFILE_STEPS=3   # (
 S=/tmp/bsx_prof_$$; mkdir -p $S
 cd $R
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $S/stats -o s --output-format csv -- python3 $R/bench.py --profile-serial --steps 3 --warmup 1 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 > $O/${TAG}_bench_serial.json 2> $S/stats.log; echo "stats rc=$?"
-rocprofv3 --kernel-trace --stats -d $S/stats_default -o s --output-format csv -- python3 $R/bench.py --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 --steps 4 --warmup 2 > $O/${TAG}_bench_under_rocprof.json 2> $S/stats_default.log; echo "stats default rc=$?"
+rocprofv3 --kernel-trace --stats -d $S/stats -o s --output-format csv -- python3 $R/bench.py --full --profile-serial --steps 3 --warmup 1 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 > $O/${TAG}_bench_serial.json 2> $S/stats.log; echo "stats rc=$?"
+rocprofv3 --kernel-trace --stats -d $S/stats_default -o s --output-format csv -- python3 $R/bench.py --full --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 --steps 4 --warmup 2 > $O/${TAG}_bench_under_rocprof.json 2> $S/stats_default.log; echo "stats default rc=$?"
 cut -c1-160 $S/stats_default/s_kernel_stats.csv > $O/${TAG}_default_kernel_stats.csv
 for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS" "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM SQ_WAIT_ANY SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE" "TA_TA_BUSY_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_LDS_ADDR_CONFLICT" "FETCH_SIZE" "WRITE_SIZE"; do
   t=$(echo $set | cut -d' ' -f1)
@@ -37,14 +37,14 @@ for m in se rrbs trim; do
 done
 export BSX_PROFILE_MODE=pe
 cd $R
-timeout 1200 python3 bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "default rc=$?"
+timeout 1200 python3 bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; echo "default rc=$?"
 for m in se rrbs trim; do
-  timeout 900 python3 bench.py --mode $m --e2e-pairs 0 > $O/${TAG}_bench_$m.json 2> $O/${TAG}_bench_$m.err; echo "$m rc=$?"
+  timeout 900 python3 bench.py --full --mode $m --e2e-pairs 0 > $O/${TAG}_bench_$m.json 2> $O/${TAG}_bench_$m.err; echo "$m rc=$?"
 done
-timeout 900 python3 bench.py --mode trim --in-flight 2 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 > $O/${TAG}_bench_trim_f2.json 2> $O/${TAG}_bench_trim_f2.err; echo "trim f2 rc=$?"
-timeout 900 python3 bench.py --mode trim --exact --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 > $O/${TAG}_bench_trim_exact.json 2> $O/${TAG}_bench_trim_exact.err; echo "trim exact rc=$?"
+timeout 900 python3 bench.py --full --mode trim --in-flight 2 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 > $O/${TAG}_bench_trim_f2.json 2> $O/${TAG}_bench_trim_f2.err; echo "trim f2 rc=$?"
+timeout 900 python3 bench.py --full --mode trim --exact --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 > $O/${TAG}_bench_trim_exact.json 2> $O/${TAG}_bench_trim_exact.err; echo "trim exact rc=$?"
 timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_command.json 2> $O/${TAG}_bench_driver_command.err; echo "driver's command rc=$?"
-timeout 900 python3 bench.py --in-flight 1 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 > $O/${TAG}_bench_one_in_flight.json 2> $O/${TAG}_bench_one_in_flight.err; echo "one in flight rc=$?"
+timeout 900 python3 bench.py --full --in-flight 1 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 > $O/${TAG}_bench_one_in_flight.json 2> $O/${TAG}_bench_one_in_flight.err; echo "one in flight rc=$?"
 [ -n "$HOST" ] && { bash $R/tools/host_ceiling.sh ${TAG} > $O/${TAG}_host_ceiling.txt 2>&1; cp $R/gpurun_out/${TAG}_hc_*.json $O/ 2>/dev/null; cat $O/${TAG}_host_ceiling.txt; }   # (HOST=1: the host-side legs, unchanged since round 4)
 $R/tools/microbench/valu_issue > $O/${TAG}_valu_issue.json 2>/dev/null; echo "valu rc=$?"
 $R/tools/microbench/gather_cost > $O/${TAG}_gather_cost.json 2>/dev/null; echo "gather rc=$?"
@@ -55,9 +55,9 @@ timeout 1500 python3 tools/validate_fullsize.py --mode pe > $O/${TAG}_validate_f
 # k_hscan_shared (its default) and through k_hscan_same (BSX_SAME=2); and the histogram of tasks per identical window / window and read offset
 for m in pe se rrbs; do for v in 1 0 2; do
   if [ $m = rrbs ]; then [ $v = 0 ] && continue; else [ $v = 2 ] && continue; fi
-  BSX_SAME=$v timeout 600 python3 bench.py --mode $m --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 --steps 8 --warmup 2 > $O/${TAG}_ab_${m}_same$v.json 2>/dev/null
+  BSX_SAME=$v timeout 600 python3 bench.py --full --mode $m --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 --steps 8 --warmup 2 > $O/${TAG}_ab_${m}_same$v.json 2>/dev/null
   python3 -c "
 import json
 d=json.load(open('$O/${TAG}_ab_${m}_same$v.json')); k=d['roofline']['dominant_kernel']; print('$m BSX_SAME=$v: %.1f ms/step %.2f M reads/s | %s %.1f ms/step %.0f G candidates/s' % (d['ms_per_step'], d['value']/1e6, k['name'], k['ms_per_step'], k['candidates_per_s']/1e9))"
 done; done
-BSX_SIGHIST=1 timeout 600 python3 bench.py --in-flight 1 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 --steps 2 --warmup 1 2>&1 >/dev/null | grep sighist > $O/${TAG}_sighist.txt; head -3 $O/${TAG}_sighist.txt
+BSX_SIGHIST=1 timeout 600 python3 bench.py --full --in-flight 1 --cpu-seconds 0 --e2e-pairs 0 --transfer-steps 0 --sensitivity 0 --other-configs 0 --steps 2 --warmup 1 2>&1 >/dev/null | grep sighist > $O/${TAG}_sighist.txt; head -3 $O/${TAG}_sighist.txt
