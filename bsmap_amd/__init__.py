@@ -45,7 +45,9 @@ CC_DTYPE = np.dtype([("n_hit", "<u2", 16), ("n_chit", "<u2", 16)])
 PAIR_DTYPE = np.dtype([("a_chr", "<u4"), ("a_loc", "<u4"), ("b_chr", "<u4"), ("b_loc", "<u4"), ("insert", "<i4"),
                        ("n_pairs", "<u2"), ("pair_class", "i1"), ("chain", "u1"), ("na", "u1"), ("nb", "u1"),
                        ("paired", "u1"), ("unpaired_out", "u1"), ("pad_", "<u4"), ("a", HIT_DTYPE), ("b", HIT_DTYPE)])
-assert HIT_DTYPE.itemsize == 16 and PAIR_DTYPE.itemsize == 64 and CC_DTYPE.itemsize == 64
+SPAN_DTYPE = np.dtype([("off", "<u8"), ("n", "<u4"), ("n_fwd", "<u4")])   # bsx_span (include/bsx.h: all hits)
+SPAN_DROPPED = 0xFFFFFFFFFFFFFFFF
+assert HIT_DTYPE.itemsize == 16 and PAIR_DTYPE.itemsize == 64 and CC_DTYPE.itemsize == 64 and SPAN_DTYPE.itemsize == 16
 
 _lib = None
 
@@ -66,7 +68,7 @@ EXPORTS = [
     "bsx_batch_create", "bsx_batch_destroy", "bsx_batch_upload_se", "bsx_batch_upload_pe", "bsx_batch_synth_reads", "bsx_batch_synth_reads_kind", "bsx_batch_download_quals",
     "bsx_batch_run", "bsx_batch_run_range", "bsx_batch_sync", "bsx_batch_set_work_counters", "bsx_batch_set_leak_exact", "bsx_batch_set_history", "bsx_batch_set_leak_state", "bsx_batch_get_leak_state", "bsx_batch_kernel_ms", "bsx_batch_scan_ms", "bsx_batch_set_stage_timing", "bsx_batch_stage_ms", "bsx_batch_results_se", "bsx_batch_results_pe",
     "bsx_batch_counters", "bsx_batch_reset_counters", "bsx_batch_download_reads", "bsx_batch_set_debug", "bsx_batch_unit_cycles", "bsx_batch_ctrl_clocks",
-    "bsx_batch_debug_hits", "bsx_batch_debug_pairs", "bsx_batch_debug_plan", "bsx_set_waves_per_cu", "bsx_set_heavy_threshold", "bsx_set_heavy_limits", "bsx_set_pool_reserve", "bsx_default_heavy_limits", "bsx_batch_pool_sizes", "bsx_batch_plan_bytes", "bsx_batch_last_heavy_units", "bsx_batch_last_heavy_list", "bsx_batch_last_redo_units", "bsx_pinned_alloc", "bsx_pinned_free", "bsx_probe_memory", "bsx_thread_device",
+    "bsx_batch_debug_hits", "bsx_batch_debug_pairs", "bsx_batch_debug_plan", "bsx_batch_set_all_hits", "bsx_batch_all_hits_need", "bsx_batch_all_hits_spans", "bsx_batch_all_hits_fetch", "bsx_set_waves_per_cu", "bsx_set_heavy_threshold", "bsx_set_heavy_limits", "bsx_set_pool_reserve", "bsx_default_heavy_limits", "bsx_batch_pool_sizes", "bsx_batch_plan_bytes", "bsx_batch_last_heavy_units", "bsx_batch_last_heavy_list", "bsx_batch_last_redo_units", "bsx_pinned_alloc", "bsx_pinned_free", "bsx_probe_memory", "bsx_thread_device",
     "bsx_meth_create", "bsx_meth_destroy", "bsx_meth_set_reference", "bsx_meth_add", "bsx_meth_combine_cpg", "bsx_meth_valid_mappings",
     "bsx_meth_report_chr", "bsx_meth_fetch_rows", "bsx_meth_add_file", "bsx_meth_write_table", "bsx_meth_create_from_fasta", "bsx_meth_n_chr", "bsx_meth_chr_name",
 ]
@@ -154,6 +156,10 @@ def lib():
         L.bsx_batch_set_stage_timing.argtypes = [vp, i32]
         L.bsx_batch_last_heavy_list.argtypes = [vp, vp, u32]
         L.bsx_probe_memory.argtypes = [i32, u64, u64, vp, vp, vp, vp]
+        L.bsx_batch_set_all_hits.argtypes = [vp, u64]
+        L.bsx_batch_all_hits_need.argtypes = [vp, vp, vp]
+        L.bsx_batch_all_hits_spans.argtypes = [vp, vp]
+        L.bsx_batch_all_hits_fetch.argtypes = [vp, vp, u64, vp]
         _lib = L
     return _lib
 
@@ -455,6 +461,30 @@ class _Batch:
         n = _check(lib().bsx_batch_debug_hits(self.h, unit, mate, orient, w, buf.ctypes.data, 1100))
         return [(int(buf[2 * i]), int(buf[2 * i + 1])) for i in range(n)]
 
+    def set_all_hits(self, pool_words):
+        """attach an all-hits pool of pool_words 32-bit words (0 detaches and frees it): every later run also keeps the best class's whole
+        list of every multi-mapped read / pair (include/bsx.h).  Needs -r 1"""
+        _check(lib().bsx_batch_set_all_hits(self.h, int(pool_words)))
+        return self
+
+    def all_hits_need(self):
+        """(words the last run wanted in all, units it dropped because the pool was too small)"""
+        w, d = C.c_uint64(), C.c_uint32()
+        _check(lib().bsx_batch_all_hits_need(self.h, C.addressof(w), C.addressof(d)))
+        return w.value, d.value
+
+    def all_hits(self, n_units=None):
+        """(spans, pool) of the last run: spans[unit][3] as SPAN_DTYPE (read or mate a, mate b, pairs; unit 0 = the run's first unit),
+        pool = the used words as uint32.  n_units: units of the last run if it was a run_range (default: the whole batch)"""
+        n = self.n if n_units is None else n_units
+        spans = np.zeros((n, 3), SPAN_DTYPE)
+        _check(lib().bsx_batch_all_hits_spans(self.h, spans.ctypes.data))
+        used = C.c_uint64()
+        _check(lib().bsx_batch_all_hits_fetch(self.h, None, 0, C.addressof(used)))
+        pool = np.zeros(max(1, used.value), np.uint32)
+        _check(lib().bsx_batch_all_hits_fetch(self.h, pool.ctypes.data, pool.size, C.addressof(used)))
+        return spans, pool[:used.value]
+
     def debug_plan(self, unit, mate=0):
         s, o = np.zeros(32, np.int32), np.zeros(32, np.int32)
         _check(lib().bsx_batch_debug_plan(self.h, unit, mate, s.ctypes.data, o.ctypes.data))
@@ -529,3 +559,24 @@ class PairAlign(_Batch):
             t, ins, ac, al, bc, bl = (int(x) for x in buf[6 * i:6 * i + 6])
             out.append((t & 0xffff, (t >> 16) & 0xff, t >> 24, np.int32(np.uint32(ins)).item(), ac, al, bc, bl))
         return out
+
+
+def all_hits_lists(spans3, pool):
+    """one unit's spans -> (hits_a, hits_b, pairs) as the Python lists debug_hits / debug_pairs return: hits = [(chr, loc), ...] (forward
+    list then reverse-complement list; the first span's n_fwd are forward), pairs = [(chain, na, nb, insert, a_chr, a_loc, b_chr, b_loc), ...].
+    A span that emitted nothing gives []; a dropped span (off == SPAN_DROPPED: it did not fit the pool) gives None."""
+    out = []
+    for k in range(3):
+        off, n = int(spans3[k]["off"]), int(spans3[k]["n"])
+        if n == 0:
+            out.append([])
+        elif off == SPAN_DROPPED:
+            out.append(None)
+        elif k < 2:
+            w = pool[off:off + 2 * n].reshape(n, 2)
+            out.append([(int(c), int(l)) for c, l in w])
+        else:
+            w = pool[off:off + 6 * n].reshape(n, 6)
+            out.append([(int(t) & 0xffff, (int(t) >> 16) & 0xff, int(t) >> 24, np.int32(np.uint32(ins)).item(), int(ac), int(al), int(bc), int(bl))
+                        for t, ins, ac, al, bc, bl in w])
+    return tuple(out)

@@ -57,7 +57,13 @@ struct Opts {
     // the reference's -B / -E shards (README.txt:83-86) on one node; --lane-files: leave one output file per lane (<out>.<lane>)
     int lanes = 0;                  // 0 off, -1 one per device, N
     bool lane_files = false;
+    // --all-hits=FILE: a side file with every equal-best placement of the multi-mapped reads and pairs (bsx.h: bsx_batch_set_all_hits); the main output is untouched
+    string all_hits;
 };
+// --all-hits: words of a batch's pool per unit of the batch — twice what the hungrier bench workload wants (C2: 2.387 words per read, C3: 0.00001 per pair;
+// tools/all_hits_cost.py, DESIGN.md "All hits").  A batch that wants more is run again with what it asked for.
+#define BSX_ALL_HITS_WORDS_X100 478u
+#define BSX_ALL_HITS_HEADER "#name\tkind\tk\tn\tchr\tpos\tstrand\tmismatches\t(kind 0: single read, 1 / 2: mate of an unreported pair)\t|\tname\tP\tk\tn\tchr\tpos_a\tstrand_a\tpos_b\tstrand_b\tinsert\tna\tnb\n"
 
 // what a lane process knows about its place in the run (index < 0: the ordinary single pipeline)
 struct LaneInfo {
@@ -126,6 +132,9 @@ void usage()
          << "                   like -B / -E shards on one node; the output is joined in input order (extension).  Joining copies every byte but\n"
          << "                   the first lane's at 3-3.5 GB/s: on one GPU it costs more than the lanes gain - use --lane-files at scale\n"
          << "       --lane-files  with --lanes: leave one output file per range, <out>.<lane>, no join (extension)\n"
+         << "       --all-hits=FILE  also write every equal-best placement of the multi-mapped reads and pairs to FILE, tab-separated, in input\n"
+         << "                   order (one line per placement; the line whose k is the reported pick repeats the main output's RNAME, POS and ZS:Z).\n"
+         << "                   Needs -r 1; the main output does not change; with --lanes: FILE.<lane>, joined unless --lane-files (extension)\n"
          << "       -h          help\n\n";
     exit(1);
 }
@@ -139,6 +148,7 @@ int parse_options(int argc, char **argv, Opts &o)
         if (argv[i][0] != '-') return i;
         if (!strncmp(argv[i], "--lanes", 7) && (argv[i][7] == 0 || argv[i][7] == '=')) { o.lanes = argv[i][7] ? max(1, atoi(argv[i] + 8)) : -1; continue; }
         if (!strcmp(argv[i], "--lane-files")) { o.lane_files = true; if (!o.lanes) o.lanes = -1; continue; }
+        if (!strncmp(argv[i], "--all-hits=", 11)) { if (!argv[i][11]) return i; o.all_hits = argv[i] + 11; continue; }
         const char c = argv[i][1];
         const char *val = nullptr;
         const bool flag_only = (c == 'R' || c == 'u' || c == 'h');
@@ -335,6 +345,38 @@ struct Formatter {
         m[k - 1] += 32; m[k - 2] += 32;
         os.uput(m, k);
     }
+    // RNAME <tab> POS and the two characters of ZS:Z of a placement: the SAM lines below and the --all-hits side file print them through these
+    inline void uput_place(uint32_t chr, uint32_t loc, Text &os) const { os.uput(rv.names[chr >> 1]); os.uput('\t'); os.uput_u(loc + 1); }
+    inline void uput_zs(int strand, int chain, Text &os) const { os.uput(chain_flag[strand]); os.uput(chain_flag[chain]); }
+    // s_OutHitPair's cut of a read-through (pairs.cpp:296-311): a fragment shorter than the read moves the start of the mate on the reverse strand
+    static void cut_read_through(uint32_t &a_loc, uint32_t &b_loc, int insert, int chain, uint32_t a_chr, uint32_t b_chr, size_t alen, size_t blen)
+    {
+        if (insert < (int)alen && (chain ^ (int)(a_chr % 2))) a_loc += (uint32_t)alen - insert;
+        if (insert < (int)blen && ((!chain) ^ (int)(b_chr % 2))) b_loc += (uint32_t)blen - insert;
+    }
+    // --all-hits: the lines of one list of a read or mate (kind 0, 1, 2), entries {chr, loc}, the first n_fwd on the read's forward orientation
+    void all_hits_read(const char *name, size_t nlen, int kind, const uint32_t *e, uint32_t n, uint32_t n_fwd, int nsnps, Text &os) const
+    {
+        for (uint32_t k = 0; k < n; k++) {
+            os.need(nlen + g_rec_max);
+            os.uput(name, nlen); os.uput('\t'); os.uput_i(kind); os.uput('\t'); os.uput_u(k); os.uput('\t'); os.uput_u(n); os.uput('\t');
+            uput_place(e[2 * k], e[2 * k + 1], os); os.uput('\t'); uput_zs((int)(e[2 * k] % 2), k >= n_fwd ? 1 : 0, os); os.uput('\t'); os.uput_i(nsnps); os.uput('\n');
+        }
+    }
+    // ... and of a pair list, entries {chain | na<<16 | nb<<24, insert, a.chr, a.loc, b.chr, b.loc}; alen / blen: the mates' lengths after trimming
+    void all_hits_pairs(const char *name, size_t nlen, const uint32_t *e, uint32_t n, size_t alen, size_t blen, Text &os) const
+    {
+        for (uint32_t k = 0; k < n; k++, e += 6) {
+            const int chain = (int)(e[0] & 0xffff), insert = (int)e[1];
+            uint32_t a_loc = e[3], b_loc = e[5];
+            cut_read_through(a_loc, b_loc, insert, chain, e[2], e[4], alen, blen);
+            os.need(nlen + g_rec_max);
+            os.uput(name, nlen); os.uput("\tP\t"); os.uput_u(k); os.uput('\t'); os.uput_u(n); os.uput('\t');
+            uput_place(e[2], a_loc, os); os.uput('\t'); uput_zs((int)(e[2] % 2), chain, os); os.uput('\t');
+            os.uput_u(b_loc + 1); os.uput('\t'); uput_zs((int)(e[4] % 2), !chain, os); os.uput('\t');
+            os.uput_i(insert); os.uput('\t'); os.uput_u((e[0] >> 16) & 0xff); os.uput('\t'); os.uput_u(e[0] >> 24); os.uput('\n');
+        }
+    }
     void put_unmapped(const Rd &r, int flag, Text &os) const
     {
         os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput("\t*\t0\t0\t*\t*\t0\t0\t"); os.uput(r.seq, r.slen); os.uput('\t'); os.uput(r.qual, r.qlen); os.uput('\n');
@@ -357,12 +399,12 @@ struct Formatter {
             n_aligned++;
             if (n > 1) flag |= 0x100;
             if (rev) { flag |= 0x10; r.revcomp_seq(); r.reverse_qual(); }
-            os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput('\t'); os.uput(rv.names[chr >> 1]); os.uput('\t'); os.uput_u(loc + 1);
+            os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput('\t'); uput_place(chr, loc, os);
             os.uput("\t255\t"); os.uput_u(r.slen); os.uput("M\t*\t0\t0\t"); os.uput(r.seq, r.slen); os.uput('\t'); os.uput(r.qual, r.qlen);
             os.uput("\tNM:i:"); os.uput_i(nsnps);
             if (o.out_ref) { os.uput("\tXR:Z:"); put_map_seq(chr, loc, r.slen, os); }
             if (p.rrbs) { uint32_t f; int s; rv.seglen(chr, loc, (int)r.slen, f, s); os.uput("\tZP:i:"); os.uput_i((int)f); os.uput("\tZL:i:"); os.uput_i(s); }
-            os.uput("\tZS:Z:"); os.uput(chain_flag[chr % 2]); os.uput(chain_flag[chain]); os.uput('\n');
+            os.uput("\tZS:Z:"); uput_zs((int)(chr % 2), chain, os); os.uput('\n');
             return;
         }
         // BSP
@@ -392,7 +434,7 @@ struct Formatter {
             if (!pair_tags) rv.seglen(chr, loc, (int)r.slen, f, s);
             os.uput("\tZP:i:"); os.uput_i((int)f); os.uput("\tZL:i:"); os.uput_i(s);
         }
-        os.uput("\tZS:Z:"); os.uput(chain_flag[strand]); os.uput(chain_flag[chain]); os.uput('\n');
+        os.uput("\tZS:Z:"); uput_zs(strand, chain, os); os.uput('\n');
     }
 
     // PairAlign::s_OutHitPair (pairs.cpp:288-424)
@@ -400,13 +442,12 @@ struct Formatter {
     {
         const int n = pp.n_pairs;
         n_aligned_pairs++;
+        cut_read_through(pp.a_loc, pp.b_loc, pp.insert, pp.chain, pp.a_chr, pp.b_chr, a.slen, b.slen);
         if (pp.insert < (int)a.slen) {  // fragment shorter than the read: cut the read-through
-            if (pp.chain ^ (pp.a_chr % 2)) pp.a_loc += (uint32_t)a.slen - pp.insert;
             a.slen = (size_t)pp.insert;
             if ((int)a.qlen > pp.insert) a.qlen = (size_t)pp.insert;
         }
         if (pp.insert < (int)b.slen) {
-            if ((!pp.chain) ^ (pp.b_chr % 2)) pp.b_loc += (uint32_t)b.slen - pp.insert;
             b.slen = (size_t)pp.insert;
             if ((int)b.qlen > pp.insert) b.qlen = (size_t)pp.insert;
         }
@@ -425,7 +466,7 @@ struct Formatter {
             if (chain ^ (int)(chr % 2)) { flag |= 0x10; seg_start = mloc + 1; pp_insert = -pp.insert; r.revcomp_seq(); r.reverse_qual(); }
             else { flag |= 0x20; seg_start = loc + 1; pp_insert = pp.insert; }
             flag |= 0x40 * (mate + 1);
-            os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput('\t'); os.uput(rv.names[chr >> 1]); os.uput('\t'); os.uput_u(loc + 1);
+            os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput('\t'); uput_place(chr, loc, os);
             os.uput("\t255\t"); os.uput_u(r.slen); os.uput("M\t=\t"); os.uput_u(mloc + 1); os.uput('\t'); os.uput_i(pp_insert); os.uput('\t');
             os.uput(r.seq, r.slen); os.uput('\t'); os.uput(r.qual, r.qlen); os.uput("\tNM:i:"); os.uput_i(mate ? pp.nb : pp.na);
             sam_tail(r, chr, loc, true, seg_start, pp.insert, chr % 2, chain, os);
@@ -460,7 +501,7 @@ struct Formatter {
         if (chain_a ^ (int)(me.chr % 2)) { flag |= 0x010; r.revcomp_seq(); r.reverse_qual(); }
         if (mate_unmapped) flag |= 0x008;
         else if (chain_b ^ (int)(mate.chr % 2)) flag |= 0x020;
-        os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput('\t'); os.uput(rv.names[me.chr >> 1]); os.uput('\t'); os.uput_u(me.loc + 1);
+        os.uput(r.name, r.nlen); os.uput('\t'); os.uput_i(flag); os.uput('\t'); uput_place(me.chr, me.loc, os);
         os.uput("\t255\t"); os.uput_u(r.slen); os.uput("M\t");
         if (mate_unmapped) os.uput("*\t0");
         else { os.uput(rv.names[mate.chr >> 1]); os.uput('\t'); os.uput_u(mate.loc + 1); }
@@ -527,6 +568,9 @@ struct Slot {
     Buf<bsx_pair> pairs;
     Buf<bsx_class_counts> cca, ccb;
     vector<Text> out, out_unpair;
+    vector<bsx_span> spans;      // --all-hits: [n][3], the words they point into, the side file's lines by format worker
+    vector<uint32_t> ah_words;
+    vector<Text> out_all;
     int stage = 0;  // 0 free, 1 parsed, 2 aligned, 3 formatted
     long batch = -1;  // ordinal of the batch the slot holds while stage != 0
 };
@@ -643,7 +687,7 @@ int fork_lanes(Opts &o, LaneInfo &lane, time_t t_begin)
     vector<int> fds(L, -1), sfds(L, -1);
     int ready[2], go[2];
     if (pipe(ready) != 0 || pipe(go) != 0) { cerr << "bsx: pipe failed\n"; exit(1); }
-    const string out0 = o.out_file, unpair0 = o.out_unpair;
+    const string out0 = o.out_file, unpair0 = o.out_unpair, all0 = o.all_hits;
     const vector<int> devs = o.devices;
     const unsigned end0 = o.read_end;
     cout.flush(); cerr.flush();
@@ -667,6 +711,7 @@ int fork_lanes(Opts &o, LaneInfo &lane, time_t t_begin)
             o.devices.assign(1, devs[(size_t)l % devs.size()]);
             o.out_file = out0 + "." + to_string(l);
             if (!unpair0.empty()) o.out_unpair = unpair0 + "." + to_string(l);
+            if (!all0.empty()) o.all_hits = all0 + "." + to_string(l);
             if (l > 0) { if (!freopen("/dev/null", "w", stdout)) {} }   // lane 0 keeps the reference's progress lines
             return l;
         }
@@ -728,6 +773,11 @@ int fork_lanes(Opts &o, LaneInfo &lane, time_t t_begin)
         for (int l = 0; l < L; l++) { parts.push_back(out0 + "." + to_string(l)); if (!unpair0.empty() && !o.out_sam && pe) parts2.push_back(unpair0 + "." + to_string(l)); }
         bsx_textout::install_sigbus_handler();   // (the join writes through shared mappings of a sparsely extended file: a full tmpfs is a SIGBUS here, too)
         if (!join_files(out0, parts, (int)ncpu) || (!parts2.empty() && !join_files(unpair0, parts2, (int)ncpu))) { cerr << "write error on the output file (joining the lanes)\n"; exit(1); }
+        if (!all0.empty()) {   // (lane 0's file carries the header line)
+            vector<string> parts3;
+            for (int l = 0; l < L; l++) parts3.push_back(all0 + "." + to_string(l));
+            if (!join_files(all0, parts3, (int)ncpu)) { cerr << "write error on the --all-hits file (joining the lanes)\n"; exit(1); }
+        }
     }
     const double join_s = now_s() - t_join0;
     char pct[64];
@@ -775,6 +825,10 @@ int main(int argc, char **argv)
     int rc = bsx_params_finish(&o.p);
     if (rc) die(rc, "bad option value");
     const bsx_params &p = o.p;
+    if (!o.all_hits.empty() && p.report_repeat_hits != 1) {
+        cerr << "--all-hits needs -r 1: with -r 0 a scan stops at the second hit of the best class and the lists are cut short\n";
+        exit(1);
+    }
     { ifstream t(o.ref_file.c_str()); if (!t) { cerr << "fatal error: failed to open ref file\n"; exit(1); } }
     // --lanes: from here on a lane process sees its own range of reads, its GPU and its output file; the parent does not come back
     LaneInfo lane;
@@ -937,6 +991,14 @@ int main(int argc, char **argv)
         fout_unpair = ::open(o.out_unpair.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
         if (fout_unpair < 0) { cerr << "failed to open output file for unpaired hits (check -2 option): " << o.out_unpair << endl; exit(1); }
     }
+    const bool all_on = !o.all_hits.empty();
+    int fout_all = -1;
+    off_t off_all = 0;
+    if (all_on) {
+        fout_all = ::open(o.all_hits.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fout_all < 0) { cerr << "failed to open the --all-hits file: " << o.all_hits << endl; exit(1); }
+        if (lane.index <= 0 || o.lane_files) { static const char hd[] = BSX_ALL_HITS_HEADER; write_all(fout_all, hd, sizeof hd - 1, 0); off_all = (off_t)(sizeof hd - 1); }
+    }
     // GPU-stage thread g drives device batch g: batches k = g, g+NG, ... of the input; thread g works on GPU g % ND, so
     // consecutive batches go to different GPUs (the reference's worker pool, main.cpp:74-84,116-131, with GPUs for threads)
     vector<bsx_batch *> batches(NG, nullptr);
@@ -946,6 +1008,10 @@ int main(int argc, char **argv)
         // nothing the command line prints depends on the work counters (the reference has none): the scan kernels skip the classification
         // that only they need (include/bsx.h; BSX_WORK_COUNTERS=1 keeps them, for diagnostics)
         if (!getenv("BSX_WORK_COUNTERS")) bsx_batch_set_work_counters(batches[g], 0);
+        if (all_on) {   // (BSX_ALL_HITS_POOL: starting pool in words — test hook for the grow-and-run-again path)
+            const uint64_t words = getenv("BSX_ALL_HITS_POOL") ? (uint64_t)max(1ll, atoll(getenv("BSX_ALL_HITS_POOL"))) : max<uint64_t>(16384, (uint64_t)o.batch * BSX_ALL_HITS_WORDS_X100 / 100);
+            if ((rc = bsx_batch_set_all_hits(batches[g], words))) die(rc, "attaching the all-hits pool");
+        }
     }
     ReadOpts ro;
     ro.read_start = o.read_start; ro.read_end = o.read_end; ro.max_readlen = p.max_readlen; ro.zero_qual = p.zero_qual;
@@ -1087,6 +1153,27 @@ int main(int argc, char **argv)
         if (NC < NB) { { lock_guard<mutex> lk(G.mu); G.free_slots++; } G.cv.notify_all(); }
         return r;
     };
+    // --all-hits: spans and pool words of the batch just run; a batch whose lists did not fit is run again with the pool it asked for
+    // (results are a function of the reads — and of the planner state the batch already holds in exact mode —, so that run drops nothing)
+    auto fetch_all_hits = [&](bsx_batch *batch, long k, Slot &s) {
+        uint64_t need = 0, used = 0;
+        uint32_t dropped = 0;
+        int r = bsx_batch_all_hits_need(batch, &need, &dropped);
+        if (!r && dropped) {
+            cerr << "bsx: --all-hits: batch " << k << " wants " << need << " words for its lists (" << dropped << " units did not fit): pool grown, batch run again\n";
+            r = bsx_batch_set_all_hits(batch, need);
+            if (!r) r = bsx_batch_run(batch);
+            if (!r) r = bsx_batch_sync(batch);
+            if (!r) r = bsx_batch_all_hits_need(batch, &need, &dropped);
+            if (!r && dropped) { cerr << "bsx: --all-hits: units dropped again\n"; fatal_exit(); }
+        }
+        s.spans.resize(s.n * 3);
+        if (!r) r = bsx_batch_all_hits_spans(batch, s.spans.data());
+        if (!r) r = bsx_batch_all_hits_fetch(batch, nullptr, 0, &used);
+        s.ah_words.resize((size_t)used);
+        if (!r && used) r = bsx_batch_all_hits_fetch(batch, s.ah_words.data(), used, nullptr);
+        if (r) die(r, "reading the all-hits lists");
+    };
     auto gpu_stage = [&](int g) {
         bsx_batch *batch = batches[g];
         for (long k = g; ring.acquire(k, 1); k += NG) {
@@ -1116,6 +1203,7 @@ int main(int argc, char **argv)
                 s.pairs.resize(n); s.cca.resize(n); s.ccb.resize(n);
                 if ((r = bsx_batch_results_pe(batch, s.pairs.data(), s.cca.data(), s.ccb.data(), nullptr))) die(r, "reading results");
             }
+            if (all_on) fetch_all_hits(batch, k, s);
             add_cpu(1, c0);
             { const double t3 = now_s(); lock_guard<mutex> lk(mu_busy); busy[1] += t3 - t; gpu_part[0] += t1 - t; gpu_part[1] += t2 - t1; gpu_part[2] += t3 - t2;
               log_ev(k, 1, t, t1); log_ev(k, 2, t1, t2); log_ev(k, 3, t2, t3); }
@@ -1132,6 +1220,7 @@ int main(int argc, char **argv)
             // the slot's text buffers keep their capacity from batch to batch (a fresh 0.7 GB per batch would be page-faulted in again)
             if ((int)s.out.size() != W) { s.out.clear(); s.out_unpair.clear(); s.out.resize(W); s.out_unpair.resize(W); }
             else for (int w = 0; w < W; w++) { s.out[w].s.clear(); s.out_unpair[w].s.clear(); }
+            if (all_on) { if ((int)s.out_all.size() != W) { s.out_all.clear(); s.out_all.resize(W); } else for (Text &x : s.out_all) x.s.clear(); }
             vector<Formatter> fm(W, Formatter(o, rv));
             auto work = [&](int w) {
                 const double c0 = thread_cpu_s();
@@ -1143,9 +1232,11 @@ int main(int argc, char **argv)
                 for (size_t i = lo; i < hi; i++) {
                     os.need(g_rec_max); os_unpair.need(g_rec_max);
                     a.load(s.A, i);
+                    const bsx_span *sp = all_on ? &s.spans[i * 3] : nullptr;
                     if (!pe) {
                         const bsx_hit &h = s.hits[i];
                         apply_trim(a, h, o);
+                        if (sp && sp[0].n) fmt.all_hits_read(a.name, a.nlen, 0, s.ah_words.data() + sp[0].off, sp[0].n, sp[0].n_fwd, h.best_class, s.out_all[w]);
                         if (h.flags & BSX_F_FILTERED) { if (p.report_repeat_hits) fmt.out_hit(a, 0, 0, -1, 0, 0, 0, 0, 0, nullptr, os); }
                         else fmt.out_hit(a, 0, (h.flags & BSX_F_CHAIN) ? 1 : 0, h.n_best, h.best_class < 0 ? h.max_snp + 1 : h.best_class, h.chr, h.loc, 0, h.max_snp, &s.cca[i], os);
                     } else {
@@ -1153,6 +1244,11 @@ int main(int argc, char **argv)
                         const bsx_pair &pp = s.pairs[i];
                         apply_trim(a, pp.a, o); apply_trim(b, pp.b, o);
                         if (o.out_sam) fix_pair_name(a, b);
+                        if (sp) {   // (before the formatters below cut the mates of a read-through pair: the lists are cut with the lengths the reads have here)
+                            if (sp[0].n) fmt.all_hits_read(a.name, a.nlen, 1, s.ah_words.data() + sp[0].off, sp[0].n, sp[0].n_fwd, pp.a.best_class, s.out_all[w]);
+                            if (sp[1].n) fmt.all_hits_read(b.name, b.nlen, 2, s.ah_words.data() + sp[1].off, sp[1].n, sp[1].n_fwd, pp.b.best_class, s.out_all[w]);
+                            if (sp[2].n) fmt.all_hits_pairs(a.name, a.nlen, s.ah_words.data() + sp[2].off, sp[2].n, a.slen, b.slen, s.out_all[w]);
+                        }
                         if (!pp.unpaired_out) fmt.out_pair(a, b, pp, &s.cca[i], &s.ccb[i], os);
                         else {
                             Text &dst = o.out_sam ? os : os_unpair;
@@ -1205,6 +1301,7 @@ int main(int argc, char **argv)
                 }
             for (thread &t : wt) t.join();
         }
+        if (all_on) for (const Text &x : s.out_all) { if (x.s.empty()) continue; write_all(fout_all, x.s.data(), x.s.size(), off_all); off_all += (off_t)x.s.size(); }
         total = s.total_after;
         busy[3] += now_s() - t;
         log_ev(k, 5, t, now_s());
@@ -1216,6 +1313,7 @@ int main(int argc, char **argv)
     t_format.join();
     ::close(fout);
     if (fout_unpair >= 0) ::close(fout_unpair);
+    if (fout_all >= 0) ::close(fout_all);
     if (bam_out) {
         cout << "Converting SAM to BAM ...\nSorting BAM ...\nIndexing BAM ...\n";  // sam2bam.sh's progress lines
         bam.finish();

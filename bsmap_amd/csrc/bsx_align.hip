@@ -1536,15 +1536,91 @@ __device__ void unit_finish(const AlignArgs &A, const MateLds &LA, const MateLds
     forget_keys(MA, U.SA, lane); forget_keys(MB, U.SB, lane);
 }
 
+// All-hits emission (include/bsx.h: bsx_batch_set_all_hits).  Called by the emitting twins of the kernels right behind unit_finish, while the
+// finished unit's slab still holds its lists (forget_keys clears the duplicate set, not the lists): the wave copies the best class's lists to the pool — na / nb
+// placements of mate a / b in class ca / cb (forward list, then reverse-complement list: the order select_hit indexes), np pairs of pair class cp.  One reservation
+// per unit, so a unit is in the pool whole or not at all; a unit that does not fit leaves the cursor behind the end (the cursor's final value is what the run
+// needs), keeps its counts in its spans and writes nothing to the pool.  unit_finish itself is untouched: the kernels of a batch without a pool are the ones
+// they always were.
+__device__ __forceinline__ void all_hits_copy(uint32_t *dst, const Slab &SL, int cls, uint32_t nf, uint32_t n, int lane)
+{
+    const u64 *l0 = SL.list(0, cls), *l1 = SL.list(1, cls);
+    for (uint32_t i = lane; i < n; i += 64) {
+        const u64 h = i < nf ? l0[i] : l1[i - nf];
+        ((uint2 *)dst)[i] = make_uint2((uint32_t)(h >> 32), (uint32_t)h);   // (spans start at even words: every entry is two or six words)
+    }
+}
+template <bool PE>
+__device__ void all_hits_emit(const AllHitsArgs &X, const Mate &MA, const Mate &MB, const UnitSlabs &U, uint32_t unit, int lane, uint32_t na, int ca, uint32_t nb, int cb,
+                              uint32_t np, int cp)
+{
+    const uint32_t words = 2 * (na + nb) + 6 * np;
+    if (!words) return;
+    unsigned long long off = 0;
+    if (lane == 0) off = atomicAdd(X.cursor, (unsigned long long)words);
+    off = ((u64)rfl((uint32_t)(off >> 32)) << 32) | rfl((uint32_t)off);
+    const bool fits = off + words <= X.cap;
+    if (!fits && lane == 0) atomicAdd(X.dropped, 1u);
+    bsx_span *sp = X.spans + (size_t)unit * 3;
+    if (na) {
+        const uint32_t nf = n_of(MA, 0, ca);
+        if (fits) all_hits_copy(X.pool + off, U.SA, ca, nf, na, lane);
+        if (lane == 0) { bsx_span s; s.off = fits ? off : BSX_SPAN_DROPPED; s.n = na; s.n_fwd = nf; sp[0] = s; }
+        off += 2 * na;
+    }
+    if (PE && nb) {
+        const uint32_t nf = n_of(MB, 0, cb);
+        if (fits) all_hits_copy(X.pool + off, U.SB, cb, nf, nb, lane);
+        if (lane == 0) { bsx_span s; s.off = fits ? off : BSX_SPAN_DROPPED; s.n = nb; s.n_fwd = nf; sp[1] = s; }
+        off += 2 * nb;
+    }
+    if (PE && np) {
+        const uint32_t *row = U.PS.row(cp);
+        if (fits) for (uint32_t i = lane; i < 6 * np; i += 64) X.pool[off + i] = row[i];
+        if (lane == 0) { bsx_span s; s.off = fits ? off : BSX_SPAN_DROPPED; s.n = np; s.n_fwd = 0; sp[2] = s; }
+    }
+}
+// first non-empty class of a mate and its size, as select_hit finds them (0 placements: filtered or no hit)
+__device__ __forceinline__ uint32_t all_hits_best(const Mate &M, int &cls)
+{
+    cls = 0;
+    if (M.u->filtered) return 0;
+    for (int ii = 0; ii <= M.u->max_snp; ii++) {
+        const uint32_t n = n_of(M, 0, ii) + n_of(M, 1, ii);
+        if (n) { cls = ii; return n; }
+    }
+    return 0;
+}
+// what the unit unit_finish has just finished emits (the counts in MA / MB are the ones behind fix_unpaired_short_fragment; -r 1: a pair that was found is reported)
+template <bool PE>
+__device__ void unit_all_hits(const DevParams &P, const AllHitsArgs &X, const Mate &MA, const Mate &MB, const UnitSlabs &U, uint32_t pcnt_reg, int paired, uint32_t unit, int lane)
+{
+    int ca = 0, cb = 0;
+    if (!PE) {
+        const uint32_t na = all_hits_best(MA, ca);
+        if (na >= 2) all_hits_emit<false>(X, MA, MA, U, unit, lane, na, ca, 0, 0, 0, 0);
+        return;
+    }
+    if (paired)
+        for (int c = 0; c <= 2 * P.max_snp_num; c++) {
+            const uint32_t n = rl(pcnt_reg, c);
+            if (!n) continue;
+            if (n >= 2) all_hits_emit<true>(X, MA, MB, U, unit, lane, 0, 0, 0, 0, n, c);
+            return;
+        }
+    const uint32_t na = all_hits_best(MA, ca), nb = all_hits_best(MB, cb);
+    all_hits_emit<true>(X, MA, MB, U, unit, lane, na >= 2 ? na : 0, ca, nb >= 2 ? nb : 0, cb, 0, 0);
+}
+
 // one unit in the main kernel; returns true if it was deferred to the heavy pipeline
 // (always inlined into the kernel: as a called function its callee-saved registers cost 21 KB of scratch writes per pair,
 //  a fifth of the kernel's memory requests — 59.6 ms against 48.6 ms per 2^20 pairs)
 // UnitLds: the wave-uniform per-unit state that is not in MateU — slab pointers and the work counters with their value at the
 // unit's start (restored when the unit is deferred); in LDS for the same reason (the main kernel is short of scalar registers)
 struct UnitLds { UnitSlabs U; Counters C, C0; };
-template <bool PE, bool EXACT, bool CTX = false>
+template <bool PE, bool EXACT, bool CTX = false, bool AH = false>
 __device__ __forceinline__ bool process_unit(const AlignArgs &A, const BlockLds &BL, MateLds &LA, MateLds &LB, uint32_t unit, uint8_t *slab, int lane, UnitLds &UL,
-                             u64 &n_aligned, u64 &n_aligned_pairs)
+                             u64 &n_aligned, u64 &n_aligned_pairs, const AllHitsArgs *X = nullptr)
 {
     const DevParams &P = A.P;
     const uint32_t hthr = A.heavy_threshold;
@@ -1575,6 +1651,7 @@ __device__ __forceinline__ bool process_unit(const AlignArgs &A, const BlockLds 
     }
     if (defer) { forget_keys(MA, U.SA, lane); if (PE) forget_keys(MB, U.SB, lane); C = C0; return true; }
     [[clang::always_inline]] unit_finish<PE>(A, LA, LB, MA, MB, U, pcnt_reg, paired, unit, lane, n_aligned, n_aligned_pairs);   // (the main kernel stays a leaf: a call costs it a kilobyte of stack per lane)
+    if (AH) { [[clang::always_inline]] unit_all_hits<PE>(P, *X, MA, MB, U, pcnt_reg, paired, unit, lane); }
     return false;
 }
 
@@ -1642,6 +1719,46 @@ __global__ __launch_bounds__(256, PE ? BSX_WAVES_PER_EU_PE : BSX_WAVES_PER_EU_SE
     }
     if (lane == 0) flush_counters(A, C, n_units_done, n_aligned, n_aligned_pairs, true);
 }
+// The emitting twin of k_align, launched instead of it while the batch has an all-hits pool (bsx_batch_set_all_hits): the same loop, process_unit<.., AH = true>.
+// A kernel of its own, an argument of its own and a translation unit of its own (bsx_align_ah.hip includes this file with BSX_ALL_HITS_TU defined and gets the
+// twins and their launchers, nothing else) — not a branch on a pointer in AlignArgs: the branch alone took k_align<true, false, true> from 152 to 176 bytes of
+// scratch per lane and k_hctrl<false> from 224 to 225 VGPRs (tests/test_kernel_budget.py); a longer AlignArgs changes the code the compiler makes for k_align;
+// and a second kernel in THIS unit that calls k_hctrl's helpers changes which of them are inlined into k_hctrl.  As it is, every kernel of
+// this unit is, instruction for instruction, what it was before the pool existed.
+#ifdef BSX_ALL_HITS_TU
+template <bool PE, bool EXACT, bool CTX = false>
+__global__ __launch_bounds__(256, PE ? BSX_WAVES_PER_EU_PE : BSX_WAVES_PER_EU_SE) void k_align_ah(AlignArgs A, AllHitsArgs X)
+{
+    __shared__ BlockLds BL;
+    __shared__ WaveLds<PE> WL[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    init_block_lds(A.P, BL, threadIdx.x, 256);
+    __syncthreads();
+    const uint32_t slot = blockIdx.x * 4 + wv;
+    MateLds &LA = WL[wv].mate[0];
+    MateLds &LB = WL[wv].mate[PE ? 1 : 0];
+    __shared__ UnitLds ULS[4];
+    UnitLds &UL = ULS[wv];
+    Counters &C = UL.C;
+    C.n_lookup = 0; C.n_cand = 0; C.sum_w = 0; C.n_orient = 0;
+    u64 n_units_done = 0, n_aligned = 0, n_aligned_pairs = 0;
+    for (;;) {
+        uint32_t unit = 0;
+        if (lane == 0) unit = atomicAdd(A.queue, 1u);
+        unit = rfl(unit) + A.first_unit;
+        if (unit >= A.n_units) break;
+        if (A.unit_list) unit = rfl(A.unit_list[unit]);  // redo run: the units named by the list
+        const u64 t_begin = A.dbg_cycles ? __builtin_readcyclecounter() : 0;
+        uint8_t *slab = A.scratch + (size_t)(A.debug ? unit : slot) * A.slab_bytes;
+        const bool deferred = process_unit<PE, EXACT, CTX, true>(A, BL, LA, LB, unit, slab, lane, UL, n_aligned, n_aligned_pairs, &X);
+        if (deferred) { if (lane == 0) A.heavy_list[atomicAdd(A.heavy_count, 1u)] = unit; }
+        else n_units_done++;
+        if (A.dbg_cycles && lane == 0) A.dbg_cycles[unit] = (uint32_t)min((u64)0xffffffffull, (u64)__builtin_readcyclecounter() - t_begin);
+        wave_fence();
+    }
+    if (lane == 0) flush_counters(A, C, n_units_done, n_aligned, n_aligned_pairs, true);
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // heavy pipeline: units whose candidate lists are too long for one wave
@@ -2153,134 +2270,20 @@ __device__ __forceinline__ bool heavy_advance(const AlignArgs &A, const HeavyArg
 template <bool PE>
 __global__ __launch_bounds__(256, PE ? BSX_HCTRL_WAVES : BSX_HCTRL_WAVES_SE) void k_hctrl(AlignArgs A_, HeavyArgs H_)
 {
-    __shared__ BlockLds BL;
-    __shared__ WaveLds<PE> WL[4];
-    __shared__ u64 SORTBUF[4][BSX_LDS_SORT];
-    // The helpers called from here (scan, replay, prepare / finish, state save / restore) are real calls that take the arguments,
-    // the cursor, the counters and the slab pointers by reference: as private objects they would live in scratch memory — 256 bytes
-    // and four cache lines per scalar access, in a kernel that is one chain of dependent accesses.  All of them are wave-uniform:
-    // one copy per block (arguments) or per wave in LDS instead.
-    __shared__ AlignArgs As;
-    __shared__ HeavyArgs Hs;
-    __shared__ HCursor KS[4];
-    __shared__ Counters CS[4];
-    __shared__ UnitSlabs US[4];
-    __shared__ uint32_t PEND[4][32];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (uint32_t i = threadIdx.x; i < sizeof(AlignArgs) / 4; i += 256) ((uint32_t *)&As)[i] = ((const uint32_t *)&A_)[i];
-    for (uint32_t i = threadIdx.x; i < sizeof(HeavyArgs) / 4; i += 256) ((uint32_t *)&Hs)[i] = ((const uint32_t *)&H_)[i];
-    __syncthreads();
-    const AlignArgs &A = As;
-    const HeavyArgs &H = Hs;
-    init_block_lds(A.P, BL, threadIdx.x, 256);
-    __syncthreads();
-    MateLds &LA = WL[wv].mate[0];
-    MateLds &LB = WL[wv].mate[PE ? 1 : 0];
-    Counters Cflush = {0, 0, 0, 0};
-    u64 n_units_done = 0, n_aligned = 0, n_aligned_pairs = 0;
-    const uint32_t n_active_in = H.fresh ? H.n_active_in : rfl(*H.n_active_in_ptr);  // later passes: count left by the previous pass
-    // One word takes ~88 atomics per microsecond and an RRBS pass visits 10^5 units: a wave takes queue entries in chunks (one while units are few: the pass
-    // then ends with its longest visit, not with a wave's leftover chunk) and hands in the units it leaves active 32 at a time (PEND).
-#ifndef BSX_QCHUNK_DIV
-#define BSX_QCHUNK_DIV 128u
-#endif
-    const uint32_t q_chunk = BSX_HCTRL_BATCH ? max(1u, min(16u, n_active_in / (gridDim.x * BSX_QCHUNK_DIV))) : 1u;   // (RRBS: 175 short visits per wave and pass, chunks of 5; C5: 25 long ones, one at a time)
-    uint32_t q_next = 0, q_end = 0, n_pend = 0;
-    uint32_t *const pend = PEND[wv];
-#define HCTRL_PEND_FLUSH() do { if (n_pend) { uint32_t b_ = 0; if (lane == 0) b_ = atomicAdd(H.n_active_out, n_pend); b_ = rfl(b_); if ((uint32_t)lane < n_pend) H.active_out[b_ + (uint32_t)lane] = pend[lane]; n_pend = 0; wave_fence(); } } while (0)
-#define HCTRL_PEND_PUSH(x) do { if (lane == 0) pend[n_pend] = (x); n_pend++; wave_fence(); if (n_pend == (BSX_HCTRL_BATCH ? 32u : 1u)) HCTRL_PEND_FLUSH(); } while (0)
-    for (;;) {
-        if (q_next == q_end) {
-            uint32_t i0 = 0;
-            if (lane == 0) i0 = atomicAdd(H.queue, q_chunk);
-            q_next = rfl(i0); q_end = min(q_next + q_chunk, n_active_in);
-            if (q_next >= n_active_in) break;
-        }
-        const uint32_t i = q_next++;
-        // (later passes take the list back to front: a unit whose visit ended last in the previous pass — a long visit — was appended
-        //  last; starting those first keeps the pass from waiting for one long visit that began when all the others were done)
-        const uint32_t hidx = H.fresh ? H.hidx_base + i : rfl(H.active_in[n_active_in - 1u - i]);
-        const uint32_t unit = rfl(A.heavy_list[H.list_base + hidx]);
-        HState *S = &H.state[hidx];
-        if (!H.fresh) {
-            // a unit whose last request was refused stays parked (no state restore / save) while the pool cannot take it:
-            // n_tasks only grows during a pass, so the reservation below would be refused again
-            const uint32_t want = rfl(S->want);
-            if (want && rfl(__hip_atomic_load(H.n_tasks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + want > H.task_cap) {
-                HCTRL_PEND_PUSH(hidx);
-                continue;
-            }
-        }
-        // (the slabs of deferred units carry the ordinary, small duplicate set even where the main kernel's are large — single-end
-        //  RRBS —: there are too many deferred units for 4 MB each; a unit that overflows it is redone by the main kernel, below)
-        uint8_t *slab = A.debug ? A.scratch + (size_t)unit * A.slab_bytes : H.slabs + (size_t)hidx * A.hslab_bytes;
-        UnitSlabs &U = US[wv];
-        U = A.debug ? carve_slab(slab, (uint32_t)A.P.max_snp_num + 1, A.rowcap, PE, A.kcap, A.hbits)
-                    : carve_slab(slab, (uint32_t)A.P.max_snp_num + 1, A.rowcap, PE, A.hkcap, A.hhbits);
-        Mate MA, MB;
-        MA.u = lds_mate(&LA.u); MB.u = PE ? lds_mate(&LB.u) : lds_mate(&LA.u2);
-        Counters &C = CS[wv];
-        C.n_lookup = 0; C.n_cand = 0; C.sum_w = 0; C.n_orient = 0;
-        HCursor &K = KS[wv];
-        K.n_active = n_active_in; K.want = 0;
-        for (int k_ = 0; k_ < 8; k_++) { K.vc[k_] = 0; K.vn[k_] = 0; }
-        uint32_t pcnt_reg = 0;
-        const u64 cat_prep0 = A.dbg_cat ? __builtin_readcyclecounter() : 0;
-        if (H.fresh) {
-            unit_prepare<PE, true>(A, BL, LA, LB, MA, MB, unit, lane, C);
-            K.level = 0; K.sub = 0; K.paired = 0;
-            for (int m_ = 0; m_ < 2; m_++) { K.orient[m_] = 0; K.have[2 * m_] = 0; K.have[2 * m_ + 1] = 0; K.c[m_] = 0; K.W[m_] = HS_WIN0; }
-        } else {
-            load_mate(S->mate[0], MA, LA, lane);
-            if (PE) load_mate(S->mate[1], MB, LB, lane); else MB = MA;
-            C = S->C;
-            C.n_lookup = (u64)rfl((uint32_t)(C.n_lookup >> 32)) << 32 | rfl((uint32_t)C.n_lookup); C.n_cand = (u64)rfl((uint32_t)(C.n_cand >> 32)) << 32 | rfl((uint32_t)C.n_cand);
-            C.sum_w = (u64)rfl((uint32_t)(C.sum_w >> 32)) << 32 | rfl((uint32_t)C.sum_w); C.n_orient = (u64)rfl((uint32_t)(C.n_orient >> 32)) << 32 | rfl((uint32_t)C.n_orient);
-            pcnt_reg = S->pcnt_reg[lane];
-            K.level = (int)rfl((uint32_t)S->level); K.sub = (int)rfl((uint32_t)S->sub); K.paired = (int)rfl((uint32_t)S->paired);
-            for (int m_ = 0; m_ < 2; m_++) {
-                K.orient[m_] = (int)rfl((uint32_t)S->orient[m_]); K.have[2 * m_] = (int)rfl((uint32_t)S->have[2 * m_]); K.have[2 * m_ + 1] = (int)rfl((uint32_t)S->have[2 * m_ + 1]); K.c[m_] = rfl(S->c[m_]); K.W[m_] = rfl(S->W[m_]);
-            }
-        }
-        if (A.dbg_cat && lane == 0) { const u64 d_ = (u64)__builtin_readcyclecounter() - cat_prep0; atomicAdd((u64 *)&A.dbg_cat[0], d_); atomicMax((u64 *)&A.dbg_cat[8], d_); }
-        const u64 cat_adv0 = A.dbg_cat ? __builtin_readcyclecounter() : 0;
-        const bool done = heavy_advance<PE>(A, H, S, hidx, BL, LA, LB, MA, MB, U, pcnt_reg, K, lane, C, SORTBUF[threadIdx.x >> 6]);
-        if (A.dbg_cat && lane == 0) {
-            const u64 d_ = (u64)__builtin_readcyclecounter() - cat_adv0;
-            atomicAdd((u64 *)&A.dbg_cat[6], d_);
-            if (atomicMax((u64 *)&A.dbg_cat[14], d_) < d_)  // the longest visit so far: leave its break-down (racy, diagnostics only)
-                for (int k_ = 0; k_ < 6; k_++) A.dbg_cat[16 + k_] = (K.vc[k_] << 16) | min(K.vn[k_], 0xffffu);
-        }
-        const u64 cat_fin0 = A.dbg_cat ? __builtin_readcyclecounter() : 0;
-        if (done && ((MA.u->flags | (PE ? MB.u->flags : 0u)) & 4u)) {
-            // the small duplicate set of this unit's heavy slab overflowed (single-end RRBS: coordinates its fragment filter rejects
-            // are remembered too): its records are not written; the main kernel redoes it alone with its large set, undeferred
-            forget_keys(MA, U.SA, lane); if (PE) forget_keys(MB, U.SB, lane);
-            if (lane == 0) A.redo_list[atomicAdd(A.redo_count, 1u)] = unit;
-        } else if (done) {
-            unit_finish<PE>(A, LA, LB, MA, MB, U, pcnt_reg, K.paired, unit, lane, n_aligned, n_aligned_pairs);
-            Cflush.n_lookup += C.n_lookup; Cflush.n_cand += C.n_cand; Cflush.sum_w += C.sum_w; Cflush.n_orient += C.n_orient;
-            n_units_done++;
-        } else {
-            save_mate(S->mate[0], MA, LA, lane);
-            if (PE) save_mate(S->mate[1], MB, LB, lane);
-            S->pcnt_reg[lane] = pcnt_reg;
-            if (lane == 0) {
-                S->want = K.want; S->C = C; S->level = K.level; S->sub = K.sub; S->paired = K.paired;
-                for (int m_ = 0; m_ < 2; m_++) {
-                    S->orient[m_] = K.orient[m_]; S->have[2 * m_] = K.have[2 * m_]; S->have[2 * m_ + 1] = K.have[2 * m_ + 1]; S->c[m_] = K.c[m_]; S->W[m_] = K.W[m_];
-                }
-            }
-            HCTRL_PEND_PUSH(hidx);
-        }
-        if (A.dbg_cat && lane == 0) { const u64 d_ = (u64)__builtin_readcyclecounter() - cat_fin0; atomicAdd((u64 *)&A.dbg_cat[4], d_); atomicMax((u64 *)&A.dbg_cat[12], d_); }
-        wave_fence();
-    }
-    HCTRL_PEND_FLUSH();
-#undef HCTRL_PEND_PUSH
-#undef HCTRL_PEND_FLUSH
-    if (lane == 0) flush_counters(A, Cflush, n_units_done, n_aligned, n_aligned_pairs);
+#define BSX_HCTRL_AH 0
+#include "bsx_hctrl_body.inc"
+#undef BSX_HCTRL_AH
 }
+#ifdef BSX_ALL_HITS_TU
+// the emitting twin (see k_align_ah)
+template <bool PE>
+__global__ __launch_bounds__(256, PE ? BSX_HCTRL_WAVES : BSX_HCTRL_WAVES_SE) void k_hctrl_ah(AlignArgs A_, HeavyArgs H_, AllHitsArgs X_)
+{
+#define BSX_HCTRL_AH 1
+#include "bsx_hctrl_body.inc"
+#undef BSX_HCTRL_AH
+}
+#endif
 
 // every wave of the chip evaluates tasks: HS_TASK consecutive candidates of one published list window
 #ifndef BSX_HSCAN_WAVES
@@ -3245,6 +3248,31 @@ __global__ __launch_bounds__(256, BSX_HSHARED_WAVES) void k_hscan_shared(AlignAr
 }
 }  // namespace
 
+#ifdef BSX_ALL_HITS_TU
+// the all-hits translation unit: the launchers of the twins, the same choice of variant as bsx_launch_align / bsx_launch_hctrl below
+void bsx_launch_align_ah(const AlignArgs &A, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs &X)
+{
+    const bool ctx = A.P.ctx && !A.work_counters && A.P.index_interval <= 4 && !A.P.rrbs;
+    if (A.leak_exact && ctx) {
+        if (paired) hipLaunchKernelGGL((k_align_ah<true, true, true>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+        else hipLaunchKernelGGL((k_align_ah<false, true, true>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+    } else if (A.leak_exact) {
+        if (paired) hipLaunchKernelGGL((k_align_ah<true, true>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+        else hipLaunchKernelGGL((k_align_ah<false, true>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+    } else if (ctx) {
+        if (paired) hipLaunchKernelGGL((k_align_ah<true, false, true>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+        else hipLaunchKernelGGL((k_align_ah<false, false, true>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+    } else if (paired) hipLaunchKernelGGL((k_align_ah<true, false>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+    else hipLaunchKernelGGL((k_align_ah<false, false>), dim3(grid_blocks), dim3(256), 0, stream, A, X);
+}
+void bsx_launch_hctrl_ah(const AlignArgs &A, const HeavyArgsRaw &R, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs &X)
+{
+    const HeavyArgs H = typed(R);
+    if (paired) hipLaunchKernelGGL(k_hctrl_ah<true>, dim3(grid_blocks), dim3(256), 0, stream, A, H, X);
+    else hipLaunchKernelGGL(k_hctrl_ah<false>, dim3(grid_blocks), dim3(256), 0, stream, A, H, X);
+}
+#else
+
 // exact mode pre-pass (see k_leak_meta): with_meta = the stream's records are not up to date (new reads / history); `final_out` != null:
 // also leave the state behind the stream's last read there
 void bsx_launch_leak(const AlignArgs &A, int paired, int n_cu, bool with_meta, bool resolve, void *final_out, hipStream_t stream)
@@ -3269,8 +3297,9 @@ size_t bsx_leakrec_bytes(void) { return sizeof(LeakRec); }
 size_t bsx_leakstate_bytes(void) { return sizeof(LeakState); }
 uint32_t bsx_leak_blk(void) { return LEAK_BLK; }
 
-void bsx_launch_align(const AlignArgs &A, int paired, int grid_blocks, hipStream_t stream)
+void bsx_launch_align(const AlignArgs &A, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs *ah)
 {
+    if (ah) { bsx_launch_align_ah(A, paired, grid_blocks, stream, *ah); return; }   // the emitting twins (bsx_align_ah.hip)
     const bool ctx = A.P.ctx && !A.work_counters && A.P.index_interval <= 4 && !A.P.rrbs;
     if (A.leak_exact && ctx) {   // (round 6: the exact mode keeps the context prefilter — it used to fall back to the plain scan, most of its 11 % on C5)
         if (paired) hipLaunchKernelGGL((k_align<true, true, true>), dim3(grid_blocks), dim3(256), 0, stream, A);
@@ -3285,17 +3314,14 @@ void bsx_launch_align(const AlignArgs &A, int paired, int grid_blocks, hipStream
     else hipLaunchKernelGGL((k_align<false, false>), dim3(grid_blocks), dim3(256), 0, stream, A);
 }
 
-void bsx_launch_hctrl(const AlignArgs &A, const HeavyArgsRaw &R, int paired, int grid_blocks, hipStream_t stream)
+void bsx_launch_hctrl(const AlignArgs &A, const HeavyArgsRaw &R, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs *ah)
 {
+    if (ah) { bsx_launch_hctrl_ah(A, R, paired, grid_blocks, stream, *ah); return; }
     const HeavyArgs H = typed(R);
     if (paired) hipLaunchKernelGGL(k_hctrl<true>, dim3(grid_blocks), dim3(256), 0, stream, A, H);
     else hipLaunchKernelGGL(k_hctrl<false>, dim3(grid_blocks), dim3(256), 0, stream, A, H);
 }
 
-// The scan launches are sized for the group's whole task pool: the number of tasks a control pass published stays on the device
-// (H.n_tasks), blocks beyond it exit at once (28 us for 131 072 empty blocks, profiles/r03_launch_cost.json) — no host read-back
-// between a control pass and its scan.
-// max_tasks: 0 = a grid for the whole task pool; otherwise a grid for that many tasks, whose blocks sweep over whatever the pass published
 void bsx_launch_hscan_shared(const AlignArgs &A, const HeavyArgsRaw &R, hipStream_t stream, uint32_t max_tasks)
 {
     const HeavyArgs H = typed(R);
@@ -3581,3 +3607,4 @@ int bsx_hctrl_occupancy(int paired)
     if (e != hipSuccess || nb < 1) nb = 1;
     return nb;
 }
+#endif  // BSX_ALL_HITS_TU

@@ -311,6 +311,13 @@ struct bsx_batch {
     size_t ctrl_ev_used = 0;
     hipEvent_t ev_align = nullptr;     // behind the main kernel (and the exact mode's pre-pass)
     bool stage_timing = false;         // bsx_batch_set_stage_timing: the events above are only recorded on request (three more per control pass on its stream)
+    // all-hits pool (bsx_batch_set_all_hits): null / 0 unless attached
+    uint32_t *d_ah_pool = nullptr;
+    uint64_t ah_cap = 0;
+    uint64_t *d_ah_ctl = nullptr;      // [0] cursor in words, [1] (low word) dropped units
+    bsx_span *d_ah_spans = nullptr;    // [max_units][3]
+    uint32_t run_first = 0, run_units = 0;   // the units of the last run
+    bool ah_ran = false;               // a run has filled the attached pool (a pool attached after the run holds nothing yet)
     bool ran = false;
     bool counted = false;        // the batch is in its reference's n_batches
 };
@@ -647,7 +654,7 @@ extern "C" void bsx_batch_destroy(bsx_batch *b)
         for (void *q : {(void *)b->d_seq[m], (void *)b->d_qual[m], (void *)b->d_off[m], (void *)b->d_cc[m]})
             if (q) (void)hipFree(q);
     for (void *q : {(void *)b->d_hits, (void *)b->d_pairs, (void *)b->d_npairs, (void *)b->d_scratch, (void *)b->d_dbg, (void *)b->d_queue, (void *)b->d_counters, (void *)b->d_scan_stats, (void *)b->d_cycles, (void *)b->d_heavy_list, (void *)b->d_heavy_count,
-                    (void *)b->d_hstate, (void *)b->d_hslabs, (void *)b->d_htasks, (void *)b->d_htout, (void *)b->d_hactive[0], (void *)b->d_hactive[1], (void *)b->d_hcnt, (void *)b->d_redo})
+                    (void *)b->d_hstate, (void *)b->d_hslabs, (void *)b->d_htasks, (void *)b->d_htout, (void *)b->d_hactive[0], (void *)b->d_hactive[1], (void *)b->d_hcnt, (void *)b->d_redo, (void *)b->d_ah_pool, (void *)b->d_ah_ctl, (void *)b->d_ah_spans})
         if (q) (void)hipFree(q);
     for (int m = 0; m < 2; m++) for (void *q : {(void *)b->d_hist_seq[m], (void *)b->d_hist_qual[m], (void *)b->d_hist_off[m]}) if (q) (void)hipFree(q);
     for (void *q : {(void *)b->d_leak_rec, (void *)b->d_leak_meta[0], (void *)b->d_leak_meta[1], (void *)b->d_leak_blk, (void *)b->d_leak_init, (void *)b->d_leak_final}) if (q) (void)hipFree(q);
@@ -873,6 +880,14 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
     HIP_TRY(hipMemsetAsync(b->d_queue, 0, 4, b->stream));
     HIP_TRY(hipMemsetAsync(b->d_heavy_count, 0, 4, b->stream));
     HIP_TRY(hipMemsetAsync(b->d_redo, 0, 4, b->stream));
+    b->run_first = first_unit; b->run_units = n_units;
+    AllHitsArgs X;   // with a pool attached the emitting twins of the kernels that finish units are launched (bsx_align_ah.hip)
+    const AllHitsArgs *ah = b->d_ah_pool ? &X : nullptr;
+    if (ah) {
+        X.pool = b->d_ah_pool; X.cap = b->ah_cap; X.cursor = (unsigned long long *)b->d_ah_ctl; X.dropped = (uint32_t *)(b->d_ah_ctl + 1); X.spans = b->d_ah_spans;
+        HIP_TRY(hipMemsetAsync(b->d_ah_ctl, 0, 16, b->stream));
+        HIP_TRY(hipMemsetAsync(b->d_ah_spans + (size_t)first_unit * 3, 0, (size_t)n_units * 3 * sizeof(bsx_span), b->stream));
+    }
     if (b->debug) HIP_TRY(hipMemsetAsync(b->d_scratch, 0, (size_t)b->max_units * b->slab_bytes, b->stream));
     HIP_TRY(hipEventRecord(b->ev0, b->stream));
     if (b->leak_exact && !b->ref->P.rrbs) {  // pre-pass of the exact mode: planner state that leaks from earlier reads
@@ -882,7 +897,7 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
         HIP_TRY(hipGetLastError());
         b->leak_meta_valid = true;
     }
-    bsx_launch_align(A, b->paired, b->grid_blocks, b->stream);
+    bsx_launch_align(A, b->paired, b->grid_blocks, b->stream, ah);
     HIP_TRY(hipGetLastError());
     if (b->stage_timing) {
         if (!b->ev_align) HIP_TRY(hipEventCreate(&b->ev_align));
@@ -937,7 +952,7 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
                 if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used], hw.s_ctrl));
                 // (no more blocks than are resident at once — two per CU by their LDS —: blocks of a high-priority kernel that wait for a slot
                 //  keep the dispatcher from placing the kernels of the normal-priority stream, 300 us per pass when the grid was twice that)
-                bsx_launch_hctrl(A, q.H, b->paired, (int)std::min<uint32_t>((q.n0 + 3) / 4, (uint32_t)b->n_cu * b->hctrl_blocks_per_cu), hw.s_ctrl);
+                bsx_launch_hctrl(A, q.H, b->paired, (int)std::min<uint32_t>((q.n0 + 3) / 4, (uint32_t)b->n_cu * b->hctrl_blocks_per_cu), hw.s_ctrl, ah);
                 HIP_TRY(hipGetLastError());
                 if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 1], hw.s_ctrl));
                 // scan order of the tasks this pass published, still on the group's stream: done by the time the main stream gets to the scan
@@ -1042,12 +1057,13 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
             AlignArgs R = A;
             R.unit_list = b->d_redo + 1; R.first_unit = 0; R.n_units = n_redo; R.heavy_threshold = 0;
             HIP_TRY(hipMemsetAsync(b->d_queue, 0, 4, b->stream));
-            bsx_launch_align(R, b->paired, std::min<int>(b->grid_blocks, (int)((n_redo + 3) / 4)), b->stream);
+            bsx_launch_align(R, b->paired, std::min<int>(b->grid_blocks, (int)((n_redo + 3) / 4)), b->stream, ah);
             HIP_TRY(hipGetLastError());
         }
     }
     HIP_TRY(hipEventRecord(b->ev1, b->stream));
     b->ran = true;
+    b->ah_ran = b->d_ah_pool != nullptr;
     return BSX_OK;
 }
 
@@ -1164,6 +1180,71 @@ extern "C" int bsx_batch_download_reads(bsx_batch *b, int mate, char *seqs, uint
     HIP_TRY(stream_wait(b));
     HIP_TRY(hipMemcpy(off, b->d_off[mate], ((size_t)b->n_units + 1) * 8, hipMemcpyDeviceToHost));
     if (seqs) HIP_TRY(hipMemcpy(seqs, b->d_seq[mate], off[b->n_units], hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// ---- all hits (include/bsx.h) -----------------------------------------------------------------------------------
+extern "C" int bsx_batch_set_all_hits(bsx_batch *b, uint64_t pool_words)
+{
+    if (!b) return BSX_ERR_ARG;
+    if (pool_words && b->ref->P.report_repeat_hits != 1) return BSX_ERR_ARG;
+    HIP_TRY(hipSetDevice(b->ref->device));
+    HIP_TRY(stream_wait(b));
+    if (pool_words == b->ah_cap && (pool_words == 0 || b->d_ah_pool)) return BSX_OK;
+    b->ah_ran = false;
+    if (b->d_ah_pool) { (void)hipFree(b->d_ah_pool); b->d_ah_pool = nullptr; b->ah_cap = 0; }
+    if (!pool_words) {
+        if (b->d_ah_ctl) { (void)hipFree(b->d_ah_ctl); b->d_ah_ctl = nullptr; }
+        if (b->d_ah_spans) { (void)hipFree(b->d_ah_spans); b->d_ah_spans = nullptr; }
+        return BSX_OK;
+    }
+    if (!b->d_ah_ctl && hipMalloc((void **)&b->d_ah_ctl, 16) != hipSuccess) { (void)hipGetLastError(); return BSX_ERR_NOMEM; }
+    if (!b->d_ah_spans) {
+        if (hipMalloc((void **)&b->d_ah_spans, (size_t)b->max_units * 3 * sizeof(bsx_span)) != hipSuccess) { (void)hipGetLastError(); b->d_ah_spans = nullptr; return BSX_ERR_NOMEM; }
+        HIP_TRY(hipMemset(b->d_ah_spans, 0, (size_t)b->max_units * 3 * sizeof(bsx_span)));
+    }
+    HIP_TRY(hipMemset(b->d_ah_ctl, 0, 16));
+    if (hipMalloc((void **)&b->d_ah_pool, (size_t)pool_words * 4) != hipSuccess) { (void)hipGetLastError(); b->d_ah_pool = nullptr; return BSX_ERR_NOMEM; }
+    b->ah_cap = pool_words;
+    return BSX_OK;
+}
+
+extern "C" int bsx_batch_all_hits_need(bsx_batch *b, uint64_t *words, uint32_t *dropped_units)
+{
+    if (!b) return BSX_ERR_ARG;
+    if (!b->d_ah_pool || !b->ah_ran) return BSX_ERR_STATE;
+    HIP_TRY(hipSetDevice(b->ref->device));
+    HIP_TRY(stream_wait(b));
+    uint64_t ctl[2];
+    HIP_TRY(hipMemcpy(ctl, b->d_ah_ctl, 16, hipMemcpyDeviceToHost));
+    if (words) *words = ctl[0];
+    if (dropped_units) *dropped_units = (uint32_t)ctl[1];
+    return BSX_OK;
+}
+
+extern "C" int bsx_batch_all_hits_spans(bsx_batch *b, bsx_span *spans)
+{
+    if (!b || !spans) return BSX_ERR_ARG;
+    if (!b->d_ah_pool || !b->ah_ran) return BSX_ERR_STATE;
+    HIP_TRY(hipSetDevice(b->ref->device));
+    HIP_TRY(stream_wait(b));
+    HIP_TRY(hipMemcpy(spans, b->d_ah_spans + (size_t)b->run_first * 3, (size_t)b->run_units * 3 * sizeof(bsx_span), hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+extern "C" int bsx_batch_all_hits_fetch(bsx_batch *b, uint32_t *words, uint64_t cap_words, uint64_t *used_words)
+{
+    if (!b || (!words && !used_words)) return BSX_ERR_ARG;
+    if (!b->d_ah_pool || !b->ah_ran) return BSX_ERR_STATE;
+    HIP_TRY(hipSetDevice(b->ref->device));
+    HIP_TRY(stream_wait(b));
+    uint64_t need = 0;
+    HIP_TRY(hipMemcpy(&need, b->d_ah_ctl, 8, hipMemcpyDeviceToHost));
+    const uint64_t used = std::min<uint64_t>(need, b->ah_cap);
+    if (used_words) *used_words = used;
+    if (!words) return BSX_OK;   // the size only
+    if (used > cap_words) return BSX_ERR_ARG;
+    if (used) HIP_TRY(hipMemcpy(words, b->d_ah_pool, (size_t)used * 4, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 

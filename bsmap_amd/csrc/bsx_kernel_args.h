@@ -48,6 +48,16 @@ struct AlignArgs {
     const uint8_t *hist_qual[2];
 };
 
+// all-hits pool (bsx_batch_set_all_hits): the argument of the emitting twins of the two kernels that finish units (k_align_ah, k_hctrl_ah).  Its own struct, not
+// fields of AlignArgs: the code the compiler makes for k_align depends on the layout of its argument block, and a batch without a pool must run the kernels it always ran
+struct AllHitsArgs {
+    uint32_t *pool;            // [cap] words
+    uint64_t cap;
+    unsigned long long *cursor;   // words reserved so far, units that did not fit included (the run's need)
+    uint32_t *dropped;         // units whose reservation ended behind cap
+    bsx_span *spans;           // [n_units][3]: read or mate a, mate b, pairs (zeroed before the run)
+};
+
 // The three counters of a control pass — active units it leaves, scan tasks it publishes, its work queue — take an atomic per visit each.  One memory word (one
 // L2 channel) serves about 88 atomics per microsecond: side by side in one cache line, as they were through round 5, the 3 x 179 K atomics of an RRBS pass were
 // 6 ms of its 6.4 (C4 spent as long in k_hctrl as in its scans).  A counter block keeps them 4 KB + 256 B apart (different channels), and k_hctrl takes queue
@@ -77,12 +87,14 @@ struct HeavyArgsRaw {
     uint32_t *glist;                 // k_hscan_same: start slots of the groups [task_cap], then their two counts
 };
 
-void bsx_launch_align(const AlignArgs &A, int paired, int grid_blocks, hipStream_t stream);
+void bsx_launch_align(const AlignArgs &A, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs *ah = nullptr);   // ah: launch the emitting twin
+void bsx_launch_align_ah(const AlignArgs &A, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs &X);   // bsx_align_ah.hip
+void bsx_launch_hctrl_ah(const AlignArgs &A, const HeavyArgsRaw &H, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs &X);
 void bsx_launch_leak(const AlignArgs &A, int paired, int n_cu, bool with_meta, bool resolve, void *final_out, hipStream_t stream);
 size_t bsx_leakrec_bytes(void);
 size_t bsx_leakstate_bytes(void);
 uint32_t bsx_leak_blk(void);
-void bsx_launch_hctrl(const AlignArgs &A, const HeavyArgsRaw &H, int paired, int grid_blocks, hipStream_t stream);
+void bsx_launch_hctrl(const AlignArgs &A, const HeavyArgsRaw &H, int paired, int grid_blocks, hipStream_t stream, const AllHitsArgs *ah = nullptr);
 void bsx_launch_hscan(const AlignArgs &A, const HeavyArgsRaw &H, hipStream_t stream, uint32_t max_tasks = 0);         // grid sized for H.task_cap (or max_tasks: the blocks sweep); the count stays on the device
 void bsx_launch_hscan_same(const AlignArgs &A, const HeavyArgsRaw &H, hipStream_t stream, uint32_t max_tasks = 0);    // WGBS: tasks of one window and read offset share fetch and shift
 void bsx_launch_hscan_shared(const AlignArgs &A, const HeavyArgsRaw &H, hipStream_t stream, uint32_t max_tasks = 0);  // RRBS: up to 16 tasks of one window per wave

@@ -274,6 +274,49 @@ int bsx_batch_last_heavy_units(bsx_batch *b);   /* units the last run handed to 
 int bsx_batch_last_heavy_list(bsx_batch *b, uint32_t *units, uint32_t cap);   /* their unit numbers inside the batch, in the order the main kernel deferred them (at most cap; returns how many): the tests use it to aim the oracle at them */
 int bsx_batch_last_redo_units(bsx_batch *b);    /* of those, units the main kernel had to redo (their duplicate set outgrew the heavy slab; single-end RRBS) */
 
+/* ---- all hits: every equal-best placement of a multi-mapped read or pair ------------------------------------------
+ * The record of a read says where ONE of its n_best equal-best placements lies (the reference's formatter prints one, picked by
+ * myrand(index) % n_best, align.cpp:610-627).  With a pool attached, the kernel that finishes a unit also copies the best class's
+ * whole list out of the unit's slab before the slab is reused — at full batch size, unlike the test hook bsx_batch_set_debug.
+ * The records, counts and counters of a run do not depend on the pool in any way; a batch without one allocates nothing for it
+ * and its kernels do nothing for it.  (The reference has no counterpart: v2.6 never reports the other placements.)
+ *
+ * A unit has three spans — [0] the read (single-end) or mate a, [1] mate b, [2] pairs — and emits only what its record does not
+ * already say:
+ *   single-end read, not filtered, n_best >= 2: span 0 = the best class's forward list, then its reverse-complement list:
+ *       n = n_best entries {chr, loc} of two words each, the first n_fwd of them forward; entry myrand(index) % n is the record's
+ *       own {chr, loc}, entries from n_fwd on are the ones that carry BSX_F_CHAIN;
+ *   reported pair (unpaired_out == 0) with n_pairs >= 2: span 2 = the best pair class's row, n = n_pairs entries of six words
+ *       {chain | na<<16 | nb<<24, insert, a.chr, a.loc, b.chr, b.loc} (the layout of bsx_batch_debug_pairs), n_fwd = 0;
+ *   pair with unpaired_out == 1: spans 0 / 1 = for each mate that is not filtered and has n_best >= 2, its lists as for a read;
+ *   everything else: n = 0.
+ * Lists are in the reference's order (what the parity suite compares).  A record flagged BSX_F_LIMIT emits what its lists hold.
+ *
+ * The pool is one array of 32-bit words that the units of a run share: the wave that finishes a unit reserves the unit's words
+ * (all its spans, back to back) from a device-wide cursor.  Which unit lies where depends on scheduling, what a span holds does
+ * not: address the pool through the spans only.  A unit whose reservation ends behind the pool is DROPPED: nothing of it is
+ * written, its spans have off == BSX_SPAN_DROPPED and still carry n and n_fwd, and the cursor keeps counting — so the need a run
+ * reports is exact whatever the pool size.  A caller that sees dropped units sets the pool to the reported words and runs the same
+ * units again: results are a pure function of the reads (and of the leak state in exact mode), so that run drops nothing.
+ * Needs -r 1 (report_repeat_hits == 1, the default): with -r 0 a scan stops at the second hit of the best class (align.cpp:210)
+ * and the list is cut short by design. */
+typedef struct bsx_span {
+    uint64_t off;    /* first word of the span in the pool, or BSX_SPAN_DROPPED */
+    uint32_t n;      /* entries: placements (two words each) in spans 0 and 1, pairs (six words each) in span 2 */
+    uint32_t n_fwd;  /* spans 0 and 1: how many of them are on the read's forward orientation (they come first) */
+} bsx_span;
+#define BSX_SPAN_DROPPED UINT64_MAX   /* value of off: the unit did not fit; n and n_fwd are still right */
+/* attach a pool of pool_words words (device memory: 4 bytes per word, plus 48 bytes per unit of the batch for the spans), replace the
+ * one attached, or with 0 detach and free it.  BSX_ERR_ARG unless the batch's parameters have -r 1; BSX_ERR_NOMEM */
+int bsx_batch_set_all_hits(bsx_batch *b, uint64_t pool_words);
+/* after a run (waits for it): the words the last run's units wanted in all — dropped units included —, and how many units it dropped.
+ * Spans and cursor start from zero at every bsx_batch_run / bsx_batch_run_range.  BSX_ERR_STATE without a pool or a run */
+int bsx_batch_all_hits_need(bsx_batch *b, uint64_t *words, uint32_t *dropped_units);
+/* spans[units of the last run][3]; bsx_batch_run_range: entry 0 belongs to its first_unit */
+int bsx_batch_all_hits_spans(bsx_batch *b, bsx_span *spans);
+/* the used part of the pool: min(need, pool size) words, BSX_ERR_ARG if cap_words is smaller; used_words may be NULL; words NULL: the size only */
+int bsx_batch_all_hits_fetch(bsx_batch *b, uint32_t *words, uint64_t cap_words, uint64_t *used_words);
+
 /* ---- measurement aid ("report both peak and a measured ceiling") -----------------------------------
  * Memory rates of `device` in GB/s (1e9 bytes): streaming read of `bytes`, streaming copy (read + write counted), and
  * 16-byte loads at random 4-byte-aligned addresses inside a window of `gather_window_bytes` — the access pattern of the
