@@ -22,6 +22,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -32,6 +34,7 @@
 
 #include "bsx_cpus.h"
 #include "bsx_internal.h"
+#include "bsx_meth_parse.h"
 
 namespace {
 
@@ -99,6 +102,7 @@ __global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n
     const uint32_t c = B.chr[i], st = B.strand[i];
     const int64_t n0 = (int64_t)(B.seq_off[i + 1] - B.seq_off[i]), clen = (int64_t)(M.chr_off[c + 1] - M.chr_off[c]);
     int64_t pos = B.pos[i], lo = 0, hi = n0;  // the read letters that survive are seq[lo:hi), aligned at pos
+    if (pos > clen) return;  // skipped by methratio.py:100 whatever is trimmed (no trim moves a read left); also keeps the sums below from overflowing on a hostile position
     const int64_t t = (int64_t)B.trim_fillin, ins = B.insert[i];
     if (t > 0) {  // methratio.py:55-63
         if (st == 2) py_slice(n0, false, 0, true, -t, lo, hi);                         // '+-': seq[:-t]
@@ -183,10 +187,13 @@ __global__ __launch_bounds__(256) void k_meth_emit(MethDev M, u64 g0, u64 n, uin
         if (row) {
             const uint32_t o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
             out_pos[o] = (uint32_t)k; out_depth[o] = d; out_meth[o] = m;
-            if (out_ctx) {  // refcr[i-2:i+3] with Python's slice rules (empty for i < 2 on any chromosome longer than five letters), byte 7 = the letter at i
+            if (out_ctx) {  // refcr[i-2:i+3] with Python's slice rules, byte 7 = the letter at i.  For i < 2 the start i-2 is negative and counts from the
+                            // chromosome's end: empty on a chromosome of at least five letters, but not below that ("CCGG": position 1 -> "G", "C": -> "C")
                 u64 ctx = 0;
                 int nb = 0;
-                if (k >= 2) for (u64 q = k - 2; q < k + 3 && q < n; q++) ctx |= (u64)M.ref[g0 + q] << (8 * nb++);
+                int64_t lo, hi;
+                py_slice((int64_t)n, true, (int64_t)k - 2, true, (int64_t)k + 3, lo, hi);
+                for (int64_t q = lo; q < hi; q++) ctx |= (u64)M.ref[g0 + (u64)q] << (8 * nb++);
                 out_ctx[o] = ctx | ((u64)M.ref[g0 + k] << 56);
             }
         }
@@ -378,284 +385,78 @@ extern "C" int bsx_meth_fetch_rows(bsx_meth *m, uint32_t *pos, uint32_t *depth, 
 }
 
 // ---- host side for whole files: the reference's per-line Python is the slow part of the tool once the pile-up is on the GPU ----
+// The parsers (BSP / SAM lines, BAM records, FASTA) are plain C++ in bsx_meth_parse.h, where the host sanitizers reach them.
+using bsx_meth_parse::ParsedChunk;
+
 namespace {
 
-struct ParsedChunk {
-    std::vector<uint32_t> chr; std::vector<int64_t> pos, cut; std::vector<uint8_t> strand; std::vector<int32_t> insert;
-    std::vector<char> seq; std::vector<u64> off{0};
-    u64 lines = 0;
-    int bad = 0;
+struct Mapping {  // a read-only memory map of a whole file, unmapped on every way out
+    const char *base = nullptr; size_t len = 0;
+    ~Mapping() { if (base) munmap((void *)base, len); }
+    int open(const char *path)  // BSX_OK (len == 0 for an empty file) or BSX_ERR_IO
+    {
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) { g_bsx_err = std::string("cannot open ") + path; return BSX_ERR_IO; }
+        struct stat st;
+        if (fstat(fd, &st) != 0) { ::close(fd); g_bsx_err = std::string("cannot stat ") + path; return BSX_ERR_IO; }
+        len = (size_t)st.st_size;
+        if (!len) { ::close(fd); return BSX_OK; }
+        void *q = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+        ::close(fd);
+        if (q == MAP_FAILED) { len = 0; g_bsx_err = std::string("cannot map ") + path; return BSX_ERR_IO; }
+        base = (const char *)q;
+        return BSX_OK;
+    }
 };
-
-inline bool field(const char *&p, const char *e, const char *&b, size_t &n)  // next tab-separated column of the line [p, e)
-{
-    if (p > e) return false;
-    b = p;
-    const char *t = (const char *)memchr(p, '\t', (size_t)(e - p));
-    if (!t) { n = (size_t)(e - p); p = e + 1; }
-    else { n = (size_t)(t - p); p = t + 1; }
-    return true;
-}
-
-// get_alignment's filters (methratio.py:31-48) for the lines of [b, e)
-void parse_chunk(const char *b, const char *e, int sam, const std::unordered_map<std::string, uint32_t> &cid, int unique, int pair, ParsedChunk &o)
-{
-    std::string key;
-    while (b < e) {
-        const char *nl = (const char *)memchr(b, '\n', (size_t)(e - b));
-        const char *le = nl ? nl : e;  // line without its newline
-        const char *p = b;
-        b = nl ? nl + 1 : e;
-        o.lines++;
-        const char *c[12]; size_t n[12];
-        int nc = 0;
-        while (nc < 12 && field(p, le, c[nc], n[nc])) nc++;
-        if (sam) {
-            if (n[0] && c[0][0] == '@') { o.lines--; continue; }
-            if (nc < 11) { o.bad = 1; continue; }
-            const long flag = strtol(std::string(c[1], n[1]).c_str(), nullptr, 10);
-            if ((flag & 0x4) || (unique && (flag & 0x100)) || (pair && !(flag & 0x2))) continue;
-            key.assign(c[2], n[2]);
-            auto it = cid.find(key);
-            if (it == cid.end()) continue;
-            const long long pos = strtoll(std::string(c[3], n[3]).c_str(), nullptr, 10) - 1, insert = strtoll(std::string(c[8], n[8]).c_str(), nullptr, 10);
-            // strand from the first ZS:Z: tag among the optional fields
-            const char *q = c[10] + n[10] + 1;
-            int st = -1;
-            while (q <= le) {
-                const char *fb; size_t fn;
-                if (!field(q, le, fb, fn)) break;
-                if (fn >= 7 && memcmp(fb, "ZS:Z:", 5) == 0) { st = (fb[5] == '-' ? 1 : 0) | (fb[6] == '-' ? 2 : 0); break; }
-            }
-            if (st < 0) { o.bad = 2; continue; }
-            o.chr.push_back(it->second); o.pos.push_back(pos); o.strand.push_back((uint8_t)st); o.insert.push_back((int32_t)insert);
-            o.cut.push_back(insert > 0 ? strtoll(std::string(c[7], n[7]).c_str(), nullptr, 10) - 1 : -1);
-            o.seq.insert(o.seq.end(), c[9], c[9] + n[9]); o.off.push_back(o.seq.size());
-        } else {
-            if (nc < 4) { o.bad = 1; continue; }
-            const char f0 = n[3] > 0 ? c[3][0] : 0, f1 = n[3] > 1 ? c[3][1] : 0;
-            if ((f0 == 'N' && f1 == 'M') || (f0 == 'Q' && f1 == 'C')) continue;
-            if (unique && !(f0 == 'U' && f1 == 'M')) continue;
-            if (nc < 8) { o.bad = 1; continue; }
-            if (pair && n[7] == 1 && c[7][0] == '0') continue;
-            key.assign(c[4], n[4]);
-            auto it = cid.find(key);
-            if (it == cid.end()) continue;
-            if (n[6] < 2) { o.bad = 2; continue; }
-            o.chr.push_back(it->second); o.pos.push_back(strtoll(std::string(c[5], n[5]).c_str(), nullptr, 10) - 1);
-            o.strand.push_back((uint8_t)((c[6][0] == '-' ? 1 : 0) | (c[6][1] == '-' ? 2 : 0)));
-            o.insert.push_back((int32_t)strtoll(std::string(c[7], n[7]).c_str(), nullptr, 10)); o.cut.push_back(-1);
-            o.seq.insert(o.seq.end(), c[1], c[1] + n[1]); o.off.push_back(o.seq.size());
-        }
-    }
-}
-
-// BAM, streamed: the BGZF blocks are inflated (in parallel) a bounded window at a time — a whole-genome BAM is hundreds of GB
-// inflated — and the alignment records of each window are handed to `flush` in file order (first-wins duplicate removal
-// depends on it); a record, or the header, that straddles the window edge is carried into the next window.  Fields as
-// `samtools view -X` would print them (what the reference reads): flag bits, RNAME from the header, POS, PNEXT, TLEN, SEQ, ZS:Z
-template <class Flush>
-int stream_bam(const char *base, size_t len, const std::unordered_map<std::string, uint32_t> &cid, int unique, int pair, size_t window, u64 &lines, int &bad_records,
-               Flush &&flush)
-{
-    struct Blk { size_t in_off, in_len, out_len; };
-    std::vector<Blk> blks;
-    size_t p = 0;
-    const unsigned char *u = (const unsigned char *)base;
-    while (p + 18 <= len) {
-        if (u[p] != 0x1f || u[p + 1] != 0x8b || u[p + 2] != 8 || !(u[p + 3] & 4)) return 1;
-        const unsigned xlen = u[p + 10] | (u[p + 11] << 8);
-        unsigned bsize = 0;
-        for (unsigned x = 0; x + 4 <= xlen;) {
-            const unsigned char *f = u + p + 12 + x;
-            const unsigned slen = f[2] | (f[3] << 8);
-            if (f[0] == 'B' && f[1] == 'C' && slen == 2) bsize = (f[4] | (f[5] << 8)) + 1;
-            x += 4 + slen;
-        }
-        if (bsize < 12 + xlen + 8 || p + bsize > len) return 1;
-        const unsigned isize = u[p + bsize - 4] | (u[p + bsize - 3] << 8) | (u[p + bsize - 2] << 16) | ((unsigned)u[p + bsize - 1] << 24);
-        blks.push_back(Blk{p + 12 + xlen, bsize - 12 - xlen - 8, isize});
-        p += bsize;
-    }
-    auto rd32 = [](const unsigned char *q) { int32_t v; memcpy(&v, q, 4); return v; };
-    static const char nt16[] = "=ACMGRSVTWYHKDBN";
-    std::vector<unsigned char> buf;
-    std::vector<int64_t> ref_id;  // BAM reference index -> our chromosome id or -1
-    int32_t n_ref = 0;
-    bool header_done = false;
-    size_t carry = 0;
-    for (size_t bi = 0; bi < blks.size();) {
-        size_t bj = bi, out = 0;
-        while (bj < blks.size() && (bj == bi || out + blks[bj].out_len <= window)) { out += blks[bj].out_len; bj++; }
-        buf.resize(carry + out + 8);
-        {
-            std::vector<size_t> at(bj - bi + 1, carry);
-            for (size_t i = bi; i < bj; i++) at[i - bi + 1] = at[i - bi] + blks[i].out_len;
-            std::atomic<size_t> next(bi);
-            std::atomic<int> bad(0);
-            auto work = [&] {
-                for (size_t i; (i = next.fetch_add(1)) < bj;) {
-                    if (!blks[i].out_len) continue;
-                    z_stream z;
-                    memset(&z, 0, sizeof(z));
-                    if (inflateInit2(&z, -15) != Z_OK) { bad = 1; continue; }
-                    z.next_in = const_cast<unsigned char *>(u + blks[i].in_off); z.avail_in = (unsigned)blks[i].in_len;
-                    z.next_out = buf.data() + at[i - bi]; z.avail_out = (unsigned)blks[i].out_len;
-                    if (inflate(&z, Z_FINISH) != Z_STREAM_END) bad = 1;
-                    inflateEnd(&z);
-                }
-            };
-            const size_t nt = std::min<size_t>(std::max<size_t>(1, (bj - bi) / 16), std::max(1u, std::min(32u, bsx_usable_cpus())));
-            std::vector<std::thread> th;
-            for (size_t t = 1; t < nt; t++) th.emplace_back(work);
-            work();
-            for (std::thread &x : th) x.join();
-            if (bad) return 1;
-        }
-        const unsigned char *b = buf.data(), *e = b + carry + out, *q = b;
-        bi = bj;
-        if (!header_done) {  // magic, text, reference names; all of it must be inside the buffer before it is read
-            bool complete = e - b >= 12 && e - b >= 12 + (ptrdiff_t)rd32(b + 4);
-            if (e - b >= 4 && memcmp(b, "BAM\1", 4) != 0) return 1;
-            if (complete) {
-                q = b + 8 + rd32(b + 4);
-                n_ref = rd32(q); q += 4;
-                ref_id.clear();
-                for (int32_t r = 0; r < n_ref && complete; r++) {
-                    if (q + 4 > e) { complete = false; break; }
-                    const int32_t ln = rd32(q);
-                    if (ln < 1) return 1;
-                    if (q + 4 + ln + 4 > e) { complete = false; break; }
-                    auto it = cid.find(std::string((const char *)q + 4, strnlen((const char *)q + 4, (size_t)ln)));
-                    ref_id.push_back(it == cid.end() ? -1 : (int64_t)it->second);
-                    q += 4 + ln + 4;
-                }
-            }
-            if (!complete) { carry += out; continue; }  // header longer than the window so far: read on
-            header_done = true;
-        }
-        ParsedChunk o;
-        while (q + 4 <= e) {
-            const int32_t bs = rd32(q);
-            if (bs < 32) return 1;
-            if (q + 4 + bs > e) break;  // the rest of this record is in the next window
-            const unsigned char *r = q + 4;
-            q += 4 + (size_t)bs;
-            o.lines++;
-            const int32_t tid = rd32(r), pos = rd32(r + 4), l_seq = rd32(r + 16), npos = rd32(r + 24), tlen = rd32(r + 28);
-            const unsigned l_name = r[8], n_cigar = r[12] | (r[13] << 8), flag = r[14] | (r[15] << 8);
-            if ((flag & 0x4) || (unique && (flag & 0x100)) || (pair && !(flag & 0x2))) continue;
-            if (tid < 0 || tid >= n_ref || ref_id[(size_t)tid] < 0) continue;
-            const unsigned char *sq = r + 32 + l_name + 4 * n_cigar, *ql = sq + ((size_t)l_seq + 1) / 2, *aux = ql + l_seq;
-            if (l_seq < 0 || aux > r + bs) return 1;
-            int st = -1;
-            while (aux + 3 <= r + bs) {  // optional fields: find ZS:Z
-                const unsigned char t0 = aux[0], t1 = aux[1], ty = aux[2];
-                aux += 3;
-                if (ty == 'Z' || ty == 'H') {
-                    const size_t n = strnlen((const char *)aux, (size_t)(r + bs - aux));
-                    if (t0 == 'Z' && t1 == 'S' && ty == 'Z' && n >= 2) { st = (aux[0] == '-' ? 1 : 0) | (aux[1] == '-' ? 2 : 0); break; }
-                    aux += n + 1;
-                } else if (ty == 'A' || ty == 'c' || ty == 'C') aux += 1;
-                else if (ty == 's' || ty == 'S') aux += 2;
-                else if (ty == 'i' || ty == 'I' || ty == 'f') aux += 4;
-                else if (ty == 'B') { if (aux + 5 > r + bs) break; const unsigned char sub = aux[0]; const int32_t cnt = rd32(aux + 1); aux += 5 + (size_t)cnt * ((sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : 4); }
-                else break;
-            }
-            if (st < 0) { bad_records = 2; continue; }
-            o.chr.push_back((uint32_t)ref_id[(size_t)tid]); o.pos.push_back(pos); o.strand.push_back((uint8_t)st); o.insert.push_back(tlen);
-            o.cut.push_back(tlen > 0 ? (int64_t)npos : -1);
-            for (int32_t i = 0; i < l_seq; i++) o.seq.push_back(nt16[(sq[i >> 1] >> ((~i & 1) << 2)) & 0xf]);
-            o.off.push_back(o.seq.size());
-        }
-        lines += o.lines;
-        if (!o.chr.empty()) { const int rc = flush(o); if (rc) return rc; }
-        carry = (size_t)(e - q);
-        if (carry) memmove(buf.data(), q, carry);
-    }
-    if (!header_done || carry) return 1;  // no header, or a record cut off by the end of the file
-    return 0;
-}
 
 }  // namespace
 
 extern "C" int bsx_meth_add_file(bsx_meth *m, const char *path, int sam, const char *const *chr_names, int unique, int pair, uint32_t trim_fillin, uint64_t *n_lines)
 {
     if (!m || !path || (!chr_names && m->names.size() != m->n_chr)) return BSX_ERR_ARG;
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) { g_bsx_err = std::string("cannot open ") + path; return BSX_ERR_IO; }
-    struct stat st;
-    fstat(fd, &st);
-    const size_t len = (size_t)st.st_size;
-    if (n_lines) *n_lines = 0;
-    if (!len) { ::close(fd); return BSX_OK; }
-    const char *base = (const char *)mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-    ::close(fd);
-    if (base == MAP_FAILED) { g_bsx_err = std::string("cannot map ") + path; return BSX_ERR_IO; }
-    std::unordered_map<std::string, uint32_t> cid;
-    for (uint32_t c = 0; c < m->n_chr; c++) cid.emplace(chr_names ? std::string(chr_names[c]) : m->names[c], c);
-    if (sam == 2) {  // BAM, a window of inflated blocks at a time (BSX_BAM_WINDOW bytes, default 256 MB)
+    try {  // (no C++ exception may cross the C ABI: a failed host allocation is BSX_ERR_NOMEM)
+        Mapping map;
+        if (n_lines) *n_lines = 0;
+        const int rc_open = map.open(path);
+        if (rc_open != BSX_OK || !map.len) return rc_open;
+        std::unordered_map<std::string, uint32_t> cid;
+        for (uint32_t c = 0; c < m->n_chr; c++) cid.emplace(chr_names ? std::string(chr_names[c]) : m->names[c], c);
         u64 lines = 0;
-        int bad = 0, rc_add = BSX_OK;
-        const size_t window = getenv("BSX_BAM_WINDOW") ? (size_t)std::max(1ll, atoll(getenv("BSX_BAM_WINDOW"))) : ((size_t)256 << 20);
-        const int rcs = stream_bam(base, len, cid, unique, pair, window, lines, bad, [&](ParsedChunk &pc) {
+        int rc_add = BSX_OK;
+        auto add = [&](ParsedChunk &pc) {  // alignments keep the file's order
             if (pc.chr.size() > 0xffffffffull) { rc_add = BSX_ERR_LIMIT; return 1; }
             pc.seq.push_back(0);
             rc_add = bsx_meth_add(m, (uint32_t)pc.chr.size(), pc.chr.data(), pc.pos.data(), pc.strand.data(), pc.insert.data(), pc.cut.data(), pc.seq.data(),
                                   (const uint64_t *)pc.off.data(), trim_fillin);
             return rc_add != BSX_OK ? 1 : 0;
-        });
-        munmap((void *)base, len);
+        };
+        if (sam == 2) {  // BAM, a window of inflated blocks at a time (BSX_BAM_WINDOW bytes, default 256 MB)
+            int bad = 0;
+            const size_t window = getenv("BSX_BAM_WINDOW") ? (size_t)std::max(1ll, atoll(getenv("BSX_BAM_WINDOW"))) : ((size_t)256 << 20);
+            const int rcs = bsx_meth_parse::stream_bam(map.base, map.len, cid, unique, pair, window, lines, bad, add);
+            if (n_lines) *n_lines = lines;
+            if (rc_add != BSX_OK) return rc_add;
+            if (rcs) { g_bsx_err = std::string("not a readable BAM file: ") + path; return BSX_ERR_IO; }
+            if (bad == 2) { g_bsx_err = "alignment record without strand information"; return BSX_ERR_ARG; }
+            return BSX_OK;
+        }
+        // pieces of ~256 MB (bounded host memory), each cut into per-thread chunks at line starts
+        const int rcs = bsx_meth_parse::stream_text(map.base, map.len, sam, cid, unique, pair, (size_t)256 << 20, lines, add);
         if (n_lines) *n_lines = lines;
         if (rc_add != BSX_OK) return rc_add;
-        if (rcs) { g_bsx_err = std::string("not a readable BAM file: ") + path; return BSX_ERR_IO; }
-        if (bad == 2) { g_bsx_err = "alignment record without strand information"; return BSX_ERR_ARG; }
-        return BSX_OK;
+        if (rcs == 2) { g_bsx_err = "alignment line without strand information"; return BSX_ERR_ARG; }
+        return rcs ? BSX_ERR_IO : BSX_OK;
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while reading ") + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("reading ") + path + ": " + x.what(); return BSX_ERR_IO;
     }
-    // pieces of ~256 MB (bounded host memory), each cut into per-thread chunks at line starts; alignments keep the file's order
-    const size_t piece = 256u << 20;
-    int rc = BSX_OK;
-    for (size_t p0 = 0; p0 < len && rc == BSX_OK;) {
-        size_t p1 = std::min(len, p0 + piece);
-        if (p1 < len) { const char *nl = (const char *)memchr(base + p1, '\n', len - p1); p1 = nl ? (size_t)(nl - base) + 1 : len; }
-        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(32u, std::max(1u, bsx_usable_cpus())), (p1 - p0) / (1u << 20) + 1));
-        std::vector<size_t> cut(nt + 1, p1);
-        cut[0] = p0;
-        for (unsigned t = 1; t < nt; t++) {
-            const size_t g = p0 + (p1 - p0) * t / nt;
-            const char *nl = (const char *)memchr(base + g, '\n', p1 - g);
-            cut[t] = nl ? (size_t)(nl - base) + 1 : p1;
-        }
-        std::vector<ParsedChunk> pc(nt);
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) th.emplace_back([&, t] { parse_chunk(base + cut[t], base + cut[t + 1], sam, cid, unique, pair, pc[t]); });
-        parse_chunk(base + cut[0], base + cut[1], sam, cid, unique, pair, pc[0]);
-        for (std::thread &x : th) x.join();
-        ParsedChunk all;
-        for (ParsedChunk &q : pc) {
-            if (q.bad == 2) { g_bsx_err = "alignment line without strand information"; rc = BSX_ERR_ARG; }
-            if (n_lines) *n_lines += q.lines;
-            const u64 b0 = all.seq.size();
-            all.chr.insert(all.chr.end(), q.chr.begin(), q.chr.end()); all.pos.insert(all.pos.end(), q.pos.begin(), q.pos.end());
-            all.cut.insert(all.cut.end(), q.cut.begin(), q.cut.end()); all.strand.insert(all.strand.end(), q.strand.begin(), q.strand.end());
-            all.insert.insert(all.insert.end(), q.insert.begin(), q.insert.end()); all.seq.insert(all.seq.end(), q.seq.begin(), q.seq.end());
-            for (size_t i = 1; i < q.off.size(); i++) all.off.push_back(b0 + q.off[i]);
-        }
-        if (rc == BSX_OK && !all.chr.empty()) {
-            all.seq.push_back(0);
-            rc = bsx_meth_add(m, (uint32_t)all.chr.size(), all.chr.data(), all.pos.data(), all.strand.data(), all.insert.data(), all.cut.data(), all.seq.data(), (const uint64_t *)all.off.data(), trim_fillin);
-        }
-        p0 = p1;
-    }
-    munmap((void *)base, len);
-    return rc;
 }
 
 // the table of methratio.py:130-151 for the chromosomes in `order` (the reference sorts the names), same arithmetic and formats
-extern "C" int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_order, const uint32_t *order, const char *const *chr_names, uint32_t min_depth, int meth0,
-                                    uint64_t *n_covered, uint64_t *sum_depth)
+static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const uint32_t *order, const char *const *chr_names, uint32_t min_depth, int meth0,
+                       uint64_t *n_covered, uint64_t *sum_depth)
 {
-    if (!m || !path || (!chr_names && m->names.size() != m->n_chr)) return BSX_ERR_ARG;
     std::vector<uint32_t> sorted_order;
     if (!order) {  // the reference writes the chromosomes in sorted name order
         for (uint32_t c = 0; c < m->n_chr; c++) sorted_order.push_back(c);
@@ -663,7 +464,8 @@ extern "C" int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_or
             return (chr_names ? std::string(chr_names[a]) : m->names[a]) < (chr_names ? std::string(chr_names[b]) : m->names[b]); });
         order = sorted_order.data(); n_order = m->n_chr;
     }
-    FILE *f = fopen(path, "w");
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
+    FILE *f = closer.f;
     if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
     fputs("chr\tpos\tstrand\tcontext\tratio\ttotal_C\tmethy_C\tCI_lower\tCI_upper\n", f);
     u64 nc = 0, nd = 0;
@@ -713,91 +515,50 @@ extern "C" int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_or
         for (std::thread &x : th) x.join();
         for (const std::string &o : parts) fwrite(o.data(), 1, o.size(), f);
     }
-    fclose(f);
+    closer.f = nullptr;
+    if (fclose(f) != 0 && rc == BSX_OK) { g_bsx_err = std::string("cannot write ") + path; rc = BSX_ERR_IO; }
     if (n_covered) *n_covered = nc;
     if (sum_depth) *sum_depth = nd;
     return rc;
 }
 
-// methratio.py:67-77 on a memory map: a record starts at a line whose first character is '>', its name is the first
-// token of line[1:-1], its sequence the concatenation of the stripped lines, upper-cased; `chroms_csv` is the -c filter
+extern "C" int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_order, const uint32_t *order, const char *const *chr_names, uint32_t min_depth, int meth0,
+                                    uint64_t *n_covered, uint64_t *sum_depth)
+{
+    if (!m || !path || (!chr_names && m->names.size() != m->n_chr)) return BSX_ERR_ARG;
+    try {
+        return write_table(m, path, n_order, order, chr_names, min_depth, meth0, n_covered, sum_depth);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
+    }
+}
+
+// the reference FASTA through bsx_meth_parse::parse_fasta (methratio.py:67-77); `chroms_csv` is the -c filter
 extern "C" int bsx_meth_create_from_fasta(const char *path, const char *chroms_csv, int rm_dup, int device, bsx_meth **out)
 {
     if (!path || !out) return BSX_ERR_ARG;
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) { g_bsx_err = std::string("cannot open ") + path; return BSX_ERR_IO; }
-    struct stat st;
-    fstat(fd, &st);
-    const size_t len = (size_t)st.st_size;
-    if (!len) { ::close(fd); return BSX_ERR_IO; }
-    const char *base = (const char *)mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-    ::close(fd);
-    if (base == MAP_FAILED) return BSX_ERR_IO;
-    std::vector<std::string> want;
-    if (chroms_csv && *chroms_csv) { std::string t(chroms_csv); size_t a = 0; for (;;) { const size_t c = t.find(',', a); want.push_back(t.substr(a, c == std::string::npos ? c : c - a)); if (c == std::string::npos) break; a = c + 1; } }
-    auto wanted = [&](const std::string &n) { if (want.empty()) return true; for (const std::string &w : want) if (w == n) return true; return false; };
-    struct Rec { std::string name; size_t b, e; };
-    std::vector<Rec> recs;
-    {   // header lines
-        size_t p = 0;
-        std::string cur; bool have = false; size_t sb = 0;
-        while (p < len) {
-            const char *nl = (const char *)memchr(base + p, '\n', len - p);
-            const size_t le = nl ? (size_t)(nl - base) + 1 : len;  // line including its newline
-            if (base[p] == '>') {
-                if (have && wanted(cur)) recs.push_back(Rec{cur, sb, p});
-                // name = line[1:-1].split()[0]
-                size_t a = p + 1, z = le > p + 1 ? le - 1 : p + 1;
-                while (a < z && (base[a] == ' ' || (base[a] >= '\t' && base[a] <= '\r'))) a++;
-                size_t q = a;
-                while (q < z && !(base[q] == ' ' || (base[q] >= '\t' && base[q] <= '\r'))) q++;
-                cur.assign(base + a, q - a); have = true; sb = le;
-                p = le;
-                continue;
-            }
-            // jump to the next header line
-            const char *g = p < len ? (const char *)memmem(base + p, len - p, "\n>", 2) : nullptr;
-            p = g ? (size_t)(g - base) + 1 : len;
-        }
-        if (have && wanted(cur)) recs.push_back(Rec{cur, sb, len});
+    std::vector<std::string> names;
+    std::vector<std::vector<char>> seqs;
+    try {
+        Mapping map;
+        const int rc_open = map.open(path);
+        if (rc_open != BSX_OK) return rc_open;
+        if (!map.len) return BSX_ERR_IO;
+        if (bsx_meth_parse::parse_fasta(map.base, map.len, chroms_csv, names, seqs)) { g_bsx_err = "no sequence selected from the reference file"; return BSX_ERR_ARG; }
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while reading ") + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("reading ") + path + ": " + x.what(); return BSX_ERR_IO;
     }
-    // (a name given twice keeps its last record, as the reference's dict does)
-    for (size_t i = 0; i < recs.size(); i++) for (size_t j = i + 1; j < recs.size(); j++) if (recs[i].name == recs[j].name) { recs.erase(recs.begin() + (long)i); i--; break; }
-    if (recs.empty()) { munmap((void *)base, len); g_bsx_err = "no sequence selected from the reference file"; return BSX_ERR_ARG; }
-    std::vector<std::vector<char>> seqs(recs.size());
-    {
-        std::atomic<size_t> next(0);
-        auto work = [&] {
-            for (size_t i; (i = next.fetch_add(1)) < recs.size();) {
-                std::vector<char> &o = seqs[i];
-                o.reserve(recs[i].e - recs[i].b);
-                size_t p = recs[i].b;
-                while (p < recs[i].e) {
-                    const char *nl = (const char *)memchr(base + p, '\n', recs[i].e - p);
-                    size_t a = p, z = nl ? (size_t)(nl - base) : recs[i].e;
-                    p = nl ? (size_t)(nl - base) + 1 : recs[i].e;
-                    while (a < z && (base[a] == ' ' || (base[a] >= '\t' && base[a] <= '\r'))) a++;     // line.strip()
-                    while (z > a && (base[z - 1] == ' ' || (base[z - 1] >= '\t' && base[z - 1] <= '\r'))) z--;
-                    const size_t o0 = o.size();
-                    o.insert(o.end(), base + a, base + z);
-                    for (size_t k = o0; k < o.size(); k++) if (o[k] >= 'a' && o[k] <= 'z') o[k] = (char)(o[k] - 32);
-                }
-            }
-        };
-        const size_t nt = std::min<size_t>(recs.size(), std::max(1u, std::min(32u, bsx_usable_cpus())));
-        std::vector<std::thread> th;
-        for (size_t t = 1; t < nt; t++) th.emplace_back(work);
-        work();
-        for (std::thread &x : th) x.join();
-    }
-    munmap((void *)base, len);
     std::vector<uint64_t> lens;
     for (const std::vector<char> &q : seqs) lens.push_back(q.size());
     bsx_meth *m = nullptr;
-    int rc = bsx_meth_create((uint32_t)recs.size(), lens.data(), rm_dup, device, &m);
+    int rc = bsx_meth_create((uint32_t)names.size(), lens.data(), rm_dup, device, &m);
     if (rc) return rc;
-    for (size_t i = 0; i < recs.size() && rc == BSX_OK; i++) {
-        m->names.push_back(recs[i].name);
+    for (size_t i = 0; i < names.size() && rc == BSX_OK; i++) {
+        m->names.push_back(names[i]);
         if (!seqs[i].empty() && hipMemcpy(m->d_ref + m->chr_off[i], seqs[i].data(), seqs[i].size(), hipMemcpyHostToDevice) != hipSuccess) rc = BSX_ERR_DEVICE;
         std::vector<char>().swap(seqs[i]);
     }

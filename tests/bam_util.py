@@ -1,4 +1,4 @@
-"""Minimal BAM writer for test fixtures (unaligned records in BGZF blocks; SAM spec §4).  Ours — used to feed both the
+"""Minimal BAM writer for test fixtures (unaligned and mapped records in BGZF blocks; SAM spec §4).  Ours — used to feed both the
 real bsmap binary (golden generation) and the command-line driver with the same bytes."""
 import struct
 import zlib
@@ -26,8 +26,39 @@ def record(name, seq, qual, flag=4):
     return struct.pack("<i", len(body)) + body
 
 
-def write_bam(path, records, header_text="@HD\tVN:1.0\tSO:unsorted\n", block=60000):
-    data = b"BAM\1" + struct.pack("<i", len(header_text)) + header_text.encode() + struct.pack("<i", 0) + b"".join(records)
+_AUX_SCALAR = {"A": "<c", "c": "<b", "C": "<B", "s": "<h", "S": "<H", "i": "<i", "I": "<I", "f": "<f"}
+
+
+def aux_field(tag, typ, value):
+    """one optional field: typ in A c C s S i I f (scalar), Z / H (text + NUL), B (value = (subtype, [numbers]))"""
+    head = tag.encode() + typ.encode()
+    if typ in ("Z", "H"):
+        return head + value.encode() + b"\0"
+    if typ == "B":
+        sub, vals = value
+        return head + sub.encode() + struct.pack("<i", len(vals)) + b"".join(struct.pack(_AUX_SCALAR[sub], v) for v in vals)
+    return head + struct.pack(_AUX_SCALAR[typ], value.encode() if typ == "A" else value)
+
+
+def mapped_record(name, seq, qual, flag, tid, pos, next_pos=-1, tlen=0, mapq=255, next_tid=None, aux=()):
+    """one mapped alignment record: tid = index into write_bam's `refs`, pos / next_pos 0-based, CIGAR = <len>M, aux = [(tag, type,
+    value)] in the order given (see aux_field)"""
+    l = len(seq)
+    packed = bytearray((l + 1) // 2)
+    for i, c in enumerate(seq):
+        packed[i >> 1] |= _NT16.get(c.upper(), 15) << (4 if i % 2 == 0 else 0)
+    q = bytes((ord(c) - 33) & 0xff for c in qual) if qual is not None else b"\xff" * l
+    nm = name.encode() + b"\0"
+    cigar = struct.pack("<I", l << 4) if l else b""
+    body = (struct.pack("<iiIIiiii", tid, pos, (4680 << 16) | (mapq << 8) | len(nm), (flag << 16) | (1 if l else 0), l, tid if next_tid is None else next_tid, next_pos, tlen)
+            + nm + cigar + bytes(packed) + q + b"".join(aux_field(*a) for a in aux))
+    return struct.pack("<i", len(body)) + body
+
+
+def write_bam(path, records, header_text="@HD\tVN:1.0\tSO:unsorted\n", block=60000, refs=()):
+    """refs: [(name, length)] of the reference sequences mapped records point into (none for unaligned files)"""
+    ref_part = struct.pack("<i", len(refs)) + b"".join(struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", l) for n, l in refs)
+    data = b"BAM\1" + struct.pack("<i", len(header_text)) + header_text.encode() + ref_part + b"".join(records)
     with open(path, "wb") as f:
         for i in range(0, len(data), block):
             f.write(_bgzf_block(data[i:i + block]))

@@ -1,5 +1,7 @@
 """The methylation-ratio oracle (oracle/methratio_oracle.py) against the output of the reference's own methratio.py on BSP
-files written by the real bsmap binary (tests/golden/methratio.json.gz, made by tests/golden/make_golden_methratio.py)."""
+files written by the real bsmap binary (tests/golden/methratio.json.gz, made by tests/golden/make_golden_methratio.py), and
+on the hand-made edge set (tests/golden/methratio_edges.json.gz, make_golden_methratio_edges.py: contigs of 1-7 letters, reads
+across chromosome ends, inserts around the read length, deep piles, PNEXT cuts) that the scale tests of the GPU tool lean on."""
 import gzip
 import json
 import os
@@ -24,3 +26,17 @@ def test_oracle_matches_reference_script(case, i):
         assert summary is None  # nothing covered: the reference divides by zero in its last print
     else:
         assert summary == run["stdout"]
+
+
+EDGES = json.load(gzip.open(os.path.join(G.GOLDEN, "methratio_edges.json.gz"), "rt"))
+EDGE_RUNS = [(c, i) for c in sorted(EDGES["cases"]) for i in range(len(EDGES["cases"][c]["runs"]))]
+
+
+@pytest.mark.parametrize("case,i", EDGE_RUNS, ids=[f"{c}-{'_'.join(EDGES['cases'][c]['runs'][i]['options']) or 'default'}" for c, i in EDGE_RUNS])
+def test_oracle_matches_reference_script_on_the_edge_set(case, i):
+    c = EDGES["cases"][case]
+    run = c["runs"][i]
+    assert not run["crashed"]  # (the generator refuses to store a crashed run: it would pin nothing)
+    table, summary = MO.run(EDGES["fasta"], [(f, c["files"][f]) for f in c["infiles"]], MO.options_from_argv(run["options"]))
+    assert table == run["table"]
+    assert summary == run["stdout"]
