@@ -13,7 +13,9 @@
 //                alternating scans of UnmaskRegion over it exactly as the chunk-parallel host packer does (dbseq.cpp:114-142).
 // WGBS references only: the RRBS site tables and the {tag, loc} index are assembled on the host from the text (bsx_host.cpp, bsx_index.hip).
 // tests: every packed word, anchor and block of the golden sets and of the oracle's own pack (tests/test_gpu_parity.py::test_reference_and_index,
-// tests/test_gpu_pack.py: the texts of tests/test_pack_cpu.py in regular and irregular form).
+// tests/test_gpu_pack.py: the texts of tests/test_pack_cpu.py in regular and irregular form); the edges — chromosomes of 29, 30, 47, 64, 4 992 and 4 993 letters, each padded to
+// ceil(nt / 16) + 2 words, a leading NNNNN, N runs of 1 and 40 letters, islands of 29 and 30, a run that reaches the last letter — are held by tests/test_gpu_boundaries.py (words, blocks and
+// index against the oracle's, then reads at every one of those edges).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
