@@ -6,6 +6,7 @@
 // Here the per-alignment part runs as one wave per alignment with atomic counters in HBM:
 //   k_meth_first   input-order duplicate removal: atomicMin of the alignment's global index on its fragment-end slot
 //   k_meth_pile    trim, bounds test, compare read and reference letters, atomicAdd on depth / methylated counters
+//   k_meth_pile_mbias   the same pile-up in a persistent grid that also tallies every call by strand, context and read cycle (M-bias, --mbias) in LDS
 //   k_meth_cpg     fold the G of every CG into its C
 //   k_meth_count / k_meth_emit   ordered compaction of the positions the table will list
 // The host side (bsmap_amd/methratio.py) parses the option surface, the FASTA and the BSP / SAM lines, and prints the
@@ -58,7 +59,17 @@ struct AlnBatch {
     const uint8_t *seq;
     const u64 *seq_off;
     uint32_t n, index_base, trim_fillin;
+    uint32_t trim5, trim3;     // calls of the first trim5 / last trim3 sequencing cycles of every read are ignored
 };
+
+// M-bias tally: cells[strand code 0..3][context 0..3][cycle 0..BSX_MBIAS_CYCLES-1][methylated ? 1 : 0], then one counter of the calls at later cycles
+struct MbiasDev {
+    u64 *cells, *overflow;
+};
+constexpr int MB_LDS_CYCLES = 256;                    // cycles a block tallies in LDS: 16 groups x 2 x 256 x 4 B = 32 KiB; later cycles go to HBM directly
+constexpr int MB_LDS_CELLS = 16 * 2 * MB_LDS_CYCLES;
+constexpr int MB_BLOCK = 1024, MB_BLOCKS_PER_CU = 2;  // 32 waves per CU, 64 KiB of its LDS
+constexpr size_t MB_CELLS = (size_t)16 * BSX_MBIAS_CYCLES * 2;
 
 // Python's s[a:b] on a string of length n (a, b may be negative or past the ends) as [lo, hi)
 __device__ __forceinline__ void py_slice(int64_t n, bool has_a, int64_t a, bool has_b, int64_t b, int64_t &lo, int64_t &hi)
@@ -89,20 +100,23 @@ __global__ void k_meth_first(MethDev M, AlnBatch B)
     if (dup_slot(M, B, i, slot)) atomicMin(&M.first[slot], B.index_base + i);
 }
 
-// one wave per alignment
-__global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n_valid)
+// What survives of alignment i: the read letters seq[lo:hi) of its n0, aligned at pos of chromosome c.  False for an alignment that is not a valid
+// mapping: a duplicate (methratio.py:52-56) or one that fails a bounds test (:102).  Depends on i alone, so it is uniform over the wave.
+struct MethWindow {
+    int64_t n0, lo, hi, pos;
+    uint32_t c, st;
+};
+
+__device__ __forceinline__ bool meth_window(const MethDev &M, const AlnBatch &B, uint32_t i, MethWindow &W)
 {
-    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (i >= B.n) return;
     if (M.first) {
         u64 slot;
-        if (dup_slot(M, B, i, slot) && M.first[slot] != B.index_base + i) return;  // an earlier alignment owns this fragment end
+        if (dup_slot(M, B, i, slot) && M.first[slot] != B.index_base + i) return false;  // an earlier alignment owns this fragment end
     }
     const uint32_t c = B.chr[i], st = B.strand[i];
     const int64_t n0 = (int64_t)(B.seq_off[i + 1] - B.seq_off[i]), clen = (int64_t)(M.chr_off[c + 1] - M.chr_off[c]);
     int64_t pos = B.pos[i], lo = 0, hi = n0;  // the read letters that survive are seq[lo:hi), aligned at pos
-    if (pos > clen) return;  // skipped by methratio.py:100 whatever is trimmed (no trim moves a read left); also keeps the sums below from overflowing on a hostile position
+    if (pos > clen) return false;  // skipped by methratio.py:100 whatever is trimmed (no trim moves a read left); also keeps the sums below from overflowing on a hostile position
     const int64_t t = (int64_t)B.trim_fillin, ins = B.insert[i];
     if (t > 0) {  // methratio.py:55-63
         if (st == 2) py_slice(n0, false, 0, true, -t, lo, hi);                         // '+-': seq[:-t]
@@ -118,18 +132,106 @@ __global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n
         py_slice(hi - lo, false, 0, true, B.cut_at[i] - pos, l2, h2);
         hi = lo + h2;
     }
-    const int64_t len = hi - lo;
-    if (pos + len > clen) return;  // methratio.py:100
-    if (lane == 0) atomicAdd(n_valid, 1ull);
-    if (pos < 0) return;           // (a negative position would make the reference slice from the chromosome's end: never produced by bsmap)
-    const uint8_t match = (st & 1) ? 'G' : 'C', convert = (st & 1) ? 'A' : 'T';  // strand[0]: '+' -> C/T, '-' -> G/A
-    const uint8_t *s = B.seq + B.seq_off[i] + lo;
-    const u64 g0 = M.chr_off[c] + (u64)pos;
+    if (pos + (hi - lo) > clen) return false;  // methratio.py:100
+    W.n0 = n0; W.lo = lo; W.hi = hi; W.pos = pos; W.c = c; W.st = st;
+    return true;
+}
+
+// Context class of the cytosine at global letter g of the chromosome [c0, c1): 0 CG, 1 CHG, 2 CHH, 3 "CN".  '+' strands look at the next two letters; '-'
+// strands (the call is a G) at the previous two, with C in the role of G.  A neighbour outside the chromosome counts as no letter: the concatenated text
+// goes on with the next chromosome there (the trap of k_meth_cpg), so both indices are tested against [c0, c1) before they are read.
+__device__ __forceinline__ uint32_t meth_context(const uint8_t *ref, u64 g, u64 c0, u64 c1, bool plus)
+{
+    uint8_t n1 = 0, n2 = 0;
+    if (plus) { if (g + 1 < c1) n1 = ref[g + 1]; if (g + 2 < c1) n2 = ref[g + 2]; }
+    else { if (g >= c0 + 1) n1 = ref[g - 1]; if (g >= c0 + 2) n2 = ref[g - 2]; }
+    const uint8_t gl = plus ? 'G' : 'C', other = plus ? 'C' : 'G';  // H = A, T and `other`
+    if (n1 == gl) return 0;
+    if (n1 != 'A' && n1 != 'T' && n1 != other) return 3;
+    if (n2 == gl) return 1;
+    return (n2 == 'A' || n2 == 'T' || n2 == other) ? 2 : 3;
+}
+
+// The calls of one valid alignment, a lane per letter: depth / methylated counters, and with MBIAS the tally cell of every call.
+// Cycle of letter j of the untrimmed read = its 0-based index in sequencing direction: j for '++' and '--', n0-1-j for '-+' and '+-'.  (methratio.py:52-63:
+// the fragment end of '+-' / '-+' is the displayed right end, '+-' loses its fill-in at the displayed right = its first cycles, '--' at the displayed left.)
+// A call at cycle c is dropped when c < trim5 or c >= n0 - trim3; the window, and with it pos, the bounds tests and the duplicate filter, does not move.
+template <bool MBIAS>
+__device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, uint32_t i, const MethWindow &W, int lane, uint32_t *s_tally, const MbiasDev &D, u64 &over)
+{
+    if (W.pos < 0) return;         // (a negative position would make the reference slice from the chromosome's end: never produced by bsmap)
+    const uint32_t st = W.st;
+    const bool plus = !(st & 1), backward = st == 1 || st == 2;
+    const uint8_t match = plus ? 'C' : 'G', convert = plus ? 'T' : 'A';  // strand[0]: '+' -> C/T, '-' -> G/A
+    const uint8_t *s = B.seq + B.seq_off[i] + W.lo;
+    const u64 c0 = M.chr_off[W.c], c1 = M.chr_off[W.c + 1], g0 = c0 + (u64)W.pos;
+    const int64_t len = W.hi - W.lo, cyc_lo = (int64_t)B.trim5, cyc_hi = W.n0 - (int64_t)B.trim3;
     for (int64_t k = lane; k < len; k += 64) {
         if (M.ref[g0 + k] != match) continue;
         const uint8_t ch = s[k];
-        if (ch == convert) atomicAdd(&M.depth[g0 + k], 1u);
-        else if (ch == match) { atomicAdd(&M.meth[g0 + k], 1u); atomicAdd(&M.depth[g0 + k], 1u); }
+        if (ch != convert && ch != match) continue;
+        const int64_t j = W.lo + k, cyc = backward ? W.n0 - 1 - j : j;  // 0 <= cyc < n0
+        if (cyc < cyc_lo || cyc >= cyc_hi) continue;
+        const uint32_t m = ch == match;
+        if (m) atomicAdd(&M.meth[g0 + k], 1u);
+        atomicAdd(&M.depth[g0 + k], 1u);
+        if (MBIAS) {
+            if (cyc >= BSX_MBIAS_CYCLES) { over++; continue; }
+            const uint32_t grp = st * 4 + meth_context(M.ref, g0 + k, c0, c1, plus);
+            // LDS cells are [group][methylated][cycle]: the lanes of a wave hold consecutive cycles, so consecutive words (no bank is hit twice)
+            if (cyc < MB_LDS_CYCLES) atomicAdd(&s_tally[(grp * 2 + m) * MB_LDS_CYCLES + (uint32_t)cyc], 1u);
+            else atomicAdd(&D.cells[((u64)grp * BSX_MBIAS_CYCLES + (u64)cyc) * 2 + m], 1ull);
+        }
+    }
+}
+
+// one wave per alignment
+__global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n_valid)
+{
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= B.n) return;
+    MethWindow W;
+    if (!meth_window(M, B, i, W)) return;
+    if (lane == 0) atomicAdd(n_valid, 1ull);
+    u64 over = 0;
+    meth_calls<false>(M, B, i, W, lane, nullptr, MbiasDev{nullptr, nullptr}, over);
+}
+
+// The twin of k_meth_pile with the M-bias tally: a grid sized by the CU count, every wave walks the alignments with the grid's stride.  The cells of the
+// first MB_LDS_CYCLES cycles are private to the block in LDS (a wave's 64 lanes are 64 cycles of one read: distinct cells) and reach HBM once, when the
+// block is done, as one 64-bit atomicAdd per non-zero cell; the count of valid mappings and the overflow count take the same way.  An LDS cell gets at
+// most one call per alignment and a batch has fewer than 2^32 alignments, so 32 bits hold it.
+__global__ __launch_bounds__(MB_BLOCK) void k_meth_pile_mbias(MethDev M, AlnBatch B, u64 *n_valid, MbiasDev D)
+{
+    __shared__ uint32_t s_tally[MB_LDS_CELLS];
+    __shared__ u64 s_over;
+    __shared__ uint32_t s_valid;
+    for (uint32_t t = threadIdx.x; t < (uint32_t)MB_LDS_CELLS; t += blockDim.x) s_tally[t] = 0;
+    if (threadIdx.x == 0) { s_over = 0; s_valid = 0; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const uint32_t waves = blockDim.x >> 6;
+    uint32_t valid = 0;
+    u64 over = 0;
+    for (u64 i = (u64)blockIdx.x * waves + (threadIdx.x >> 6); i < B.n; i += (u64)gridDim.x * waves) {
+        MethWindow W;
+        if (!meth_window(M, B, (uint32_t)i, W)) continue;
+        valid++;
+        meth_calls<true>(M, B, (uint32_t)i, W, lane, s_tally, D, over);
+    }
+    if (lane == 0 && valid) atomicAdd(&s_valid, valid);
+    if (over) atomicAdd(&s_over, over);
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < (uint32_t)MB_LDS_CELLS; t += blockDim.x) {
+        const uint32_t v = s_tally[t];
+        if (!v) continue;
+        const uint32_t gm = t / MB_LDS_CYCLES, cyc = t % MB_LDS_CYCLES;  // gm = group * 2 + methylated
+        atomicAdd(&D.cells[((u64)(gm >> 1) * BSX_MBIAS_CYCLES + cyc) * 2 + (gm & 1)], (u64)v);
+    }
+    if (threadIdx.x == 0) {
+        if (s_valid) atomicAdd(n_valid, (u64)s_valid);
+        if (s_over) atomicAdd(D.overflow, s_over);
     }
 }
 
@@ -212,6 +314,9 @@ struct bsx_meth {
     u64 *d_chr_off = nullptr, *d_counts = nullptr;  // d_counts: [0] valid alignments, [1] nc, [2] nd
     uint32_t *d_depth = nullptr, *d_meth = nullptr, *d_first = nullptr;
     uint32_t index_base = 0;
+    uint32_t trim5 = 0, trim3 = 0;  // bsx_meth_set_cycle_trim
+    u64 *d_mbias = nullptr;         // bsx_meth_set_mbias: MB_CELLS cells and the overflow counter, or null
+    int n_cu = 0;
     hipStream_t stream = nullptr;
     // report buffers of the last bsx_meth_report_chr
     uint32_t *d_blk = nullptr, *d_blk_start = nullptr, *d_out[3] = {nullptr, nullptr, nullptr};
@@ -228,7 +333,7 @@ extern "C" void bsx_meth_destroy(bsx_meth *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     for (void *q : {(void *)m->d_ref, (void *)m->d_chr_off, (void *)m->d_counts, (void *)m->d_depth, (void *)m->d_meth, (void *)m->d_first, (void *)m->d_blk,
-                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp})
+                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias})
         if (q) (void)hipFree(q);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
@@ -243,6 +348,7 @@ extern "C" int bsx_meth_create(uint32_t n_chr, const uint64_t *chr_len, int rm_d
     HIP_TRY(hipSetDevice(device));
     bsx_meth *m = new bsx_meth();
     m->device = device; m->n_chr = n_chr;
+    if (hipDeviceGetAttribute(&m->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || m->n_cu <= 0) { delete m; return BSX_ERR_DEVICE; }
     m->chr_off.assign(1, 0);
     for (uint32_t c = 0; c < n_chr; c++) m->chr_off.push_back(m->chr_off.back() + chr_len[c]);
     const u64 total = m->chr_off.back();
@@ -293,16 +399,97 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
     }
     if (rc == BSX_OK) {
         AlnBatch B; B.chr = d_chr; B.pos = d_pos; B.strand = d_strand; B.insert = d_ins; B.cut_at = d_cut; B.seq = d_seq; B.seq_off = d_off;
-        B.n = n; B.index_base = m->index_base; B.trim_fillin = trim_fillin;
+        B.n = n; B.index_base = m->index_base; B.trim_fillin = trim_fillin; B.trim5 = m->trim5; B.trim3 = m->trim3;
         const MethDev M = m->dev();
         if (m->d_first) hipLaunchKernelGGL(k_meth_first, dim3((n + 255) / 256), dim3(256), 0, m->stream, M, B);
-        hipLaunchKernelGGL(k_meth_pile, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts);
+        if (m->d_mbias) {  // the grid comes from the CU count; a batch too small to give every wave an alignment gets fewer blocks (fewer flushes)
+            const unsigned waves = MB_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * MB_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
+            hipLaunchKernelGGL(k_meth_pile_mbias, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, m->d_counts, MbiasDev{m->d_mbias, m->d_mbias + MB_CELLS});
+        } else
+            hipLaunchKernelGGL(k_meth_pile, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts);
         chk(hipGetLastError());
         chk(hipStreamSynchronize(m->stream));
         m->index_base += n;
     }
     for (void *q : {(void *)d_chr, (void *)d_pos, (void *)d_cut, (void *)d_strand, (void *)d_ins, (void *)d_seq, (void *)d_off}) if (q) (void)hipFree(q);
     return rc;
+}
+
+extern "C" int bsx_meth_set_cycle_trim(bsx_meth *m, uint32_t trim5, uint32_t trim3)
+{
+    if (!m) return BSX_ERR_ARG;
+    m->trim5 = trim5; m->trim3 = trim3;
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_set_mbias(bsx_meth *m, int on)
+{
+    if (!m) return BSX_ERR_ARG;
+    if (m->index_base) { g_bsx_err = "bsx_meth_set_mbias after alignments have been added"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!on) {
+        if (m->d_mbias) (void)hipFree(m->d_mbias);
+        m->d_mbias = nullptr;
+        return BSX_OK;
+    }
+    if (m->d_mbias) return BSX_OK;
+    if (hipMalloc((void **)&m->d_mbias, (MB_CELLS + 1) * 8) != hipSuccess) { m->d_mbias = nullptr; return BSX_ERR_NOMEM; }
+    hipError_t e = hipMemsetAsync(m->d_mbias, 0, (MB_CELLS + 1) * 8, m->stream);  // on the handle's stream: it does not wait for the null stream
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) { (void)hipFree(m->d_mbias); m->d_mbias = nullptr; HIP_TRY(e); }
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_mbias_fetch(bsx_meth *m, uint64_t *cells, uint64_t *overflow_calls)
+{
+    if (!m || !cells) return BSX_ERR_ARG;
+    if (!m->d_mbias) { g_bsx_err = "the M-bias tally is off (bsx_meth_set_mbias)"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpy(cells, m->d_mbias, MB_CELLS * 8, hipMemcpyDeviceToHost));
+    if (overflow_calls) HIP_TRY(hipMemcpy(overflow_calls, m->d_mbias + MB_CELLS, 8, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_write_mbias(bsx_meth *m, const char *path)
+{
+    if (!m || !path) return BSX_ERR_ARG;
+    try {
+        std::vector<uint64_t> cells(MB_CELLS);
+        uint64_t over = 0;
+        const int rc = bsx_meth_mbias_fetch(m, cells.data(), &over);
+        if (rc) return rc;
+        auto cell = [&](int grp, int cyc, int me) { return cells[((size_t)grp * BSX_MBIAS_CYCLES + (size_t)cyc) * 2 + (size_t)me]; };
+        int lmax = 0;  // cycles to print: up to the last one with a call in any group
+        for (int grp = 0; grp < 16; grp++)
+            for (int cyc = lmax; cyc < BSX_MBIAS_CYCLES; cyc++) if (cell(grp, cyc, 0) | cell(grp, cyc, 1)) lmax = cyc + 1;
+        static const char *const strands[4] = {"++", "-+", "+-", "--"}, *const contexts[4] = {"CG", "CHG", "CHH", "CN"};
+        std::string o = "strand\tcontext\tcycle\tmeth\tdepth\tratio\n";
+        char line[160];
+        auto ratio = [](uint64_t me, uint64_t d, char *buf, size_t cap) { if (d) snprintf(buf, cap, "%.3f", (double)me / (double)d); else snprintf(buf, cap, "NA"); };
+        uint64_t tot[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+        for (int grp = 0; grp < 16; grp++)
+            for (int cyc = 0; cyc < BSX_MBIAS_CYCLES; cyc++) {
+                const uint64_t me = cell(grp, cyc, 1), d = cell(grp, cyc, 0) + me;
+                tot[grp & 3][0] += me; tot[grp & 3][1] += d;
+                if (cyc >= lmax) continue;
+                char r[32];
+                ratio(me, d, r, sizeof(r));
+                o.append(line, (size_t)snprintf(line, sizeof(line), "%s\t%s\t%d\t%llu\t%llu\t%s\n", strands[grp >> 2], contexts[grp & 3], cyc + 1, (u64)me, (u64)d, r));
+            }
+        for (int x = 0; x < 4; x++) {
+            char r[32];
+            ratio(tot[x][0], tot[x][1], r, sizeof(r));
+            o.append(line, (size_t)snprintf(line, sizeof(line), "# total\t%s\t%llu\t%llu\t%s\n", contexts[x], (u64)tot[x][0], (u64)tot[x][1], r));
+        }
+        o.append(line, (size_t)snprintf(line, sizeof(line), "# calls beyond cycle %d: %llu\n", BSX_MBIAS_CYCLES, (u64)over));
+        FILE *f = fopen(path, "w");
+        if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+        const bool bad = fwrite(o.data(), 1, o.size(), f) != o.size();
+        if ((fclose(f) != 0) | bad) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+        return BSX_OK;
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
+    }
 }
 
 extern "C" int bsx_meth_combine_cpg(bsx_meth *m)

@@ -11,7 +11,9 @@ fallback: without the library and a gfx950 device this fails.
     python -m bsmap_amd.methratio -o out.txt -d genome.fa [options] alignments.bsp|.sam [...]
 
 Differences from the reference: SAM and BAM files are read directly (numeric flags: 0x4 = 'u', 0x100 = 's', 0x2 = 'P' of
-`samtools view -X`; BGZF through zlib), no samtools is spawned and `-s` is accepted and ignored."""
+`samtools view -X`; BGZF through zlib), no samtools is spawned and `-s` is accepted and ignored.  Extensions: `--mbias=FILE`
+writes the M-bias table (methylated / all calls per sequencing cycle, strand and cytosine context, tallied by the pile-up
+kernel), `--trim-5p=N` / `--trim-3p=N` ignore the calls of the first / last N cycles of every read."""
 import ctypes as C
 import sys
 import time
@@ -19,6 +21,10 @@ import time
 import numpy as np
 
 from . import lib, _check
+
+MBIAS_CYCLES = 1024  # BSX_MBIAS_CYCLES of include/bsx.h: bsx_meth_mbias_fetch fills [4][4][MBIAS_CYCLES][2] uint64
+MBIAS_STRANDS = ("++", "-+", "+-", "--")
+MBIAS_CONTEXTS = ("CG", "CHG", "CHH", "CN")
 
 def _bind():
     L = lib()
@@ -36,8 +42,20 @@ def _bind():
     L.bsx_meth_create_from_fasta.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
     L.bsx_meth_add_file.argtypes = [vp, C.c_char_p, i32, vp, i32, i32, u32, vp]
     L.bsx_meth_write_table.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, i32, vp, vp]
+    L.bsx_meth_set_cycle_trim.argtypes = [vp, u32, u32]
+    L.bsx_meth_set_mbias.argtypes = [vp, i32]
+    L.bsx_meth_mbias_fetch.argtypes = [vp, vp, vp]
+    L.bsx_meth_write_mbias.argtypes = [vp, C.c_char_p]
     L._meth_bound = True
     return L
+
+
+def mbias_fetch(L, h):
+    """the M-bias cells of a handle as uint64 [strand][context][cycle][unmethylated, methylated] and the count of calls beyond the last cycle"""
+    cells = np.zeros((4, 4, MBIAS_CYCLES, 2), np.uint64)
+    over = C.c_uint64()
+    _check(L.bsx_meth_mbias_fetch(h, cells.ctypes.data, C.byref(over)))
+    return cells, over.value
 
 
 def load_reference(path, chroms):
@@ -57,7 +75,7 @@ def load_reference(path, chroms):
 
 
 def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=False, rm_dup=False, trim_fillin=2, combine_CpG=False,
-        min_depth=1, device=0, quiet=True):
+        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0):
     """returns the summary line the reference prints on stdout"""
     def disp(txt):
         if not quiet:
@@ -68,11 +86,18 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
     h = C.c_void_p()
     _check(L.bsx_meth_create_from_fasta(reffile.encode(), ",".join(chroms).encode() if chroms else None, 1 if rm_dup else 0, device, C.byref(h)))
     try:
+        if mbias:
+            _check(L.bsx_meth_set_mbias(h, 1))
+        if trim5 or trim3:
+            _check(L.bsx_meth_set_cycle_trim(h, trim5, trim3))
         for infile in infiles:
             disp("reading %s ..." % infile)
             ext = infile[-4:].upper()
             nl = C.c_uint64()
             _check(L.bsx_meth_add_file(h, infile.encode(), 2 if ext == ".BAM" else 1 if ext == ".SAM" else 0, None, 1 if unique else 0, 1 if pair else 0, max(0, trim_fillin), C.byref(nl)))
+        if mbias:
+            disp("writing %s ..." % mbias)
+            _check(L.bsx_meth_write_mbias(h, mbias.encode()))
         if combine_CpG:
             disp("combining CpG methylation from both strands ...")
             _check(L.bsx_meth_combine_cpg(h))
@@ -106,10 +131,19 @@ def main(argv=None):
     ap.add_argument("-g", "--combine-CpG", dest="combine_CpG", action="store_true", help="add the counts of the G of each CpG to its C")
     ap.add_argument("-m", "--min-depth", dest="min_depth", type=int, default=1, help="lowest depth a listed cytosine must have (default 1)")
     ap.add_argument("-G", "--gpu", dest="device", type=int, default=0, help="GPU ordinal (extension)")
+    def cycles(txt):
+        n = int(txt)
+        if n < 0:
+            raise argparse.ArgumentTypeError("a number of cycles cannot be negative")
+        return n
+    ap.add_argument("--mbias", dest="mbias", default=None, metavar="FILE", help="write the M-bias table: methylated / all calls per read cycle, strand and context (extension)")
+    ap.add_argument("--trim-5p", dest="trim5", type=cycles, default=0, metavar="N", help="ignore the calls of the first N sequencing cycles of every read (extension, default 0)")
+    ap.add_argument("--trim-3p", dest="trim3", type=cycles, default=0, metavar="N", help="ignore the calls of the last N sequencing cycles of every read (extension, default 0)")
     ap.add_argument("infiles", nargs="+", help="mapping files written by bsmap: *.sam / *.bam by their format, anything else as BSP")
     o = ap.parse_args(argv)
     sys.stdout.write(run(o.reffile, o.infiles, o.outfile, chroms=o.chroms.split(",") if o.chroms else None, unique=o.unique, pair=o.pair, meth0=o.meth0,
-                         rm_dup=o.rm_dup, trim_fillin=o.trim_fillin, combine_CpG=o.combine_CpG, min_depth=o.min_depth, device=o.device, quiet=o.quiet))
+                         rm_dup=o.rm_dup, trim_fillin=o.trim_fillin, combine_CpG=o.combine_CpG, min_depth=o.min_depth, device=o.device, quiet=o.quiet,
+                         mbias=o.mbias, trim5=o.trim5, trim3=o.trim3))
 
 
 if __name__ == "__main__":

@@ -349,6 +349,23 @@ int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const int64_t *po
  * threads with get_alignment's filters (NM/QC or unmapped, -u unique, -p pair, chromosome known; methratio.py:31-48), alignments
  * keep the file's order; chr_names[n_chr] in id order */
 int bsx_meth_add_file(bsx_meth *m, const char *path, int sam, const char *const *chr_names, int unique, int pair, uint32_t trim_fillin, uint64_t *n_lines);
+/* Cycle trimming (extension): in every later bsx_meth_add / bsx_meth_add_file a call at sequencing cycle c (the letter's 0-based index in
+ * the untrimmed read of n0 letters in sequencing direction: j for "++" / "--", n0-1-j for "-+" / "+-") is ignored when c < trim5 or
+ * c >= n0 - trim3.  Calls only: position, bounds tests, duplicate removal and the count of valid mappings do not change; a letter has
+ * to survive trim_fillin and cut_at as well. */
+int bsx_meth_set_cycle_trim(bsx_meth *m, uint32_t trim5, uint32_t trim3);
+/* M-bias tally (extension): with on != 0 allocates (zeroed) cells[4 strand codes][4 contexts: CG, CHG, CHH, other][BSX_MBIAS_CYCLES][0 unmethylated,
+ * 1 methylated] in HBM and every later add counts each call that enters depth / meth in its cell; calls at cycles >= BSX_MBIAS_CYCLES go to one
+ * overflow counter.  The tally accumulates over calls and files; bsx_meth_combine_cpg does not touch it.  on == 0 frees it.  BSX_ERR_STATE once
+ * alignments have been added. */
+#define BSX_MBIAS_CYCLES 1024
+int bsx_meth_set_mbias(bsx_meth *m, int on);
+/* the tally so far; overflow_calls may be NULL.  BSX_ERR_STATE when the M-bias is off */
+int bsx_meth_mbias_fetch(bsx_meth *m, uint64_t *cells /* [4][4][BSX_MBIAS_CYCLES][2] */, uint64_t *overflow_calls);
+/* the tally as a tab-separated file: header "strand context cycle meth depth ratio"; rows by strand (++ -+ +- --), context (CG CHG CHH CN) and
+ * 1-based cycle up to the last cycle with a call in any group, ratio "%.3f" or NA at depth 0; then "# total <context> <meth> <depth> <ratio>"
+ * per context (tab-separated, over the cells) and "# calls beyond cycle 1024: <n>".  BSX_ERR_STATE when the M-bias is off */
+int bsx_meth_write_mbias(bsx_meth *m, const char *path);
 int bsx_meth_combine_cpg(bsx_meth *m);                      /* -g, methratio.py:118-128 */
 int bsx_meth_valid_mappings(bsx_meth *m, uint64_t *n);      /* "total %d valid mappings" */
 /* rows of one chromosome's table in position order: positions with depth >= min_depth and (methylated > 0 or meth0);
