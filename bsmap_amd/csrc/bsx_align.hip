@@ -2572,8 +2572,15 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 //     returns 1 KB whatever the addresses, 8 cycles of the CU's LDS path, and four of them per chunk (k_hscan_shared's scheme)
 //     outweigh the 27 vector instructions of an evaluation — then 3 v_bitop3 + 1 v_bcnt per word and candidate, the two
 //     early-out classes of the reference (align.h:189-197) and the survivors, written in list order.
-// No second stage and no FIFO: on the hg38-sized workload 36-55 % of the candidates of a giant bucket are still within the
-// threshold after 64 nt, so a chunk of 64 practically always holds one that needs all the words.
+// No second stage and no FIFO, but with the work counters off a chunk is left as soon as none of its 64 candidates is within the
+// threshold (same_exit, HG_EXIT).  Through round 6 every word of every chunk was evaluated, on the argument that 36-55 % of a giant
+// bucket's candidates are still within the threshold after 64 nt, "so a chunk of 64 practically always holds one that needs all the
+// words".  That treats the 64 lanes as independent, and they are not: a chunk is 64 consecutive entries of one bucket against ONE read,
+// and whether the first words reject is mostly a property of the read (where its microsatellite part lies).  Measured (DESIGN 3.2,
+// round 7): per candidate 0.49 fail in the first word and 0.29 are within the threshold after 64 nt, yet only 0.017 of the (read, chunk)
+// evaluations hold a survivor; with a test behind every word a chunk takes 3.27 of its five words in their natural order and 2.03 in
+// the order 0, 4, 3, 2, 1 (GPU, C3 at bench size: 2.02).  Only reads of 129-160 nt take it: shorter reads in natural order with the test lost time
+// (hs_eval_read).  The counted instantiations (STATS) evaluate as before: both class counts need the first words of every candidate.
 // Groups of one task, and tasks that span sub-ranges, go one per wave through hp_task.  Results per task are exactly k_hscan's.
 // ---------------------------------------------------------------------------------------------------------------
 #ifndef HG_WPB
@@ -2594,6 +2601,11 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 #endif
 #ifndef HG_PREFETCH
 #define HG_PREFETCH 0   /* 1: the gathers of a step are issued a step earlier (13 registers per chunk: only fits with two chunks per step) */
+#endif
+#ifndef HG_EXIT
+#define HG_EXIT 15      /* the exiting evaluation of the WGBS groups of 129-160 nt reads without work counters (same_exit).  Bit i: a wave-uniform test behind the (i + 1)-th
+                           evaluated word (the last word's test is the survivor ballot and always there).  15 against 3: C3 209.8-210.3 against 211.3 ms per step.
+                           0 = the form before round 7: all words of every chunk, in their natural order */
 #endif
 #ifndef BSX_HSAME_WAVES
 #define BSX_HSAME_WAVES 4
@@ -2706,6 +2718,48 @@ __device__ __forceinline__ void same_counts(const uint32_t (&flo)[5], const uint
 #undef SAME_MM
 }
 
+// The exiting form (HG_EXIT; WGBS groups without the work counters): the words one at a time, and behind a word a wave-uniform test whether any
+// candidate of the chunk is still within the threshold — if none is, the chunk is done for this read.  A count only grows, so a candidate within
+// the threshold at the end was within it behind every word: a chunk that holds a survivor is never left early, its survivors carry their whole
+// count, and the mask behind the last word is the survivors' one.  Reads of 129-160 nt take their words in the order 0, 4, 3, 2, 1: whether the
+// first words reject is mostly a property of the READ (where its microsatellite part lies), the same for all 64 candidates of a chunk, and the
+// far end of the read is what differs most from the seed's surroundings (mean words per evaluation: see DESIGN 3.2).
+// word j of a 129-160 nt read against a candidate: the two-instruction form where the read has no N (words 0-3), the masked form for word 4
+template <bool PLAIN>
+__device__ __forceinline__ uint32_t same_word(int j, const uint32_t (&flo)[5], const uint32_t (&fhi)[5], const uint4 &a0, const uint4 &a1, const uint4 &a2, const uint4 &a3)
+{
+    uint32_t X, Y, M;   // (j is a constant wherever this is inlined)
+    switch (j) {
+    case 0: X = a0.x; Y = a0.y; M = a0.z; break;
+    case 1: X = a0.w; Y = a1.x; M = a1.y; break;
+    case 2: X = a1.z; Y = a1.w; M = a2.x; break;
+    case 3: X = a2.z; Y = a2.w; M = a3.x; break;
+    default: X = a3.y; Y = a3.z; M = a3.w; break;
+    }
+    return (PLAIN && j < 4) ? bsx_plane_mismatch_full(flo[j], fhi[j], X, Y) : bsx_plane_mismatch(flo[j], fhi[j], X, Y, M);
+}
+// returns the lanes within the threshold behind the last word (0: the chunk was left early, or has no survivor); tot is their count, `words` the
+// words evaluated.  FULL: every lane holds a candidate
+template <bool PLAIN, bool FULL>
+__device__ __forceinline__ u64 same_exit(const uint32_t (&flo)[5], const uint32_t (&fhi)[5], const uint4 &a0, const uint4 &a1, const uint4 &a2, const uint4 &a3,
+                                         uint32_t thr, u64 valid, uint32_t &tot, uint32_t &words)
+{
+    u64 bp = 0;
+    tot = 0;
+    // (written out: a loop that holds a ballot and leaves in its middle is not unrolled)
+#define SAME_STEP(i, j)                                                                \
+    tot = popc_acc(same_word<PLAIN>(j, flo, fhi, a0, a1, a2, a3), tot);                \
+    words = (i) + 1;                                                                   \
+    if ((i) == 4 || ((HG_EXIT >> (i)) & 1)) {                                          \
+        bp = bsx_ballot(tot <= thr);                                                   \
+        if (!FULL) bp &= valid;                                                        \
+        if (!bp) return 0;                                                             \
+    }
+    SAME_STEP(0, 0) SAME_STEP(1, 4) SAME_STEP(2, 3) SAME_STEP(3, 2) SAME_STEP(4, 1)
+#undef SAME_STEP
+    return bp;
+}
+
 // one read of a group against the step's chunks: counts and survivors.  PLAIN as in same_counts; FULL: every lane of every chunk holds a candidate
 // (all steps of a window but its last) — the masks need no AND with the valid lanes.  Both are decided once per read and step, outside the chunk loop
 // (scan 56.2-56.6 against 57.7-57.8 ms per step with the two tests inside it)
@@ -2716,10 +2770,23 @@ __device__ __forceinline__ void hs_eval_read(const uint32_t (&flo)[HG_C][5], con
 {
 #pragma unroll
     for (int u = 0; u < HG_C; u++) {
-        uint32_t w0ref, w01ref, tot;
-        same_counts<NWR, PLAIN, RRBS, STATS>(flo[u], fhi[u], him[u], nwr, a0, a1, a2, a3, thr, vm[u], w0ref, w01ref, tot);
-        u64 bp = bsx_ballot(tot <= thr);
-        if (!FULL) bp &= vm[u];
+        uint32_t w0ref = 0, w01ref = 0, tot;
+        u64 bp;
+        // (the counted instantiations keep every word: both class counts need them; RRBS lists keep SKIP; reads of 97-128 nt and of any length keep every word too:
+        //  with the test behind each word in natural order C2 ran at 178.3-183.8 against 165.5-168.9 ms per step and C5 at 489.3-492.7 against 472.2-473.4, round 7)
+        if (HG_EXIT && !STATS && !RRBS && NWR == 5) {
+            uint32_t words;
+            bp = same_exit<PLAIN, FULL>(flo[u], fhi[u], a0, a1, a2, a3, thr, vm[u], tot, words);
+#ifdef BSX_SCAN_WORDS
+            if (vm[u]) add15 += 1u + (words << 16);   // (diagnostic build: add15 is free where the work counters are off)
+#else
+            (void)words;
+#endif
+        } else {
+            same_counts<NWR, PLAIN, RRBS, STATS>(flo[u], fhi[u], him[u], nwr, a0, a1, a2, a3, thr, vm[u], w0ref, w01ref, tot);
+            bp = bsx_ballot(tot <= thr);
+            if (!FULL) bp &= vm[u];
+        }
         if (STATS) {   // the two early-out classes of the reference (align.h:189-197): work counters only, no effect on any hit
             u64 b1 = bsx_ballot(w0ref > thr), b5 = bsx_ballot(w01ref <= thr);
             if (!FULL) { b1 &= vm[u]; b5 &= vm[u]; }
@@ -2767,7 +2834,7 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     }
     // diagnostic build (-DBSX_SIGHIST_DUPS, with BSX_SIGHIST=1; round 5 measured 0.00 % for C3, 1.4 % for C2): members of the group whose read words
     // and threshold equal an earlier member's (they would yield the same survivors).  Not in the shipped kernel: it is bound by its vector issue.
-    uint32_t n_dup = 0;
+    uint32_t n_dup = 0; (void)n_dup;
 #ifdef BSX_SIGHIST_DUPS
     for (uint32_t j = 1; j < K; j++) {
         const u64 sj = ((u64)rl_u((uint32_t)(rowsig >> 32), j) << 32) | rl_u((uint32_t)rowsig, j);
@@ -2781,6 +2848,11 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     W.ref_off = strand ? P.plane_rc_off : 0u; W.anchor = P.anchor; W.plane = reinterpret_cast<const uint8_t *>(P.refplane); W.nwr = nwr;
     uint32_t c15 = 0, nsv = 0;   // lane k: counters of read k — candidates beyond the first word | five-word candidates << 16; survivors
     uint32_t n_cand = 0;         // RRBS: the entries that passed the filters
+#ifdef BSX_SCAN_WORDS
+    // diagnostic build (tools/build_variant.sh words -DBSX_SCAN_WORDS, tools/scan_words.sh): the (read, chunk) evaluations of the exiting form (reads of 129-160 nt: the only
+    // class that takes it) and the words they took — the GPU's side of the table in DESIGN 3.2.  Not in the shipped kernel
+    u64 dg_ev = 0, dg_words = 0;
+#endif
     // one step = HG_C chunks of 64 candidates.  nx: the gathers of the coming step (issued a step earlier); en: the entries of the step after it
     constexpr uint32_t STEP = 64u * HG_C;
     SameChunk nx[HG_C];
@@ -2859,6 +2931,9 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
                 else hs_eval_read<NWR, RRBS, false, false, STATS>(flo, fhi, him, vm, ordsh, hchr, hloc, nwr, a0, a1, a2, a3, thr, sv, nsk, add15);
             }
             if ((uint32_t)lane == k) { if (STATS) c15 += add15; nsv = nsk; }
+#ifdef BSX_SCAN_WORDS
+            if (!STATS) { dg_ev += add15 & 0xffffu; dg_words += add15 >> 16; }
+#endif
         }
     }
     wave_fence();
@@ -2879,8 +2954,16 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
         atomicAdd((u64 *)&sh[0], (u64)kk * n_cand);
         if (STATS) { atomicAdd((u64 *)&sh[1], 2ull * kk * n_cand - s1 + 3ull * s5); atomicAdd((u64 *)&sh[2], (u64)s1); atomicAdd((u64 *)&sh[3], (u64)s5); }
         if (K > 1) atomicAdd((u64 *)&sh[4], (u64)kk * n_cand);   // counter 15: candidates evaluated in groups of two reads and more
+#ifndef BSX_SCAN_WORDS
         atomicAdd((u64 *)&sh[5], (u64)kk * n_cand * K); if (K >= 4) atomicAdd((u64 *)&sh[6], (u64)kk * n_cand); if (n_dup) atomicAdd((u64 *)&sh[7], (u64)n_dup * n_cand);  // diagnostics (BSX_SIGHIST)
+#endif
     }
+#ifdef BSX_SCAN_WORDS
+    if (lane == 0 && dg_ev) {   // (slots 5 and 6 of shard 0, which in this build nothing else writes: hs_group's own diagnostics above are the only other writer of slots 5-7)
+        u64 *sh = (u64 *)A.scan_stats;
+        atomicAdd((u64 *)&sh[5], dg_ev); atomicAdd((u64 *)&sh[6], dg_words);
+    }
+#endif
     wave_fence();
 }
 

@@ -1156,11 +1156,20 @@ extern "C" int bsx_batch_counters(bsx_batch *b, uint64_t c[BSX_N_COUNTERS])
     HIP_TRY(hipMemcpy(c, b->d_counters, BSX_N_COUNTERS * 8, hipMemcpyDeviceToHost));
     uint64_t sh[64 * 8];
     HIP_TRY(hipMemcpy(sh, b->d_scan_stats, sizeof(sh), hipMemcpyDeviceToHost));
+#ifdef BSX_SCAN_WORDS
+    // diagnostic build: slots 5 and 6 of shard 0 hold the group scan's (read, chunk) evaluations of the exiting form and their words (hs_group; reads of 129-160 nt
+    // only, C3).  The [sighist] line is not printed by this build: its slots hold these counts instead
+    for (int i = 0; i < 64; i++) { for (int k = 0; k < 4; k++) c[7 + k] += sh[i * 8 + k]; c[15] += sh[i * 8 + 4]; }
+    if (sh[5])
+        fprintf(stderr, "[scanwords] 129-160 nt: %llu (read, 64-candidate chunk) evaluations, %llu words, mean %.3f words per evaluation\n",
+                (unsigned long long)sh[5], (unsigned long long)sh[6], (double)sh[6] / (double)sh[5]);
+#else
     uint64_t dg[3] = {0, 0, 0};
     for (int i = 0; i < 64; i++) { for (int k = 0; k < 4; k++) c[7 + k] += sh[i * 8 + k]; c[15] += sh[i * 8 + 4]; for (int k = 0; k < 3; k++) dg[k] += sh[i * 8 + 5 + k]; }
     if (b->sig_hist && c[15])
         fprintf(stderr, "[sighist] scan kernel: %.4f of the candidates in groups, mean group %.2f reads, in groups of >= 4 %.4f; evaluations of a read whose words and threshold equal an earlier member's of its group: %.4f of all\n", (double)c[15] / (double)std::max<uint64_t>(1, c[7]),
                 (double)dg[0] / (double)c[15], (double)dg[1] / (double)c[7], (double)dg[2] / (double)c[7]);
+#endif
     return BSX_OK;
 }
 extern "C" int bsx_batch_reset_counters(bsx_batch *b)
