@@ -2582,6 +2582,10 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 // the order 0, 4, 3, 2, 1 (GPU, C3 at bench size: 2.02).  Only reads of 129-160 nt take it: shorter reads in natural order with the test lost time
 // (hs_eval_read).  The counted instantiations (STATS) evaluate as before: both class counts need the first words of every candidate.
 // Groups of one task, and tasks that span sub-ranges, go one per wave through hp_task.  Results per task are exactly k_hscan's.
+// Round 8: a group of 129-160 nt reads also takes the tasks of the same window whose read offset is the group's plus 32 d, d <= HG_D (k_task_groups sorts the
+// members by d).  Such a read sees every candidate at the same bit shift, (entry + h - 1) & 31, and its reference frame is the same funnel-shifted word stream
+// read d words further on: the gather is HG_D pairs longer, the shift makes HG_D more words, and at the first row of the next d the frame moves down a word —
+// 10 register moves per chunk, once per class and step; nothing is done per read.  The positions a member is evaluated at are the ones its own group would use.
 // ---------------------------------------------------------------------------------------------------------------
 #ifndef HG_WPB
 #define HG_WPB 1        /* waves (= groups) per block: 1 measured best (1: 96.0-98.9, 2: 101.7-102.2, 4: 110.9 ms per step) — a block gives its slot back when its LAST wave ends */
@@ -2610,6 +2614,15 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 #ifndef BSX_HSAME_WAVES
 #define BSX_HSAME_WAVES 4
 #endif
+#ifndef HG_D
+#define HG_D 2          /* offset classes a WGBS group of 129-160 nt reads spans beyond its first: members' read offsets are h0 + 32 d, d = 0 .. HG_D.  They see every candidate at the
+                           same bit shift and their reference frames are one funnel-shifted word stream read d words apart: the gather is HG_D pairs longer, the frame HG_D words,
+                           and the frame moves down a word where the rows of the next d begin (hs_group).  BSX_SAME_D (0 .. HG_D) at run time; 0: groups of one offset only.
+                           Round 8, C3 ms per step, three plain runs each beside the parent's 210.6-211.2: 1: 210.9-211.3; 2: 207.0-207.7 (120 VGPRs, no scratch).  With reads of
+                           97-128 nt included C2 ran at 174.6-179.6 against 172.6-173.3: they keep groups of one offset.  BSX_SAME_D=0 is NOT the parent's kernel: the groups and
+                           the task order are the parent's, but a group of 129-160 nt reads still gathers HG_D more pairs and shifts HG_D more words per candidate; the
+                           baseline of an A/B is a build with -DHG_D=0 (or the parent's library) */
+#endif
 #ifndef HG_ROWPF
 #define HG_ROWPF 0      /* the next read's LDS row requested before this read is evaluated (16 registers) */
 #endif
@@ -2620,7 +2633,7 @@ struct SameLds {
         struct { uint32_t TAB[4][32]; uint2 PT[HP_PAIRS * 32]; uint2 Q[HP_QCAP]; } one;   // one-task path (hp_task); 4 KB per wave: k_hctrl's blocks (58 KB paired) have to fit beside 20 waves of this kernel
     } W[HG_WPB];
 };
-struct SameChunk { U4 r0, r1, r2; uint32_t pm1, strand; bool valid; };   // pairs (pm1 >> 5) .. + 5 of the plane copy; RRBS: the candidate's strand copy, and whether the entry passed the filters
+struct SameChunk { U4 r0, r1, r2, r3; uint32_t pm1, strand; bool valid; };   // pairs (pm1 >> 5) .. + 5 (+ XP: r3) of the plane copy; RRBS: the candidate's strand copy, and whether the entry passed the filters
 // what a group's window is made of.  WGBS: 4-byte entries, candidate position = entry + h.  RRBS: one bucket of {tag | chromosome, position}
 // pairs — the entries with ((tag ^ tag_xor) >> 16) == tag_want and position >= h are the candidates (align.cpp:187,229,263), position =
 // anchor[chromosome] + (position - h), each on its own strand copy
@@ -2667,9 +2680,11 @@ __global__ __launch_bounds__(256) void k_sector_pop(uint32_t n_words)
 }
 #endif
 
-template <bool RRBS>
+// XP: pairs beyond the sixth (groups that span offset classes: 0, 1 or 2)
+template <bool RRBS, int XP = 0>
 __device__ __forceinline__ SameChunk same_load(const SameWin &W, const SameEntry &e)
 {
+    static_assert(XP >= 0 && XP <= 2, "r3 holds two pairs");
     SameChunk c;
     uint32_t off = W.ref_off;
     if (RRBS) {
@@ -2684,6 +2699,9 @@ __device__ __forceinline__ SameChunk same_load(const SameWin &W, const SameEntry
     c.r1.a = c.r1.b = c.r1.c = c.r1.d = 0; c.r2.a = c.r2.b = c.r2.c = c.r2.d = 0;
     if (W.nwr > 1) c.r1 = *reinterpret_cast<const U4 *>(src + 16);
     if (W.nwr > 3) c.r2 = *reinterpret_cast<const U4 *>(src + 32);
+    c.r3.a = c.r3.b = c.r3.c = c.r3.d = 0;
+    if (XP == 1) { const U2 x = *reinterpret_cast<const U2 *>(src + 48); c.r3.a = x.a; c.r3.b = x.b; }
+    if (XP == 2) c.r3 = *reinterpret_cast<const U4 *>(src + 48);
 #ifdef BSX_SECTOR_STATS
     if (c.valid) sector_mark(hp_boff(c.pm1, off), W.nwr > 3 ? 3 : W.nwr > 1 ? 2 : 1); else sector_mark(0u, 0);
 #endif
@@ -2805,11 +2823,15 @@ __device__ __forceinline__ void hs_eval_read(const uint32_t (&flo)[HG_C][5], con
 // its own code (5: 129-160 nt, the headline configuration; 4: 97-128 nt; 3: 65-96 nt, RRBS), 0 for any length.
 template <int NWR, bool RRBS, bool STATS>
 __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H, SameLds &L, int lane, int wv, uint32_t K, uint32_t tid, uint32_t th, uint32_t tc0,
-                                         uint32_t key, uint32_t n, uint32_t hh, uint32_t flags, uint32_t tag_xor, uint32_t tag_want)
+                                         uint32_t key, uint32_t n, uint32_t hh, uint32_t sub_h, uint32_t flags, uint32_t tag_xor, uint32_t tag_want)
 {
     const DevParams &P = A.P;
     uint32_t *uw = &L.W[wv].UW[0][0];
     const int nwr = NWR ? NWR : (int)((flags >> 8) & 15u);
+    // XD: the offset classes behind the first that the group may hold (k_task_groups forms such groups for these instantiations only); XP: the pairs their frames
+    // need beyond the six of the three 16-byte gathers
+    constexpr int XD = (!RRBS && NWR == 5) ? HG_D : 0, XP = XD;
+    static_assert(HG_D >= 0 && HG_D <= 2 && 6 + HG_D <= BSX_PLANE_PAD, "the gather holds two pairs more at most, and stays inside the pad behind the strand copy");
 #ifdef BSX_SIGHIST_DUPS
     u64 rowsig = 0;
 #endif
@@ -2824,7 +2846,8 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
             row[f + o] = R.px[j]; row[f + 1 + o] = R.py[j]; row[f + 2 + o] = pm;
             if (j < nwr - 1) inner &= pm;
         }
-        row[9] = R.thres | (inner == 0xFFFFFFFFu ? 0x10000u : 0u); row[16] = tid; row[17] = tc0;
+        // (bits 17 and up: the row's offset class d — the group's frame is that of slot 0, whose d is 0, and the rows are sorted by d)
+        row[9] = R.thres | (inner == 0xFFFFFFFFu ? 0x10000u : 0u) | (XD ? ((sub_h - hh) >> 5) << 17 : 0u); row[16] = tid; row[17] = tc0;
 #ifdef BSX_SIGHIST_DUPS
         u64 hsh = R.thres;
 #pragma unroll
@@ -2844,6 +2867,8 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     wave_fence();
     const uint32_t strand = flags & 1u;
     SameWin W;
+    // (hh is the group's frame, the smallest offset of its members: a member of class d is gathered from 32 d nt before its own position on — at most 32 HG_D nt
+    //  earlier than its own group would begin; the BSX_REF_MARGIN words in front of the reference cover that, as BSX_PLANE_PAD covers the longer end)
     W.ent = P.entries + (RRBS ? 2u * (size_t)key : (size_t)key); W.n = n; W.h = hh; W.tag_xor = tag_xor; W.tag_want = tag_want; W.rc_off = P.plane_rc_off;
     W.ref_off = strand ? P.plane_rc_off : 0u; W.anchor = P.anchor; W.plane = reinterpret_cast<const uint8_t *>(P.refplane); W.nwr = nwr;
     uint32_t c15 = 0, nsv = 0;   // lane k: counters of read k — candidates beyond the first word | five-word candidates << 16; survivors
@@ -2859,7 +2884,7 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     SameEntry en[HG_C];
 #if HG_PREFETCH
 #pragma unroll
-    for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS>(W, same_entry<RRBS>(W, (uint32_t)(u * 64 + lane)));
+    for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS, XP>(W, same_entry<RRBS>(W, (uint32_t)(u * 64 + lane)));
 #pragma unroll
     for (int u = 0; u < HG_C; u++) en[u] = same_entry<RRBS>(W, STEP + (uint32_t)(u * 64 + lane));
     // (the first step's gathers are waited for here: pending into the loop they make the compiler wait for every load in flight — the coming step's too — before each step's
@@ -2873,21 +2898,25 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     for (uint32_t cb = 0; cb < n; cb += STEP) {
 #if !HG_PREFETCH
 #pragma unroll
-        for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS>(W, en[u]);
+        for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS, XP>(W, en[u]);
 #pragma unroll
         for (int u = 0; u < HG_C; u++) en[u] = same_entry<RRBS>(W, cb + STEP + (uint32_t)(u * 64 + lane));
 #endif
         // the candidates' reference planes in the read frame — the same for every read of the group
-        uint32_t flo[HG_C][5], fhi[HG_C][5], him[HG_C], hloc[HG_C], ordsh[HG_C], hchr[HG_C];
+        // (xlo, xhi: the words behind the frame, for the members whose offset is 32 d further on)
+        uint32_t flo[HG_C][5], fhi[HG_C][5], xlo[HG_C][XD ? XD : 1], xhi[HG_C][XD ? XD : 1], him[HG_C], hloc[HG_C], ordsh[HG_C], hchr[HG_C];
         u64 vm[HG_C];
 #pragma unroll
         for (int u = 0; u < HG_C; u++) {
             const SameChunk &c = nx[u];
-            const uint32_t wd[12] = {c.r0.a, c.r0.b, c.r0.c, c.r0.d, c.r1.a, c.r1.b, c.r1.c, c.r1.d, c.r2.a, c.r2.b, c.r2.c, c.r2.d};
+            const uint32_t wd[16] = {c.r0.a, c.r0.b, c.r0.c, c.r0.d, c.r1.a, c.r1.b, c.r1.c, c.r1.d, c.r2.a, c.r2.b, c.r2.c, c.r2.d, c.r3.a, c.r3.b, c.r3.c, c.r3.d};
             const uint32_t shf = 31u - (c.pm1 & 31u);                     // 32 - ((pm1 & 31) + 1)
             him[u] = 0xFFFFFFFFu << ((c.pm1 + 1u) & 15u);                 // read nt [0, 32 - k), k = position mod 16
 #pragma unroll
             for (int t = 0; t < 5; t++) { flo[u][t] = __builtin_amdgcn_alignbit(wd[2 * t], wd[2 * t + 2], shf); fhi[u][t] = __builtin_amdgcn_alignbit(wd[2 * t + 1], wd[2 * t + 3], shf); }
+#pragma unroll
+            for (int t = 5; t < 5 + XD; t++) { xlo[u][t - 5] = __builtin_amdgcn_alignbit(wd[2 * t], wd[2 * t + 2], shf); xhi[u][t - 5] = __builtin_amdgcn_alignbit(wd[2 * t + 1], wd[2 * t + 3], shf); }
+            if (!XD) xlo[u][0] = xhi[u][0] = 0;
             hloc[u] = c.pm1 + 1u;
             hchr[u] = RRBS ? c.strand : strand;
             ordsh[u] = (cb + (uint32_t)(u * 64 + lane)) << 8;
@@ -2897,7 +2926,7 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
 #if HG_PREFETCH
         if (cb + STEP < n) {   // the next step's gathers fly while this step is evaluated, and the entries of the step after it
 #pragma unroll
-            for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS>(W, en[u]);
+            for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS, XP>(W, en[u]);
 #pragma unroll
             for (int u = 0; u < HG_C; u++) en[u] = same_entry<RRBS>(W, cb + 2u * STEP + (uint32_t)(u * 64 + lane));
         }
@@ -2908,6 +2937,7 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
         uint4 p0, p1, p2, p3 = make_uint4(0u, 0u, 0u, 0u);
         { const uint4 *row = reinterpret_cast<const uint4 *>(uw); p0 = row[0]; p1 = row[1]; p2 = row[2]; if (nwr > 3) p3 = row[3]; }
 #endif
+        uint32_t dcur = 0;   // the offset class the frame stands at
         for (uint32_t k = 0; k < K; k++) {
             // (a 16-byte LDS read of a wave moves 1 KB, 8 cycles of the CU's LDS path: one read of the row per step, not per chunk)
 #if HG_ROWPF
@@ -2920,7 +2950,22 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
             if (nwr > 3) a3 = row[3];
 #endif
             const uint32_t tp = rfl(a2.y), thr = tp & 0xffffu;
-            const bool plain = NWR != 0 && (tp >> 16) != 0;
+            const bool plain = NWR != 0 && ((tp >> 16) & 1u) != 0;
+            if (XD) {
+                // the first row of the next offset class: the frame moves down a word (the candidates' reference 32 nt further on, at the same bit shift) and the
+                // positions follow; once per class and step, and the evaluation below is the one code for every class
+                for (; dcur < (tp >> 17); dcur++) {
+#pragma unroll
+                    for (int u = 0; u < HG_C; u++) {
+#pragma unroll
+                        for (int t = 0; t < 4; t++) { flo[u][t] = flo[u][t + 1]; fhi[u][t] = fhi[u][t + 1]; }
+                        flo[u][4] = xlo[u][0]; fhi[u][4] = xhi[u][0];
+#pragma unroll
+                        for (int t = 0; t + 1 < XD; t++) { xlo[u][t] = xlo[u][t + 1]; xhi[u][t] = xhi[u][t + 1]; }
+                        hloc[u] += 32u;
+                    }
+                }
+            }
             SurvRec *const sv = H.tout[rl_u(tid, k)].surv;   // (wave-uniform: the address arithmetic stays on the scalar unit)
             uint32_t nsk = rl_u(nsv, k), add15 = 0;
             if (full) {
@@ -2999,13 +3044,13 @@ __global__ __launch_bounds__(64 * HG_WPB, BSX_HSAME_WAVES) void k_hscan_same(Ali
         if (n0 == 0) {   // slots neutralised by a refused request: their units have not published a list
             if ((uint32_t)lane < K) { HTaskOut *o = &H.tout[tid]; o->count = 0; o->overflow = 0; o->acc[0] = o->acc[1] = o->acc[2] = o->acc[3] = 0; o->c0 = 0; o->n = 0; }
         } else if (f0 & 4u) {   // RRBS (hp_task takes WGBS lists only); reads of 65-96 nt have their own code
-            if (((f0 >> 8) & 15u) == 3u) hs_group<3, true, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), f0, rfl(tx), rfl(tw));
-            else hs_group<0, true, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), f0, rfl(tx), rfl(tw));
+            if (((f0 >> 8) & 15u) == 3u) hs_group<3, true, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), hh, f0, rfl(tx), rfl(tw));
+            else hs_group<0, true, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), hh, f0, rfl(tx), rfl(tw));
         }
         else if (K > 1) {   // (a lone task as a group of one instead of through hp_task: measured slower, C3 222.4-222.8 against 218.2-218.9 ms per step, gpurun_out/r06t)
-            if (((f0 >> 8) & 15u) == 5u) hs_group<5, false, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), f0, 0u, 0u);
-            else if (((f0 >> 8) & 15u) == 4u) hs_group<4, false, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), f0, 0u, 0u);   // 97-128 nt (C2: 100 nt single-end)
-            else hs_group<0, false, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), f0, 0u, 0u);
+            if (((f0 >> 8) & 15u) == 5u) hs_group<5, false, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), hh, f0, 0u, 0u);
+            else if (((f0 >> 8) & 15u) == 4u) hs_group<4, false, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), hh, f0, 0u, 0u);   // 97-128 nt (C2: 100 nt single-end)
+            else hs_group<0, false, STATS>(A, H, L, lane, wv, K, tid, th, tc0, rfl(key), n0, rfl(hh), hh, f0, 0u, 0u);
         }
         else hp_task<STATS>(A, H, rfl(tid), lane, L.W[wv].one.TAB, L.W[wv].one.PT, L.W[wv].one.Q);
         wave_fence();
@@ -3018,7 +3063,11 @@ __global__ __launch_bounds__(64 * HG_WPB, BSX_HSAME_WAVES) void k_hscan_same(Ali
 // that span sub-ranges are groups of one; neutralised slots (n = 0) form one group.  The start slots of the groups go into glist, a wave's
 // groups next to each other, the waves' parts in the order their atomic additions arrive — nearly the scan order, which is all the
 // scan kernel needs (neighbouring waves on the same cache lines); glist[cap], glist[cap + 1] count them (zeroed by k_bin_scan).
-__global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, uint32_t *order, uint32_t *ghead, uint32_t *glist)
+// D > 0 (WGBS tasks of 129-160 nt reads: the instantiation of hs_group that holds a longer frame): a group also takes the tasks whose read offset is that of its
+// first member plus 32 d, d <= D.  Of the pending tasks with the window and the offset's low five bits of the first pending one, the smallest offset (as a signed
+// number: h is minus the seed's place in the read) is the group's frame, and the members are written back sorted by d, so that slot 0 holds a task of the frame
+// itself.  Every turn removes at least the task of that smallest offset.  D = 0: the groups of equal offset, opened in the order of their first members.
+__global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, uint32_t *order, uint32_t *ghead, uint32_t *glist, uint32_t D)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t n_tasks = min(*n_tasks_ptr, cap);
@@ -3039,12 +3088,28 @@ __global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const u
             u64 mem = 1ull << i0;
             if (n0 == 0) mem = bsx_ballot(pending && tn == 0);
             else if (f0 & 2u) {
-                const bool same = pending && tn == n0 && key == key0 && hh == h0 && flags == f0 && tx == tx0 && tw == tw0;
-                mem = bsx_ballot(same);
-                if ((uint32_t)__builtin_popcountll(mem) > HG_R) mem = bsx_ballot(same && (uint32_t)__builtin_popcountll(mem & lanemask_lt(lane)) < HG_R);
+                const uint32_t Dg = (!(f0 & 4u) && ((f0 >> 8) & 15u) == 5u) ? D : 0u;
+                const bool win = pending && tn == n0 && key == key0 && flags == f0 && tx == tx0 && tw == tw0;
+                uint32_t hmin = h0;
+                if (Dg) {   // the smallest congruent offset still pending (compared with the sign bit turned: offsets are small signed numbers)
+                    uint32_t v = win && ((hh ^ h0) & 31u) == 0 ? hh ^ 0x80000000u : 0xffffffffu;
+#pragma unroll
+                    for (int o = 32; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor(v, o));
+                    hmin = v ^ 0x80000000u;
+                }
+                const uint32_t dh = hh - hmin;
+                mem = 0;
+                uint32_t Kg = 0;
+                for (uint32_t dd = 0; dd <= Dg && Kg < HG_R; dd++) {   // the members by offset class, at most HG_R in all
+                    const bool same = win && dh == 32u * dd;
+                    u64 md = bsx_ballot(same);
+                    if (Kg + (uint32_t)__builtin_popcountll(md) > HG_R) md = bsx_ballot(same && Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane)) < HG_R);
+                    if ((md >> lane) & 1) dst = off + Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane));
+                    mem |= md; Kg += (uint32_t)__builtin_popcountll(md);
+                }
             }
             const uint32_t K = (uint32_t)__builtin_popcountll(mem);
-            if ((mem >> lane) & 1) dst = off + (uint32_t)__builtin_popcountll(mem & lanemask_lt(lane));
+            if (!(n0 != 0 && (f0 & 2u)) && ((mem >> lane) & 1)) dst = off + (uint32_t)__builtin_popcountll(mem & lanemask_lt(lane));
             if ((uint32_t)lane == off) head = K;
             off += K; todo &= ~mem;
         }
@@ -3427,6 +3492,8 @@ void bsx_launch_hscan_same(const AlignArgs &A, const HeavyArgsRaw &R, hipStream_
     else hipLaunchKernelGGL(k_hscan_same<false>, dim3(blocks), dim3(64 * HG_WPB), 0, stream, A, H);
 }
 
+uint32_t bsx_same_d_max(void) { return HG_D; }
+
 void bsx_launch_hscan(const AlignArgs &A, const HeavyArgsRaw &R, hipStream_t stream, uint32_t max_tasks)
 {
     const HeavyArgs H = typed(R);
@@ -3460,7 +3527,9 @@ __device__ __forceinline__ uint32_t task_bin(const HTask &tk, uint32_t shift, ui
     if (spread && (tk.flags & 2u)) {
         const uint32_t span = tk.n >> shift;
         const uint32_t nb = span >= 16u ? 16u : span >= 8u ? 8u : span >= 4u ? 4u : span >= 2u ? 2u : 1u;
-        bin += ((tk.sub_h * 0x9E3779B1u) >> 28) & (nb - 1u);
+        // (spread 2, WGBS tasks of 129-160 nt reads: by the offset's low five bits — the offsets h + 32 d, which one group of k_hscan_same can hold, land in one bin)
+        const bool congruent = spread == 2u && !(tk.flags & 4u) && ((tk.flags >> 8) & 15u) == 5u;
+        bin += (((congruent ? tk.sub_h & 31u : tk.sub_h) * 0x9E3779B1u) >> 28) & (nb - 1u);
     }
     return min(bin, n_bins - 1u);
 }
@@ -3551,20 +3620,22 @@ uint32_t bsx_bin_chunks(uint32_t n_bins) { return (n_bins + BIN_CHUNK - 1) / BIN
 // bins: [n_bins] zero on entry and on exit; bstart: [n_bins]; chunk_tot: [bsx_bin_chunks(n_bins)] (<= 1024 chunks); rank, order: [task_cap];
 // zero_blk: the counter block to clear for the coming pass (or null)
 void bsx_launch_task_order(const HeavyArgsRaw &R, uint32_t shift, uint32_t n_bins, uint32_t *bins, uint32_t *bstart, uint32_t *chunk_tot, uint32_t *rank, uint32_t *order,
-                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread, bool groups)
+                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread, bool groups, uint32_t same_d)
 {
     const uint32_t grid = std::max(1u, std::min(512u, (R.task_cap + 255u) / 256u)), n_chunks = bsx_bin_chunks(n_bins);
     hipLaunchKernelGGL(k_task_bins, dim3(std::max(1u, std::min(256u, (R.task_cap + 1023u) / 1024u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, shift, n_bins, spread, bins, rank, zero_blk);
     hipLaunchKernelGGL(k_bin_scan, dim3(n_chunks), dim3(256), 0, stream, R.n_tasks, bins, bstart, chunk_tot, n_bins, groups ? R.glist + R.task_cap : (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_task_order, dim3(grid), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, shift, n_bins, spread, bstart, chunk_tot, n_chunks, rank, order);
     // (the ranks are spent: their array takes the group sizes)
-    if (groups) hipLaunchKernelGGL(k_task_groups, dim3(std::max(1u, std::min(1024u, (R.task_cap + 255u) / 256u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, order, rank, R.glist);
+    if (groups) hipLaunchKernelGGL(k_task_groups, dim3(std::max(1u, std::min(1024u, (R.task_cap + 255u) / 256u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, order, rank, R.glist, std::min<uint32_t>(same_d, HG_D));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Diagnostics (BSX_SIGHIST=1, bsx_api.hip): per pass, how many tasks cover exactly the same window (first entry, length, strand copy)
 // with the same read offset h — the tasks that could share one fetch AND one shift of the candidates' reference.  Candidates are
 // counted by the size R of their task's group: hist[k] for R in (2^(k-1), 2^k], hist[31] for tasks that span sub-ranges.
+// A third signature, for D = 1, 2, 4: same window and same low five bits of h, and h >> 5 within D of the smallest of that set — the tasks that one group of
+// k_hscan_same could hold with a frame D words longer (its first group, that is: the tasks further than D from the smallest are counted as hist[30], "beyond").
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 __device__ __forceinline__ unsigned long long sig_of(const HTask &tk, bool with_h)
@@ -3608,6 +3679,50 @@ __global__ __launch_bounds__(256) void k_sig_hist(const HTask *tasks, const uint
         atomicAdd(&hist[32 + k], 1ull);
     }
 }
+// the third signature.  Slot word 1: low half the largest ~(h >> 5) of the set (sign bit of h turned; k_sigc_min, while the high half is still zero), high half the
+// tasks within D of that smallest h >> 5 (k_sigc_count)
+__device__ __forceinline__ unsigned long long sigc_of(const HTask &tk)
+{
+    HTask t = tk; t.sub_h &= 31u;
+    return sig_of(t, true);
+}
+__device__ __forceinline__ uint32_t sigc_class(const HTask &tk) { return (tk.sub_h ^ 0x80000000u) >> 5; }
+__global__ __launch_bounds__(256) void k_sigc_min(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, unsigned long long *tab, uint32_t mask)
+{
+    const uint32_t n = min(*n_tasks_ptr, cap);
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const HTask tk = tasks[i];
+        if (!tk.n || !(tk.flags & 2u)) continue;
+        const unsigned long long sg = sigc_of(tk);
+        for (uint32_t slot = (uint32_t)(sg >> 20) & mask;; slot = (slot + 1) & mask) {
+            const unsigned long long prev = atomicCAS(&tab[2 * (size_t)slot], 0ull, sg);
+            if (prev == 0ull || prev == sg) { atomicMax(&tab[2 * (size_t)slot + 1], (unsigned long long)(0x0fffffffu - sigc_class(tk))); break; }
+        }
+    }
+}
+// pass 0 counts the tasks within D of their set's smallest class, pass 1 files every task under that count
+__global__ __launch_bounds__(256) void k_sigc_count(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, unsigned long long *tab, uint32_t mask, uint32_t D, int pass, unsigned long long *hist)
+{
+    const uint32_t n = min(*n_tasks_ptr, cap);
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const HTask tk = tasks[i];
+        if (!tk.n) continue;
+        uint32_t k = 31;
+        if (tk.flags & 2u) {
+            const unsigned long long sg = sigc_of(tk);
+            uint32_t slot = (uint32_t)(sg >> 20) & mask, probes = 0;   // (bounded probe: see k_sig_hist)
+            while (tab[2 * (size_t)slot] != sg && probes <= mask) { slot = (slot + 1) & mask; probes++; }
+            if (probes > mask) continue;
+            const unsigned long long w = tab[2 * (size_t)slot + 1];
+            const bool within = sigc_class(tk) - (0x0fffffffu - (uint32_t)(w & 0xffffffffull)) <= D;
+            if (!pass) { if (within) atomicAdd(&tab[2 * (size_t)slot + 1], 1ull << 32); continue; }
+            const uint32_t r = (uint32_t)(w >> 32);
+            k = !within ? 30u : r <= 1 ? 0u : 32u - (uint32_t)__builtin_clz(r - 1u);
+        }
+        if (pass) { atomicAdd(&hist[k], (unsigned long long)tk.n); atomicAdd(&hist[32 + k], 1ull); }
+    }
+}
+const int SIG_KINDS = 5;   // same window; and offset; and offset mod 32 within D = 1, 2, 4
 unsigned long long *g_sig_tab = nullptr, *g_sig_hist = nullptr;
 const uint32_t SIG_SLOTS = 1u << 23;
 }  // namespace
@@ -3615,30 +3730,39 @@ const uint32_t SIG_SLOTS = 1u << 23;
 void bsx_sig_hist_pass(const HeavyArgsRaw &R, hipStream_t stream)
 {
     if (!g_sig_tab) {
-        if (hipMalloc((void **)&g_sig_tab, (size_t)SIG_SLOTS * 16) != hipSuccess || hipMalloc((void **)&g_sig_hist, 2 * 64 * 8) != hipSuccess) { g_sig_tab = nullptr; return; }
-        (void)hipMemsetAsync(g_sig_hist, 0, 2 * 64 * 8, stream);
+        if (hipMalloc((void **)&g_sig_tab, (size_t)SIG_SLOTS * 16) != hipSuccess || hipMalloc((void **)&g_sig_hist, SIG_KINDS * 64 * 8) != hipSuccess) { g_sig_tab = nullptr; return; }
+        (void)hipMemsetAsync(g_sig_hist, 0, SIG_KINDS * 64 * 8, stream);
     }
     for (int with_h = 0; with_h < 2; with_h++) {
         (void)hipMemsetAsync(g_sig_tab, 0, (size_t)SIG_SLOTS * 16, stream);
         hipLaunchKernelGGL(k_sig_count, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, g_sig_tab, SIG_SLOTS - 1, with_h);
         hipLaunchKernelGGL(k_sig_hist, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, g_sig_tab, SIG_SLOTS - 1, with_h, g_sig_hist + 64 * with_h);
     }
+    for (int kind = 2; kind < SIG_KINDS; kind++) {
+        const uint32_t D = kind == 2 ? 1u : kind == 3 ? 2u : 4u;
+        (void)hipMemsetAsync(g_sig_tab, 0, (size_t)SIG_SLOTS * 16, stream);
+        hipLaunchKernelGGL(k_sigc_min, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, g_sig_tab, SIG_SLOTS - 1);
+        for (int pass = 0; pass < 2; pass++)
+            hipLaunchKernelGGL(k_sigc_count, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, g_sig_tab, SIG_SLOTS - 1, D, pass, g_sig_hist + 64 * kind);
+    }
 }
 
 void bsx_sig_hist_report(void)
 {
     if (!g_sig_tab) return;
-    unsigned long long h[128];
+    unsigned long long h[SIG_KINDS * 64];
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, g_sig_hist, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return;
-    for (int with_h = 0; with_h < 2; with_h++) {
+    static const char *const kind_name[SIG_KINDS] = {"", " and offset", " and offset mod 32, offset / 32 within 1 of the smallest", " and offset mod 32, offset / 32 within 2 of the smallest",
+                                                     " and offset mod 32, offset / 32 within 4 of the smallest"};
+    for (int with_h = 0; with_h < SIG_KINDS; with_h++) {
         unsigned long long tot = 0, tt = 0;
         for (int k = 0; k < 32; k++) { tot += h[64 * with_h + k]; tt += h[64 * with_h + 32 + k]; }
-        fprintf(stderr, "[sighist] same window%s: candidates %llu tasks %llu\n", with_h ? " and offset" : "", tot, tt);
+        fprintf(stderr, "[sighist] same window%s: candidates %llu tasks %llu\n", kind_name[with_h], tot, tt);
         for (int k = 0; k < 32; k++)
             if (h[64 * with_h + 32 + k])
-                fprintf(stderr, "[sighist]   %s %-6u cand %.4f tasks %.4f\n", k == 31 ? "spanning" : "R <=", k == 31 ? 0u : 1u << k, (double)h[64 * with_h + k] / (double)std::max(1ull, tot), (double)h[64 * with_h + 32 + k] / (double)std::max(1ull, tt));
+                fprintf(stderr, "[sighist]   %s %-6u cand %.4f tasks %.4f\n", k == 31 ? "spanning" : k == 30 && with_h >= 2 ? "beyond" : "R <=", k == 31 || (k == 30 && with_h >= 2) ? 0u : 1u << k, (double)h[64 * with_h + k] / (double)std::max(1ull, tot), (double)h[64 * with_h + 32 + k] / (double)std::max(1ull, tt));
     }
-    (void)hipMemset(g_sig_hist, 0, 2 * 64 * 8);
+    (void)hipMemset(g_sig_hist, 0, SIG_KINDS * 64 * 8);
 }
 
 // BSX_SECTOR_STATS (diagnostic build only; a no-op in the shipped library): count and clear the sectors the scan launch just marked

@@ -6,6 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// pairs of zero words behind each strand copy of the plane copy (bsx_planes_build): what a scan kernel's gather may reach beyond a candidate's first pair
+#define BSX_PLANE_PAD 16
+
 // 3-letter seed hash: per nt collapse code 3 (read nucleotide, 'T') onto code 1 ('C'), then read the 16 two-bit
 // digits as a base-3 number, first nt most significant.  The reference uses a 64K-entry table per 8 nt; on the GPU
 // the digits are folded pairwise in four multiply-adds, no table and no memory traffic.

@@ -102,8 +102,7 @@ template <class T> struct DevBuf {
 
 // Plane copy of the packed reference for the scan kernels of the heavy pipeline (k_hscan, k_hscan_shared): 2 bits per nt like
 // the packed copy (2 x 0.77 GB at hg38 size).  BSX_PLANE_PAD pairs behind each strand copy: a candidate's last gather reaches
-// six pairs from its first.
-#define BSX_PLANE_PAD 16
+// six pairs from its first, and k_hscan_same's HG_D more for a group that spans offset classes (BSX_PLANE_PAD: bsx_dev.h).
 int bsx_planes_build(bsx_ref *r)
 {
     const uint64_t n_pairs = (r->n_words + 1) / 2 + BSX_PLANE_PAD;
