@@ -2586,12 +2586,22 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 // members by d).  Such a read sees every candidate at the same bit shift, (entry + h - 1) & 31, and its reference frame is the same funnel-shifted word stream
 // read d words further on: the gather is HG_D pairs longer, the shift makes HG_D more words, and at the first row of the next d the frame moves down a word —
 // 10 register moves per chunk, once per class and step; nothing is done per read.  The positions a member is evaluated at are the ones its own group would use.
+// Round 9: a group holds up to HG_R = 64 tasks instead of 16 (a row of LDS and a lane per member, nothing else grows; BSX_SAME_R at run time), the groups of more than 32 tasks are started
+// first and an XCD turn is 128 groups: a wave with 64 reads runs four times as long as one with 16, and in plain order the launches ended on such waves.
 // ---------------------------------------------------------------------------------------------------------------
 #ifndef HG_WPB
 #define HG_WPB 1        /* waves (= groups) per block: 1 measured best (1: 96.0-98.9, 2: 101.7-102.2, 4: 110.9 ms per step) — a block gives its slot back when its LAST wave ends */
 #endif
 #ifndef HG_R
-#define HG_R 16u        /* tasks per group at most */
+#define HG_R 64u        /* tasks per group at most: 16, 32, 48 or 64 — a row of LDS and a lane of the wave per member, so 64 is the ceiling, and a group can then be a whole 64-slot segment of
+                           k_task_groups.  BSX_SAME_R (1 .. HG_R) at run time; 16 gives the groups and the task order of round 8 with this kernel (the baseline of an A/B is still the
+                           parent's library).  Round 9, C3 ms per step in plain scan order beside the parent's 206.40-207.11: 32: 204.49-205.14, mean group 19.5 reads; 48: 207.10-209.02, 23.8
+                           (a full segment splits into 48 + 16); 64: 199.34-205.54, 25.1 against the parent's 12.3, vector loads -22 %, 5 120 B of LDS per wave, registers unchanged.  What 64
+                           is worth depends on the order of the launch: HG_BIG, HG_XCD_DIV.  One cap for every length class: with 16 kept for all but the 129-160 nt reads C2 and C5 gained nothing.  As shipped 202.60-203.28 against 206.37-207.33; C2 and C5 ahead as well */
+#endif
+static_assert(HG_R == 16u || HG_R == 32u || HG_R == 48u || HG_R == 64u, "a lane per member: 64 at most, and whole quarters of a segment");
+#ifndef HG_XCD_DIV
+#define HG_XCD_DIV (HG_R > 16u ? 2u : 1u)   /* the XCD piece in groups (k_hscan_same): BSX_XCD_MAP x BSX_HSCAN_WPB / HG_WPB through round 8, half of that since groups hold up to 64 */
 #endif
 #ifndef HG_C
 #define HG_C 4          /* chunks per step.  Round 5 (without the work counters, 2^22 pairs per batch; scan ms per step / C3 M reads/s, one box): 2 chunks with the gathers a step
@@ -2600,8 +2610,11 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
                            the scalar bookkeeping) is spread over twice the candidates */
 #endif
 #ifndef HG_BIG
-#define HG_BIG 1u       /* groups of this many tasks and more are started first, the others fill the tail of the launch.  1 = plain scan order, measured best:
-                           from 4 tasks 103.5-104.2 against 99.4-100.3 ms per step, from 8 103.0 — the long groups of all windows at once lose the shared cache lines */
+#define HG_BIG (HG_R > 32u ? 33u : 1u)   /* groups of this many tasks and more are started first, the others fill the tail of the launch.  1 = plain scan order, measured best with groups
+                           of up to 16: from 4 tasks 103.5-104.2 against 99.4-100.3 ms per step, from 8 103.0 — the long groups of all windows at once lose the shared cache lines.  Round 9,
+                           groups of up to 64: a wave that holds 64 reads runs four times as long as one that held 16, and in plain order the launches end on such waves (resident waves per SIMD
+                           3.60 -> 3.37 in the counter pass, which gave back nearly all of the 7 % fewer wave cycles).  That the order gives the residency back is inferred: no counter pass of this order was taken.  The groups of more than 32 first, C3 ms per step on one box:
+                           203.01 / 203.02 / 203.13 against 204.68 / 204.83 / 204.98 in plain order and the parent's 206.15 / 206.62 / 206.73 */
 #endif
 #ifndef HG_PREFETCH
 #define HG_PREFETCH 0   /* 1: the gathers of a step are issued a step earlier (13 registers per chunk: only fits with two chunks per step) */
@@ -2633,6 +2646,8 @@ struct SameLds {
         struct { uint32_t TAB[4][32]; uint2 PT[HP_PAIRS * 32]; uint2 Q[HP_QCAP]; } one;   // one-task path (hp_task); 4 KB per wave: k_hctrl's blocks (58 KB paired) have to fit beside 20 waves of this kernel
     } W[HG_WPB];
 };
+// twenty waves of this kernel beside k_hctrl's blocks (58 KB paired) in the CU's 160 KB: 5 120 B per wave at HG_R = 64 (20 x 5 120 B + 58 KB = 158 KB); up to 48 rows fit the 4 KB of the other arm
+static_assert(20u * (sizeof(SameLds) / HG_WPB) + 58u * 1024u <= 160u * 1024u, "twenty waves of k_hscan_same beside k_hctrl's 58 KB have to fit the CU's LDS");
 struct SameChunk { U4 r0, r1, r2, r3; uint32_t pm1, strand; bool valid; };   // pairs (pm1 >> 5) .. + 5 (+ XP: r3) of the plane copy; RRBS: the candidate's strand copy, and whether the entry passed the filters
 // what a group's window is made of.  WGBS: 4-byte entries, candidate position = entry + h.  RRBS: one bucket of {tag | chromosome, position}
 // pairs — the entries with ((tag ^ tag_xor) >> 16) == tag_want and position >= h are the candidates (align.cpp:187,229,263), position =
@@ -3025,8 +3040,9 @@ __global__ __launch_bounds__(64 * HG_WPB, BSX_HSAME_WAVES) void k_hscan_same(Ali
     const uint32_t nvb = (n_groups + HG_WPB - 1) / HG_WPB;
     for (uint32_t vb = blockIdx.x;; vb += gridDim.x) {
         uint32_t b_;
-        // (pieces of 256 groups per XCD turn — about a thousand tasks, twice k_hscan's 512: 64 groups 97.7-98.5 ms per step, 256 96.0, 1024 97.1, 16 101.3, as dispatched 104.4)
-        const int st_ = bsx_order_block(vb, nvb, H.xcd_map >= 2 ? max(2u, H.xcd_map * BSX_HSCAN_WPB / HG_WPB) : H.xcd_map, b_);
+        // (pieces of 128 groups per XCD turn.  Through round 8, groups of up to 16: 256 groups, about a thousand tasks — 64 groups 97.7-98.5 ms per step, 256 96.0, 1024 97.1, 16 101.3,
+        //  as dispatched 104.4.  Round 9, groups of up to 64, mean 25 reads, C3 ms per step: 256 groups 200.9 / 204.3 / 205.5, 128 groups 200.9 / 202.5 / 203.3, 64 groups 203.9 / 205.0 / 207.0)
+        const int st_ = bsx_order_block(vb, nvb, H.xcd_map >= 2 ? max(2u, H.xcd_map * BSX_HSCAN_WPB / (HG_XCD_DIV * HG_WPB)) : H.xcd_map, b_);
         if (st_ == 2) break;
         if (st_ == 1) continue;
         const uint32_t g = b_ * HG_WPB + (uint32_t)wv;
@@ -3067,7 +3083,7 @@ __global__ __launch_bounds__(64 * HG_WPB, BSX_HSAME_WAVES) void k_hscan_same(Ali
 // first member plus 32 d, d <= D.  Of the pending tasks with the window and the offset's low five bits of the first pending one, the smallest offset (as a signed
 // number: h is minus the seed's place in the read) is the group's frame, and the members are written back sorted by d, so that slot 0 holds a task of the frame
 // itself.  Every turn removes at least the task of that smallest offset.  D = 0: the groups of equal offset, opened in the order of their first members.
-__global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, uint32_t *order, uint32_t *ghead, uint32_t *glist, uint32_t D)
+__global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, uint32_t *order, uint32_t *ghead, uint32_t *glist, uint32_t D, uint32_t Rg)
 {
     const int lane = threadIdx.x & 63;
     const uint32_t n_tasks = min(*n_tasks_ptr, cap);
@@ -3100,10 +3116,10 @@ __global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const u
                 const uint32_t dh = hh - hmin;
                 mem = 0;
                 uint32_t Kg = 0;
-                for (uint32_t dd = 0; dd <= Dg && Kg < HG_R; dd++) {   // the members by offset class, at most HG_R in all
+                for (uint32_t dd = 0; dd <= Dg && Kg < Rg; dd++) {   // the members by offset class, at most Rg in all
                     const bool same = win && dh == 32u * dd;
                     u64 md = bsx_ballot(same);
-                    if (Kg + (uint32_t)__builtin_popcountll(md) > HG_R) md = bsx_ballot(same && Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane)) < HG_R);
+                    if (Kg + (uint32_t)__builtin_popcountll(md) > Rg) md = bsx_ballot(same && Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane)) < Rg);
                     if ((md >> lane) & 1) dst = off + Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane));
                     mem |= md; Kg += (uint32_t)__builtin_popcountll(md);
                 }
@@ -3493,6 +3509,7 @@ void bsx_launch_hscan_same(const AlignArgs &A, const HeavyArgsRaw &R, hipStream_
 }
 
 uint32_t bsx_same_d_max(void) { return HG_D; }
+uint32_t bsx_same_r_max(void) { return HG_R; }
 
 void bsx_launch_hscan(const AlignArgs &A, const HeavyArgsRaw &R, hipStream_t stream, uint32_t max_tasks)
 {
@@ -3620,14 +3637,14 @@ uint32_t bsx_bin_chunks(uint32_t n_bins) { return (n_bins + BIN_CHUNK - 1) / BIN
 // bins: [n_bins] zero on entry and on exit; bstart: [n_bins]; chunk_tot: [bsx_bin_chunks(n_bins)] (<= 1024 chunks); rank, order: [task_cap];
 // zero_blk: the counter block to clear for the coming pass (or null)
 void bsx_launch_task_order(const HeavyArgsRaw &R, uint32_t shift, uint32_t n_bins, uint32_t *bins, uint32_t *bstart, uint32_t *chunk_tot, uint32_t *rank, uint32_t *order,
-                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread, bool groups, uint32_t same_d)
+                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread, bool groups, uint32_t same_d, uint32_t same_r)
 {
     const uint32_t grid = std::max(1u, std::min(512u, (R.task_cap + 255u) / 256u)), n_chunks = bsx_bin_chunks(n_bins);
     hipLaunchKernelGGL(k_task_bins, dim3(std::max(1u, std::min(256u, (R.task_cap + 1023u) / 1024u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, shift, n_bins, spread, bins, rank, zero_blk);
     hipLaunchKernelGGL(k_bin_scan, dim3(n_chunks), dim3(256), 0, stream, R.n_tasks, bins, bstart, chunk_tot, n_bins, groups ? R.glist + R.task_cap : (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_task_order, dim3(grid), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, shift, n_bins, spread, bstart, chunk_tot, n_chunks, rank, order);
     // (the ranks are spent: their array takes the group sizes)
-    if (groups) hipLaunchKernelGGL(k_task_groups, dim3(std::max(1u, std::min(1024u, (R.task_cap + 255u) / 256u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, order, rank, R.glist, std::min<uint32_t>(same_d, HG_D));
+    if (groups) hipLaunchKernelGGL(k_task_groups, dim3(std::max(1u, std::min(1024u, (R.task_cap + 255u) / 256u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, order, rank, R.glist, std::min<uint32_t>(same_d, HG_D), same_r ? std::min<uint32_t>(same_r, HG_R) : HG_R);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -296,6 +296,7 @@ struct bsx_batch {
     bool sig_hist = false;    // diagnostics: histogram of tasks per identical window (bsx_sig_hist_pass)
     bool same_kernel = false;    // the scan kernel is k_hscan_same (WGBS unless BSX_SAME=0, RRBS with BSX_SAME=2): read once, at creation
     uint32_t same_d = 0;         // ... and its groups span this many offset classes beyond their first (BSX_SAME_D, 0 .. the build's HG_D, which is the default): read with it
+    uint32_t same_r = 0;         // ... and hold this many tasks at most (BSX_SAME_R, 1 .. the build's HG_R, which is the default; 0 until the batch is created: the build's HG_R)
     bool sector_stats = false;   // diagnostics (a build with -DBSX_SECTOR_STATS): distinct sectors per scan launch
     uint32_t xcd_map = 128;   // order_block (bsx_align.hip): pieces of 128 scan blocks dealt to the XCDs in turn
     uint32_t *h_pinned = nullptr;  // pinned host words for the per-pass count read-backs
@@ -513,6 +514,7 @@ static int ensure_scratch(bsx_batch *b)
         const int same_env0 = getenv("BSX_SAME") ? atoi(getenv("BSX_SAME")) : 1;
         const bool same_kernel = b->same_kernel = b->ref->P.rrbs ? same_env0 == 2 : same_env0 != 0;
         b->same_d = getenv("BSX_SAME_D") ? (uint32_t)std::min<long>(std::max<long>(0, atol(getenv("BSX_SAME_D"))), (long)bsx_same_d_max()) : bsx_same_d_max();
+        b->same_r = getenv("BSX_SAME_R") ? (uint32_t)std::min<long>(std::max<long>(1, atol(getenv("BSX_SAME_R"))), (long)bsx_same_r_max()) : bsx_same_r_max();
         auto alloc_pools = [&]() -> hipError_t {
             hipError_t e;
 #define POOL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
@@ -959,7 +961,7 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
                 if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 1], hw.s_ctrl));
                 // scan order of the tasks this pass published, still on the group's stream: done by the time the main stream gets to the scan
                 q.H.order = hw.d_order; q.H.xcd_map = b->xcd_map; q.H.ghead = hw.d_rank; q.H.glist = hw.d_glist;
-                bsx_launch_task_order(q.H, b->bin_shift, b->n_bins, hw.d_bins, hw.d_bstart, hw.d_chunk_tot, hw.d_rank, hw.d_order, in, hw.s_ctrl, spread, same_scan, b->same_d);
+                bsx_launch_task_order(q.H, b->bin_shift, b->n_bins, hw.d_bins, hw.d_bstart, hw.d_chunk_tot, hw.d_rank, hw.d_order, in, hw.s_ctrl, spread, same_scan, b->same_d, b->same_r);
                 // The scan: on the batch's stream with a grid for the whole task pool — or, once the group is in its tail (few tasks per
                 // pass, see the poll loop), behind the control kernel on the group's own high-priority stream with a small grid whose
                 // blocks sweep: beside ANOTHER batch's bulk scans a pool-sized grid of mostly empty blocks only trickles through the
