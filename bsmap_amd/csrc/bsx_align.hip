@@ -24,6 +24,7 @@
 // slab (they are usually 1-2 entries but may legally reach 1000 per class).
 #include "bsx_internal.h"
 #include "bsx_dev.h"
+#include "bsx_groups.h"
 #include "bsx_kernel_args.h"
 
 namespace {
@@ -2588,18 +2589,20 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 // 10 register moves per chunk, once per class and step; nothing is done per read.  The positions a member is evaluated at are the ones its own group would use.
 // Round 9: a group holds up to HG_R = 64 tasks instead of 16 (a row of LDS and a lane per member, nothing else grows; BSX_SAME_R at run time), the groups of more than 32 tasks are started
 // first and an XCD turn is 128 groups: a wave with 64 reads runs four times as long as one with 16, and in plain order the launches ended on such waves.
+// Round 10: the groups are formed over whole runs of a window inside tiles of 1 024 slots of the scan order and cut into near-equal sizes (k_task_groups, bsx_groups.h); this kernel is unchanged.  A fetch
+// serves 13.7 reads instead of 10.0, C3 203.4 -> 194.5 ms per step.
 // ---------------------------------------------------------------------------------------------------------------
 #ifndef HG_WPB
 #define HG_WPB 1        /* waves (= groups) per block: 1 measured best (1: 96.0-98.9, 2: 101.7-102.2, 4: 110.9 ms per step) — a block gives its slot back when its LAST wave ends */
 #endif
 #ifndef HG_R
-#define HG_R 64u        /* tasks per group at most: 16, 32, 48 or 64 — a row of LDS and a lane of the wave per member, so 64 is the ceiling, and a group can then be a whole 64-slot segment of
-                           k_task_groups.  BSX_SAME_R (1 .. HG_R) at run time; 16 gives the groups and the task order of round 8 with this kernel (the baseline of an A/B is still the
+#define HG_R 64u        /* tasks per group at most: 16, 32, 48 or 64 — a row of LDS and a lane of the wave per member, so 64 is the ceiling (through round 9 a whole 64-slot segment of
+                           k_task_groups; since round 10 the groups are cut from whole runs of a tile, see k_task_groups).  BSX_SAME_R (1 .. HG_R) at run time; 16 gives the groups and the task order of round 8 with this kernel (the baseline of an A/B is still the
                            parent's library).  Round 9, C3 ms per step in plain scan order beside the parent's 206.40-207.11: 32: 204.49-205.14, mean group 19.5 reads; 48: 207.10-209.02, 23.8
                            (a full segment splits into 48 + 16); 64: 199.34-205.54, 25.1 against the parent's 12.3, vector loads -22 %, 5 120 B of LDS per wave, registers unchanged.  What 64
                            is worth depends on the order of the launch: HG_BIG, HG_XCD_DIV.  One cap for every length class: with 16 kept for all but the 129-160 nt reads C2 and C5 gained nothing.  As shipped 202.60-203.28 against 206.37-207.33; C2 and C5 ahead as well */
 #endif
-static_assert(HG_R == 16u || HG_R == 32u || HG_R == 48u || HG_R == 64u, "a lane per member: 64 at most, and whole quarters of a segment");
+static_assert(HG_R == 16u || HG_R == 32u || HG_R == 48u || HG_R == 64u, "a lane per member: 64 at most");
 #ifndef HG_XCD_DIV
 #define HG_XCD_DIV (HG_R > 16u ? 2u : 1u)   /* the XCD piece in groups (k_hscan_same): BSX_XCD_MAP x BSX_HSCAN_WPB / HG_WPB through round 8, half of that since groups hold up to 64 */
 #endif
@@ -2614,7 +2617,8 @@ static_assert(HG_R == 16u || HG_R == 32u || HG_R == 48u || HG_R == 64u, "a lane 
                            of up to 16: from 4 tasks 103.5-104.2 against 99.4-100.3 ms per step, from 8 103.0 — the long groups of all windows at once lose the shared cache lines.  Round 9,
                            groups of up to 64: a wave that holds 64 reads runs four times as long as one that held 16, and in plain order the launches end on such waves (resident waves per SIMD
                            3.60 -> 3.37 in the counter pass, which gave back nearly all of the 7 % fewer wave cycles).  That the order gives the residency back is inferred: no counter pass of this order was taken.  The groups of more than 32 first, C3 ms per step on one box:
-                           203.01 / 203.02 / 203.13 against 204.68 / 204.83 / 204.98 in plain order and the parent's 206.15 / 206.62 / 206.73 */
+                           203.01 / 203.02 / 203.13 against 204.68 / 204.83 / 204.98 in plain order and the parent's 206.15 / 206.62 / 206.73.  Round 10, groups from whole runs (mean 38 reads; BSX_GROUP_BIG at run time),
+                           one box, alternating: from 17: 192.30 / 192.99 / 194.83; from 33: 190.19 / 191.86 / 197.30; from 49: 192.69 / 192.79 / 192.97 (C2 and C5 level with 33) — no median outside the others' spread, 33 stays */
 #endif
 #ifndef HG_PREFETCH
 #define HG_PREFETCH 0   /* 1: the gathers of a step are issued a step earlier (13 registers per chunk: only fits with two chunks per step) */
@@ -3073,71 +3077,130 @@ __global__ __launch_bounds__(64 * HG_WPB, BSX_HSAME_WAVES) void k_hscan_same(Ali
     }
 }
 
-// The groups of a pass: a wave takes 64 consecutive slots of the scan order, splits their tasks into groups of up to HG_R with equal
-// (first entry, length, strand copy, read offset, read words) — any of the 64, not only neighbours —, writes the slots back with
-// the members of each group next to each other, in the order the groups were opened, and the group sizes into ghead.  Tasks
-// that span sub-ranges are groups of one; neutralised slots (n = 0) form one group.  The start slots of the groups go into glist, a wave's
-// groups next to each other, the waves' parts in the order their atomic additions arrive — nearly the scan order, which is all the
-// scan kernel needs (neighbouring waves on the same cache lines); glist[cap], glist[cap + 1] count them (zeroed by k_bin_scan).
-// D > 0 (WGBS tasks of 129-160 nt reads: the instantiation of hs_group that holds a longer frame): a group also takes the tasks whose read offset is that of its
-// first member plus 32 d, d <= D.  Of the pending tasks with the window and the offset's low five bits of the first pending one, the smallest offset (as a signed
-// number: h is minus the seed's place in the read) is the group's frame, and the members are written back sorted by d, so that slot 0 holds a task of the frame
-// itself.  Every turn removes at least the task of that smallest offset.  D = 0: the groups of equal offset, opened in the order of their first members.
-__global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, uint32_t *order, uint32_t *ghead, uint32_t *glist, uint32_t D, uint32_t Rg)
+// The groups of a pass: a block takes a tile of consecutive slots of the scan order (HG_TILE, BSX_GROUP_TILE at run time), sorts its tasks in LDS by window (first
+// entry, then a hash of length, flags and tag filter), by the low five bits of the read offset, by the offset as a signed number (h is minus the seed's place in
+// the read) and by task id, and cuts every run of one window and one congruence class into groups with bsx_group_cut (bsx_groups.h): the frame of a group is the
+// smallest offset still pending, its members the next tasks of the sorted run with offset - frame in {0, 32, .., 32 D} (D > 0 for WGBS tasks of 129-160 nt reads
+// only: the instantiation of hs_group that holds a longer frame; D = 0: groups of equal offset), at most Rg, in near-equal sizes.  The hash only sorts: where a
+// run begins is decided on the full fields, so a collision can split a group and never merge two.  The slots of the tile are written back in sorted order — the
+// members of a group next to each other, sorted by d, a task of the frame itself in slot 0 — with the group sizes in ghead.  Tasks that span sub-ranges are groups
+// of one; the neutralised slots (n = 0) of a tile form one group (of up to 64: a lane per member).  Through round 9 a wave grouped 64 consecutive slots: the classes
+// of a window lie interleaved in its bins in the order of arrival, a segment held pieces of about eight groups, and a fetch served 10 reads where the sets allow 14.5.
+// The start slots of the groups go into glist, a tile's groups next to each other in slot order, the tiles' parts in the order their atomic additions arrive —
+// nearly the scan order, which is all the scan kernel needs (neighbouring waves on the same cache lines); groups of `big` tasks and more from the front, the
+// others from the back (they cannot meet: a slot starts at most one group); glist[cap], glist[cap + 1] count them (zeroed by k_bin_scan).
+#ifndef HG_TILE
+#define HG_TILE 1024u   /* slots per tile: a power of two, 64 .. HG_TILE_MAX (BSX_GROUP_TILE at run time; 64 with BSX_SAME_R=16 is nearest to the groups before round 10).  C3 ms per step on one box,
+                           alternating: 512: 192.53 / 192.53 / 195.26; 1 024: 190.19 / 191.86 / 197.30; 2 048: 190.61 / 192.71 / 194.52 — no difference outside the spread; the parent's segments of 64: 203.05 / 203.38 / 203.39
+                           on the box before */
+#endif
+#define HG_TILE_MAX 2048u
+static_assert(HG_TILE >= 64u && HG_TILE <= HG_TILE_MAX && (HG_TILE & (HG_TILE - 1u)) == 0, "a power of two of whole waves");
+__device__ __forceinline__ bool tg_less(const uint4 &a, const uint4 &b)
 {
+    if (a.x != b.x) return a.x < b.x;
+    if (a.y != b.y) return a.y < b.y;
+    if (a.z != b.z) return a.z < b.z;
+    return a.w < b.w;
+}
+// tasks of one run: one window (all fields), inside one sub-range, offsets congruent mod 32 — or both neutralised
+__device__ __forceinline__ bool tg_same_run(const HTask &a, const HTask &b)
+{
+    if (a.n == 0 || b.n == 0) return a.n == b.n;
+    return (a.flags & 2u) && a.flags == b.flags && a.key == b.key && a.n == b.n && a.pad[0] == b.pad[0] && a.pad[1] == b.pad[1] && ((a.sub_h ^ b.sub_h) & 31u) == 0;
+}
+__global__ __launch_bounds__(256) void k_task_groups(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, uint32_t *order, uint32_t *ghead, uint32_t *glist, uint32_t D, uint32_t Rg,
+                                                     uint32_t T, uint32_t big)
+{
+    extern __shared__ uint4 tg_lds[];
+    uint4 *K = tg_lds;                                   // [T] sort keys: window, hash | class, offset (sign bit turned), task id
+    uint32_t *head = (uint32_t *)(K + T);                // [T] group sizes by sorted slot
+    u64 *brk = (u64 *)(head + T);                        // [32] the slots at which a run begins, a bit each
+    uint32_t *cnt = (uint32_t *)(brk + HG_TILE_MAX / 64u);   // [2][32] groups per 64 slots, big and small; then their places in glist
     const int lane = threadIdx.x & 63;
+    const uint32_t wv = threadIdx.x >> 6, n_ch = T >> 6;
     const uint32_t n_tasks = min(*n_tasks_ptr, cap);
-    for (uint32_t s0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; s0 < n_tasks; s0 += gridDim.x * 256u) {
-        const uint32_t nj = min(64u, n_tasks - s0);
-        uint32_t tid = 0, tn = 0, key = 0, hh = 0, flags = 0, tx = 0, tw = 0;
-        if ((uint32_t)lane < nj) {
-            tid = order[s0 + lane];
-            const HTask tk = tasks[tid];
-            tn = tk.n; key = tk.key; hh = tk.sub_h; flags = tk.flags; tx = tk.pad[0]; tw = tk.pad[1];   // (pad: the tag filter of an RRBS list, 0 otherwise)
-        }
-        u64 todo = bsx_ballot((uint32_t)lane < nj);
-        uint32_t off = 0, head = 0, dst = 0;
-        while (todo) {
-            const uint32_t i0 = (uint32_t)__builtin_ctzll(todo);
-            const uint32_t n0 = rl_u(tn, i0), f0 = rl_u(flags, i0), key0 = rl_u(key, i0), h0 = rl_u(hh, i0), tx0 = rl_u(tx, i0), tw0 = rl_u(tw, i0);
-            const bool pending = (todo >> lane) & 1;
-            u64 mem = 1ull << i0;
-            if (n0 == 0) mem = bsx_ballot(pending && tn == 0);
-            else if (f0 & 2u) {
-                const uint32_t Dg = (!(f0 & 4u) && ((f0 >> 8) & 15u) == 5u) ? D : 0u;
-                const bool win = pending && tn == n0 && key == key0 && flags == f0 && tx == tx0 && tw == tw0;
-                uint32_t hmin = h0;
-                if (Dg) {   // the smallest congruent offset still pending (compared with the sign bit turned: offsets are small signed numbers)
-                    uint32_t v = win && ((hh ^ h0) & 31u) == 0 ? hh ^ 0x80000000u : 0xffffffffu;
-#pragma unroll
-                    for (int o = 32; o; o >>= 1) v = min(v, (uint32_t)__shfl_xor(v, o));
-                    hmin = v ^ 0x80000000u;
-                }
-                const uint32_t dh = hh - hmin;
-                mem = 0;
-                uint32_t Kg = 0;
-                for (uint32_t dd = 0; dd <= Dg && Kg < Rg; dd++) {   // the members by offset class, at most Rg in all
-                    const bool same = win && dh == 32u * dd;
-                    u64 md = bsx_ballot(same);
-                    if (Kg + (uint32_t)__builtin_popcountll(md) > Rg) md = bsx_ballot(same && Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane)) < Rg);
-                    if ((md >> lane) & 1) dst = off + Kg + (uint32_t)__builtin_popcountll(md & lanemask_lt(lane));
-                    mem |= md; Kg += (uint32_t)__builtin_popcountll(md);
+    for (uint32_t s0 = blockIdx.x * T; s0 < n_tasks; s0 += gridDim.x * T) {
+        const uint32_t nj = min(T, n_tasks - s0);
+        for (uint32_t i = threadIdx.x; i < T; i += 256u) {
+            uint4 k = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);   // (beyond the tile's tasks: behind everything)
+            if (i < nj) {
+                const uint32_t tid = order[s0 + i];
+                const HTask tk = tasks[tid];
+                if (tk.n == 0) k = make_uint4(0xffffffffu, 0xfffffffeu, 0u, tid);
+                else {
+                    uint32_t hs = tk.n * 0x9E3779B1u ^ tk.flags * 0x85EBCA6Bu ^ tk.pad[0] * 0xC2B2AE35u ^ tk.pad[1] * 0x27D4EB2Fu;   // (pad: the tag filter of an RRBS list, 0 otherwise)
+                    hs ^= hs >> 15; hs *= 0x2C1B3C6Du; hs ^= hs >> 13;
+                    k = make_uint4(tk.key, (hs & ~31u) | (tk.sub_h & 31u), tk.sub_h ^ 0x80000000u, tid);
                 }
             }
-            const uint32_t K = (uint32_t)__builtin_popcountll(mem);
-            if (!(n0 != 0 && (f0 & 2u)) && ((mem >> lane) & 1)) dst = off + (uint32_t)__builtin_popcountll(mem & lanemask_lt(lane));
-            if ((uint32_t)lane == off) head = K;
-            off += K; todo &= ~mem;
+            K[i] = k;
         }
-        if ((uint32_t)lane < nj) { order[s0 + dst] = tid; ghead[s0 + lane] = head; }
-        // groups of HG_BIG tasks and more from the front of glist, the others from its back (they cannot meet: a slot starts at most one group)
-        const u64 hb = bsx_ballot(head >= HG_BIG), hs = bsx_ballot(head != 0 && head < HG_BIG);
-        uint32_t base = 0;
-        if (lane == 0 && hb) base = atomicAdd(&glist[cap], (uint32_t)__builtin_popcountll(hb));
-        if (lane == 1 && hs) base = atomicAdd(&glist[cap + 1], (uint32_t)__builtin_popcountll(hs));
-        const uint32_t base_b = rl_u(base, 0), base_s = rl_u(base, 1);
-        if (head >= HG_BIG) glist[base_b + (uint32_t)__builtin_popcountll(hb & lanemask_lt(lane))] = s0 + (uint32_t)lane;
-        else if (head != 0) glist[cap - 1u - (base_s + (uint32_t)__builtin_popcountll(hs & lanemask_lt(lane)))] = s0 + (uint32_t)lane;
+        __syncthreads();
+        for (uint32_t kk = 2; kk <= T; kk <<= 1)   // bitonic sort, ascending
+            for (uint32_t j = kk >> 1; j; j >>= 1) {
+                for (uint32_t t = threadIdx.x; t < (T >> 1); t += 256u) {
+                    const uint32_t i = 2u * t - (t & (j - 1u)), l = i + j;
+                    const uint4 a = K[i], b = K[l];
+                    if (tg_less(b, a) == ((i & kk) == 0)) { K[i] = b; K[l] = a; }
+                }
+                __syncthreads();
+            }
+        // where runs begin, and what a run's groups may hold: info = 1 | D << 1 | Rg << 8 at a run's first slot, 0 elsewhere
+        uint32_t info[HG_TILE_MAX / 256u];
+#pragma unroll
+        for (uint32_t m = 0; m < HG_TILE_MAX / 256u; m++) {
+            const uint32_t c = wv + 4u * m, i = c * 64u + (uint32_t)lane;   // (a wave takes whole pieces of 64 slots: the ballot below)
+            info[m] = 0;
+            if (c >= n_ch) continue;
+            bool start = false;
+            if (i < nj) {
+                const uint4 k = K[i];
+                const HTask tk = tasks[k.w];
+                start = true;
+                if (i) {
+                    const uint4 kp = K[i - 1u];
+                    if (kp.x == k.x && kp.y == k.y) start = !tg_same_run(tasks[kp.w], tk);
+                }
+                const uint32_t Dg = (!(tk.flags & 4u) && ((tk.flags >> 8) & 15u) == 5u) ? D : 0u;
+                if (start) info[m] = 1u | (tk.n == 0 ? 64u << 8 : !(tk.flags & 2u) ? 1u << 8 : Dg << 1 | Rg << 8);
+            }
+            const u64 bm = bsx_ballot(start);
+            if (lane == 0) brk[c] = bm;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t m = 0; m < HG_TILE_MAX / 256u; m++) {
+            if (!info[m]) continue;
+            const uint32_t i = (wv + 4u * m) * 64u + (uint32_t)lane;
+            uint32_t c = i >> 6;
+            u64 w = brk[c] & ~((2ull << (i & 63u)) - 1ull);   // the next run's first slot
+            while (!w && ++c < n_ch) w = brk[c];
+            const uint32_t e = w ? c * 64u + (uint32_t)__builtin_ctzll(w) : nj;
+            bsx_group_cut(&K[i].z, 4u, e - i, (info[m] >> 1) & 127u, info[m] >> 8, head + i, 1u);   // (at most e - i turns: bsx_groups.h)
+        }
+        __syncthreads();
+        for (uint32_t c = wv; c < n_ch; c += 4u) {
+            const uint32_t i = c * 64u + (uint32_t)lane, hd = i < nj ? head[i] : 0u;
+            if (i < nj) { order[s0 + i] = K[i].w; ghead[s0 + i] = hd; }
+            const u64 hb = bsx_ballot(hd >= big), hsm = bsx_ballot(hd != 0 && hd < big);
+            if (lane == 0) { cnt[c] = (uint32_t)__builtin_popcountll(hb); cnt[32u + c] = (uint32_t)__builtin_popcountll(hsm); }
+        }
+        __syncthreads();
+        if (threadIdx.x < 2u) {   // thread 0: the big groups' places, thread 1: the small ones'
+            uint32_t *q = cnt + 32u * threadIdx.x, tot = 0;
+            for (uint32_t c = 0; c < n_ch; c++) tot += q[c];
+            uint32_t run = tot ? atomicAdd(&glist[cap + threadIdx.x], tot) : 0u;
+            for (uint32_t c = 0; c < n_ch; c++) { const uint32_t v = q[c]; q[c] = run; run += v; }
+        }
+        __syncthreads();
+        for (uint32_t c = wv; c < n_ch; c += 4u) {
+            const uint32_t i = c * 64u + (uint32_t)lane, hd = i < nj ? head[i] : 0u;
+            const u64 hb = bsx_ballot(hd >= big), hsm = bsx_ballot(hd != 0 && hd < big);
+            if (hd >= big) glist[cnt[c] + (uint32_t)__builtin_popcountll(hb & lanemask_lt(lane))] = s0 + i;
+            else if (hd != 0) glist[cap - 1u - (cnt[32u + c] + (uint32_t)__builtin_popcountll(hsm & lanemask_lt(lane)))] = s0 + i;
+        }
+        __syncthreads();
     }
 }
 
@@ -3546,6 +3609,8 @@ __device__ __forceinline__ uint32_t task_bin(const HTask &tk, uint32_t shift, ui
         const uint32_t nb = span >= 16u ? 16u : span >= 8u ? 8u : span >= 4u ? 4u : span >= 2u ? 2u : 1u;
         // (spread 2, WGBS tasks of 129-160 nt reads: by the offset's low five bits — the offsets h + 32 d, which one group of k_hscan_same can hold, land in one bin)
         const bool congruent = spread == 2u && !(tk.flags & 4u) && ((tk.flags >> 8) & 15u) == 5u;
+        // (round 10: the 32 classes dealt evenly, class c to bin c nb / 32, instead of by this hash, which leaves a window's bins uneven: C3 190.60 / 191.33 / 193.71 against 190.19 / 191.86 / 197.30 ms
+        //  per step with the hash on one box — inside the spread since k_task_groups sorts whole tiles, not kept)
         bin += (((congruent ? tk.sub_h & 31u : tk.sub_h) * 0x9E3779B1u) >> 28) & (nb - 1u);
     }
     return min(bin, n_bins - 1u);
@@ -3632,19 +3697,31 @@ __global__ __launch_bounds__(256) void k_task_order(const HTask *tasks, const ui
 }
 }  // namespace
 
+// the tile of k_task_groups: a power of two, 64 .. HG_TILE_MAX (0: the build's HG_TILE)
+uint32_t bsx_group_tile(uint32_t tile)
+{
+    uint32_t T = 64u;
+    while (T < HG_TILE_MAX && T < (tile ? tile : HG_TILE)) T <<= 1;
+    return T;
+}
 uint32_t bsx_bin_chunks(uint32_t n_bins) { return (n_bins + BIN_CHUNK - 1) / BIN_CHUNK; }
 
 // bins: [n_bins] zero on entry and on exit; bstart: [n_bins]; chunk_tot: [bsx_bin_chunks(n_bins)] (<= 1024 chunks); rank, order: [task_cap];
 // zero_blk: the counter block to clear for the coming pass (or null)
 void bsx_launch_task_order(const HeavyArgsRaw &R, uint32_t shift, uint32_t n_bins, uint32_t *bins, uint32_t *bstart, uint32_t *chunk_tot, uint32_t *rank, uint32_t *order,
-                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread, bool groups, uint32_t same_d, uint32_t same_r)
+                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread, bool groups, uint32_t same_d, uint32_t same_r, uint32_t tile, uint32_t big)
 {
     const uint32_t grid = std::max(1u, std::min(512u, (R.task_cap + 255u) / 256u)), n_chunks = bsx_bin_chunks(n_bins);
     hipLaunchKernelGGL(k_task_bins, dim3(std::max(1u, std::min(256u, (R.task_cap + 1023u) / 1024u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, shift, n_bins, spread, bins, rank, zero_blk);
     hipLaunchKernelGGL(k_bin_scan, dim3(n_chunks), dim3(256), 0, stream, R.n_tasks, bins, bstart, chunk_tot, n_bins, groups ? R.glist + R.task_cap : (uint32_t *)nullptr);
     hipLaunchKernelGGL(k_task_order, dim3(grid), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, shift, n_bins, spread, bstart, chunk_tot, n_chunks, rank, order);
     // (the ranks are spent: their array takes the group sizes)
-    if (groups) hipLaunchKernelGGL(k_task_groups, dim3(std::max(1u, std::min(1024u, (R.task_cap + 255u) / 256u))), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, order, rank, R.glist, std::min<uint32_t>(same_d, HG_D), same_r ? std::min<uint32_t>(same_r, HG_R) : HG_R);
+    if (groups) {
+        const uint32_t T = bsx_group_tile(tile);
+        const size_t lds = (size_t)T * 20u + HG_TILE_MAX / 64u * 8u + 64u * 4u;   // keys, group sizes, run bits, counts (k_task_groups)
+        hipLaunchKernelGGL(k_task_groups, dim3(std::max(1u, std::min(1024u, (R.task_cap + T - 1u) / T))), dim3(256), lds, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, order, rank, R.glist,
+                           std::min<uint32_t>(same_d, HG_D), same_r ? std::min<uint32_t>(same_r, HG_R) : HG_R, T, big ? std::min<uint32_t>(big, HG_R + 1u) : HG_BIG);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -3739,16 +3816,52 @@ __global__ __launch_bounds__(256) void k_sigc_count(const HTask *tasks, const ui
         if (pass) { atomicAdd(&hist[k], (unsigned long long)tk.n); atomicAdd(&hist[32 + k], 1ull); }
     }
 }
-const int SIG_KINDS = 5;   // same window; and offset; and offset mod 32 within D = 1, 2, 4
+// What the groups of a pass are worth (behind k_task_groups).  st[0]: (read, candidate) evaluations, st[1]: 64-candidate chunks of groups — one fetch and shift of
+// the candidates' reference each: st[0] / (64 st[1]) reads share a fetch, the harmonic figure that the loads follow.
+__global__ __launch_bounds__(256) void k_group_fetches(const HTask *tasks, uint32_t cap, const uint32_t *order, const uint32_t *ghead, const uint32_t *glist, unsigned long long *st)
+{
+    const uint32_t n_big = min(glist[cap], cap), n_groups = min(n_big + glist[cap + 1], cap);
+    unsigned long long ev = 0, ch = 0;
+    for (uint32_t g = blockIdx.x * 256 + threadIdx.x; g < n_groups; g += gridDim.x * 256) {
+        const uint32_t slot = glist[g < n_big ? g : cap - 1u - (g - n_big)], n = tasks[order[slot]].n;
+        ev += (unsigned long long)ghead[slot] * n; ch += (n + 63u) / 64u;
+    }
+    if (ev) { atomicAdd(&st[0], ev); atomicAdd(&st[1], ch); }
+}
+// st[2]: candidates of the tasks inside one sub-range, st[3]: those of them whose set (window and offset mod 32: the third signature) lies in more than one tile of
+// k_task_groups.  Slot word 1: a bit per tile, mod 64 (pass 0); a set whose tiles are 64 apart and no others is not seen as cut.
+__global__ __launch_bounds__(256) void k_sigc_tiles(const HTask *tasks, const uint32_t *n_tasks_ptr, uint32_t cap, const uint32_t *order, unsigned long long *tab, uint32_t mask, uint32_t T, int pass, unsigned long long *st)
+{
+    const uint32_t n = min(*n_tasks_ptr, cap);
+    for (uint32_t s = blockIdx.x * 256 + threadIdx.x; s < n; s += gridDim.x * 256) {
+        const HTask tk = tasks[order[s]];
+        if (!tk.n || !(tk.flags & 2u)) continue;
+        const unsigned long long sg = sigc_of(tk);
+        if (!pass) {
+            for (uint32_t slot = (uint32_t)(sg >> 20) & mask;; slot = (slot + 1) & mask) {
+                const unsigned long long prev = atomicCAS(&tab[2 * (size_t)slot], 0ull, sg);
+                if (prev == 0ull || prev == sg) { atomicOr(&tab[2 * (size_t)slot + 1], 1ull << ((s / T) & 63u)); break; }
+            }
+            continue;
+        }
+        uint32_t slot = (uint32_t)(sg >> 20) & mask, probes = 0;   // (bounded probe: see k_sig_hist)
+        while (tab[2 * (size_t)slot] != sg && probes <= mask) { slot = (slot + 1) & mask; probes++; }
+        if (probes > mask) continue;
+        const unsigned long long w = tab[2 * (size_t)slot + 1];
+        atomicAdd(&st[2], (unsigned long long)tk.n);
+        if (w & (w - 1ull)) atomicAdd(&st[3], (unsigned long long)tk.n);
+    }
+}
+const int SIG_KINDS = 5;   // same window; and offset; and offset mod 32 within D = 1, 2, 4; behind them four words of group figures (k_group_fetches, k_sigc_tiles)
 unsigned long long *g_sig_tab = nullptr, *g_sig_hist = nullptr;
 const uint32_t SIG_SLOTS = 1u << 23;
 }  // namespace
 
-void bsx_sig_hist_pass(const HeavyArgsRaw &R, hipStream_t stream)
+void bsx_sig_hist_pass(const HeavyArgsRaw &R, hipStream_t stream, bool groups, uint32_t tile)
 {
     if (!g_sig_tab) {
-        if (hipMalloc((void **)&g_sig_tab, (size_t)SIG_SLOTS * 16) != hipSuccess || hipMalloc((void **)&g_sig_hist, SIG_KINDS * 64 * 8) != hipSuccess) { g_sig_tab = nullptr; return; }
-        (void)hipMemsetAsync(g_sig_hist, 0, SIG_KINDS * 64 * 8, stream);
+        if (hipMalloc((void **)&g_sig_tab, (size_t)SIG_SLOTS * 16) != hipSuccess || hipMalloc((void **)&g_sig_hist, (SIG_KINDS * 64 + 4) * 8) != hipSuccess) { g_sig_tab = nullptr; return; }
+        (void)hipMemsetAsync(g_sig_hist, 0, (SIG_KINDS * 64 + 4) * 8, stream);
     }
     for (int with_h = 0; with_h < 2; with_h++) {
         (void)hipMemsetAsync(g_sig_tab, 0, (size_t)SIG_SLOTS * 16, stream);
@@ -3762,6 +3875,18 @@ void bsx_sig_hist_pass(const HeavyArgsRaw &R, hipStream_t stream)
         for (int pass = 0; pass < 2; pass++)
             hipLaunchKernelGGL(k_sigc_count, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, g_sig_tab, SIG_SLOTS - 1, D, pass, g_sig_hist + 64 * kind);
     }
+    if (groups) {   // (the order and the groups of this pass are in place: the caller runs this behind bsx_launch_task_order on the same stream)
+        hipLaunchKernelGGL(k_group_fetches, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.task_cap, R.order, R.ghead, R.glist, g_sig_hist + 64 * SIG_KINDS);
+        (void)hipMemsetAsync(g_sig_tab, 0, (size_t)SIG_SLOTS * 16, stream);
+        for (int pass = 0; pass < 2; pass++)
+            hipLaunchKernelGGL(k_sigc_tiles, dim3(1024), dim3(256), 0, stream, (const HTask *)R.tasks, R.n_tasks, R.task_cap, R.order, g_sig_tab, SIG_SLOTS - 1, bsx_group_tile(tile), pass, g_sig_hist + 64 * SIG_KINDS);
+    }
+}
+
+// st: evaluations, group chunks, candidates inside one sub-range, those of them in sets that a tile border cut — summed since the last report
+bool bsx_sig_group_stats(unsigned long long st[4])
+{
+    return g_sig_tab && hipDeviceSynchronize() == hipSuccess && hipMemcpy(st, g_sig_hist + 64 * SIG_KINDS, 32, hipMemcpyDeviceToHost) == hipSuccess;
 }
 
 void bsx_sig_hist_report(void)
@@ -3779,7 +3904,7 @@ void bsx_sig_hist_report(void)
             if (h[64 * with_h + 32 + k])
                 fprintf(stderr, "[sighist]   %s %-6u cand %.4f tasks %.4f\n", k == 31 ? "spanning" : k == 30 && with_h >= 2 ? "beyond" : "R <=", k == 31 || (k == 30 && with_h >= 2) ? 0u : 1u << k, (double)h[64 * with_h + k] / (double)std::max(1ull, tot), (double)h[64 * with_h + 32 + k] / (double)std::max(1ull, tt));
     }
-    (void)hipMemset(g_sig_hist, 0, SIG_KINDS * 64 * 8);
+    (void)hipMemset(g_sig_hist, 0, (SIG_KINDS * 64 + 4) * 8);
 }
 
 // BSX_SECTOR_STATS (diagnostic build only; a no-op in the shipped library): count and clear the sectors the scan launch just marked

@@ -297,6 +297,8 @@ struct bsx_batch {
     bool same_kernel = false;    // the scan kernel is k_hscan_same (WGBS unless BSX_SAME=0, RRBS with BSX_SAME=2): read once, at creation
     uint32_t same_d = 0;         // ... and its groups span this many offset classes beyond their first (BSX_SAME_D, 0 .. the build's HG_D, which is the default): read with it
     uint32_t same_r = 0;         // ... and hold this many tasks at most (BSX_SAME_R, 1 .. the build's HG_R, which is the default; 0 until the batch is created: the build's HG_R)
+    uint32_t group_tile = 0;     // ... formed over tiles of this many slots of the scan order (BSX_GROUP_TILE, a power of two from 64; 0: the build's HG_TILE)
+    uint32_t group_big = 0;      // ... of which those of this many tasks and more are started first (BSX_GROUP_BIG; 0: the build's HG_BIG)
     bool sector_stats = false;   // diagnostics (a build with -DBSX_SECTOR_STATS): distinct sectors per scan launch
     uint32_t xcd_map = 128;   // order_block (bsx_align.hip): pieces of 128 scan blocks dealt to the XCDs in turn
     uint32_t *h_pinned = nullptr;  // pinned host words for the per-pass count read-backs
@@ -515,6 +517,8 @@ static int ensure_scratch(bsx_batch *b)
         const bool same_kernel = b->same_kernel = b->ref->P.rrbs ? same_env0 == 2 : same_env0 != 0;
         b->same_d = getenv("BSX_SAME_D") ? (uint32_t)std::min<long>(std::max<long>(0, atol(getenv("BSX_SAME_D"))), (long)bsx_same_d_max()) : bsx_same_d_max();
         b->same_r = getenv("BSX_SAME_R") ? (uint32_t)std::min<long>(std::max<long>(1, atol(getenv("BSX_SAME_R"))), (long)bsx_same_r_max()) : bsx_same_r_max();
+        b->group_tile = getenv("BSX_GROUP_TILE") ? (uint32_t)std::max<long>(0, atol(getenv("BSX_GROUP_TILE"))) : 0u;
+        b->group_big = getenv("BSX_GROUP_BIG") ? (uint32_t)std::max<long>(0, atol(getenv("BSX_GROUP_BIG"))) : 0u;
         auto alloc_pools = [&]() -> hipError_t {
             hipError_t e;
 #define POOL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
@@ -961,14 +965,14 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
                 if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 1], hw.s_ctrl));
                 // scan order of the tasks this pass published, still on the group's stream: done by the time the main stream gets to the scan
                 q.H.order = hw.d_order; q.H.xcd_map = b->xcd_map; q.H.ghead = hw.d_rank; q.H.glist = hw.d_glist;
-                bsx_launch_task_order(q.H, b->bin_shift, b->n_bins, hw.d_bins, hw.d_bstart, hw.d_chunk_tot, hw.d_rank, hw.d_order, in, hw.s_ctrl, spread, same_scan, b->same_d, b->same_r);
+                bsx_launch_task_order(q.H, b->bin_shift, b->n_bins, hw.d_bins, hw.d_bstart, hw.d_chunk_tot, hw.d_rank, hw.d_order, in, hw.s_ctrl, spread, same_scan, b->same_d, b->same_r, b->group_tile, b->group_big);
                 // The scan: on the batch's stream with a grid for the whole task pool — or, once the group is in its tail (few tasks per
                 // pass, see the poll loop), behind the control kernel on the group's own high-priority stream with a small grid whose
                 // blocks sweep: beside ANOTHER batch's bulk scans a pool-sized grid of mostly empty blocks only trickles through the
                 // dispatcher, which stretched the tail of the older batch until the younger one's bulk was done — two batches in flight
                 // always finished together, and their transfers never overlapped the other's kernels.
                 if (b->stage_timing) { HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 2], hw.s_ctrl)); b->ctrl_ev_used += 3; }
-                if (b->sig_hist) bsx_sig_hist_pass(q.H, hw.s_ctrl);
+                if (b->sig_hist) bsx_sig_hist_pass(q.H, hw.s_ctrl, same_scan, b->group_tile);
                 hipStream_t s_scan = b->stream;
                 if (q.tail) s_scan = hw.s_ctrl;
                 else {
@@ -1170,9 +1174,16 @@ extern "C" int bsx_batch_counters(bsx_batch *b, uint64_t c[BSX_N_COUNTERS])
 #else
     uint64_t dg[3] = {0, 0, 0};
     for (int i = 0; i < 64; i++) { for (int k = 0; k < 4; k++) c[7 + k] += sh[i * 8 + k]; c[15] += sh[i * 8 + 4]; for (int k = 0; k < 3; k++) dg[k] += sh[i * 8 + 5 + k]; }
-    if (b->sig_hist && c[15])
-        fprintf(stderr, "[sighist] scan kernel: %.4f of the candidates in groups, mean group %.2f reads, in groups of >= 4 %.4f; evaluations of a read whose words and threshold equal an earlier member's of its group: %.4f of all\n", (double)c[15] / (double)std::max<uint64_t>(1, c[7]),
-                (double)dg[0] / (double)c[15], (double)dg[1] / (double)c[7], (double)dg[2] / (double)c[7]);
+    if (b->sig_hist && c[15]) {
+        // (behind the line's own text: what a fetch serves — the harmonic figure, from the groups as formed — and what the tiles of k_task_groups cut; both summed over
+        //  the process since the last report, like the histograms)
+        unsigned long long gs[4] = {0, 0, 0, 0};
+        (void)bsx_sig_group_stats(gs);
+        fprintf(stderr, "[sighist] scan kernel: %.4f of the candidates in groups, mean group %.2f reads, in groups of >= 4 %.4f; evaluations of a read whose words and threshold equal an earlier member's of its group: %.4f of all"
+                "; reads per fetch %.2f (%llu evaluations, %llu group chunks), candidates in sets that a tile border cut %.4f\n", (double)c[15] / (double)std::max<uint64_t>(1, c[7]),
+                (double)dg[0] / (double)c[15], (double)dg[1] / (double)c[7], (double)dg[2] / (double)c[7],
+                (double)gs[0] / (64.0 * (double)std::max(1ull, gs[1])), gs[0], gs[1], (double)gs[3] / (double)std::max(1ull, gs[2]));
+    }
 #endif
     return BSX_OK;
 }

@@ -101,10 +101,12 @@ void bsx_launch_hscan_shared(const AlignArgs &A, const HeavyArgsRaw &H, hipStrea
 // scan order of a pass (task ids by the index entry they start at, 2^shift entries per bin), computed on the device
 uint32_t bsx_bin_chunks(uint32_t n_bins);
 void bsx_launch_task_order(const HeavyArgsRaw &H, uint32_t shift, uint32_t n_bins, uint32_t *bins, uint32_t *bstart, uint32_t *chunk_tot, uint32_t *rank, uint32_t *order,
-                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread = 0, bool groups = false, uint32_t same_d = 0, uint32_t same_r = 0);   // spread: tasks inside one sub-range are dealt over the bins they cover by their read offset (k_hscan_same), 2: by its low five bits; same_d: offset classes a group spans beyond its first; same_r: tasks per group at most (0: the build's HG_R)
+                           uint32_t *zero_blk, hipStream_t stream, uint32_t spread = 0, bool groups = false, uint32_t same_d = 0, uint32_t same_r = 0, uint32_t tile = 0, uint32_t big = 0);   // spread: tasks inside one sub-range are dealt over the bins they cover by their read offset (k_hscan_same), 2: by its low five bits; same_d: offset classes a group spans beyond its first; same_r: tasks per group at most (0: the build's HG_R); tile: slots of the scan order that k_task_groups groups at a time (0: the build's HG_TILE); big: groups of this many tasks and more are started first (0: the build's HG_BIG)
 uint32_t bsx_same_d_max(void);   // HG_D of this build
 uint32_t bsx_same_r_max(void);   // HG_R of this build
-void bsx_sig_hist_pass(const HeavyArgsRaw &H, hipStream_t stream);   // diagnostics, BSX_SIGHIST=1
+void bsx_sig_hist_pass(const HeavyArgsRaw &H, hipStream_t stream, bool groups = false, uint32_t tile = 0);   // diagnostics, BSX_SIGHIST=1 (groups: behind bsx_launch_task_order with groups, the figures of bsx_sig_group_stats as well)
+bool bsx_sig_group_stats(unsigned long long st[4]);   // (read, candidate) evaluations, 64-candidate chunks of groups, candidates inside one sub-range, those in sets that lie in more than one tile
+uint32_t bsx_group_tile(uint32_t tile);   // the tile k_task_groups takes for this setting
 void bsx_sig_hist_report(void);
 void bsx_sector_pass(const bsx_ref *r, hipStream_t stream);   // diagnostics (build with -DBSX_SECTOR_STATS, run with BSX_SECTOR_STATS=1): distinct 64-byte sectors the group scan touches per launch
 void bsx_sector_report(void);
