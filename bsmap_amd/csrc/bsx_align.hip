@@ -25,6 +25,7 @@
 #include "bsx_internal.h"
 #include "bsx_dev.h"
 #include "bsx_groups.h"
+#include "bsx_rows.h"
 #include "bsx_kernel_args.h"
 
 namespace {
@@ -2591,6 +2592,9 @@ __global__ __launch_bounds__(64 * BSX_HSCAN_WPB, BSX_HSCAN_WAVES) void k_hscan(A
 // first and an XCD turn is 128 groups: a wave with 64 reads runs four times as long as one with 16, and in plain order the launches ended on such waves.
 // Round 10: the groups are formed over whole runs of a window inside tiles of 1 024 slots of the scan order and cut into near-equal sizes (k_task_groups, bsx_groups.h); this kernel is unchanged.  A fetch
 // serves 13.7 reads instead of 10.0, C3 203.4 -> 194.5 ms per step.
+// Round 11: the groups of 129-160 nt reads with the work counters off have a read loop of their own (hs_eval_lean): nothing of a survivor's is formed before a chunk holds
+// one, and a word is evaluated for the step's four chunks together — four independent chains, one test per word (HG_LEAN, HG_JOINT; HG_SPLIT, the row in evaluation order
+// read in two halves, is built and off).  C3 194.2 -> 168.8 and 196.2 -> 166.9 ms per step on two boxes.
 // ---------------------------------------------------------------------------------------------------------------
 #ifndef HG_WPB
 #define HG_WPB 1        /* waves (= groups) per block: 1 measured best (1: 96.0-98.9, 2: 101.7-102.2, 4: 110.9 ms per step) — a block gives its slot back when its LAST wave ends */
@@ -2626,7 +2630,8 @@ static_assert(HG_R == 16u || HG_R == 32u || HG_R == 48u || HG_R == 64u, "a lane 
 #ifndef HG_EXIT
 #define HG_EXIT 15      /* the exiting evaluation of the WGBS groups of 129-160 nt reads without work counters (same_exit).  Bit i: a wave-uniform test behind the (i + 1)-th
                            evaluated word (the last word's test is the survivor ballot and always there).  15 against 3: C3 209.8-210.3 against 211.3 ms per step.
-                           0 = the form before round 7: all words of every chunk, in their natural order */
+                           0 = the form before round 7: all words of every chunk, in their natural order.  Since round 11 the shipped loop of this class is hs_eval_lean (HG_LEAN), which
+                           has a test behind every word and is taken only with 15; any other value runs same_exit as before */
 #endif
 #ifndef BSX_HSAME_WAVES
 #define BSX_HSAME_WAVES 4
@@ -2641,10 +2646,39 @@ static_assert(HG_R == 16u || HG_R == 32u || HG_R == 48u || HG_R == 64u, "a lane 
                            baseline of an A/B is a build with -DHG_D=0 (or the parent's library) */
 #endif
 #ifndef HG_ROWPF
-#define HG_ROWPF 0      /* the next read's LDS row requested before this read is evaluated (16 registers) */
+#define HG_ROWPF 0      /* hs_eval_read's loop (every instantiation but the one HG_LEAN takes): the next read's whole LDS row requested before this read is evaluated (16 registers).
+                           Round 7: 226.5 against 210 ms per step.  Round 11 measured the half of it that fits the budget (HG_SPLIT, eight registers): level too — the row's LDS round trip
+                           is not what the read loop waits for */
+#endif
+#ifndef HG_LEAN
+#define HG_LEAN 1       /* round 11, WGBS groups of 129-160 nt reads without the work counters only (hs_eval_lean; needs HG_EXIT = 15): what a survivor needs — the task's lane read and
+                           output address, its survivor count and the write-back, the list ordinal, the position (the frame's plus 32 d, d kept as a scalar) — is formed where a chunk
+                           holds a survivor, 1.7 % of the (read, chunk) evaluations, not per read.  0: hs_eval_read for every instantiation, the loop of round 10.  On its own (HG_JOINT=0,
+                           HG_SPLIT=0) it measured level with the parent, C3 192.09 / 193.80 / 194.12 against 193.20 / 194.16 / 195.41 ms per step: the loop is bound by its chains of
+                           dependent instructions and their branches, not by the number of instructions.  It is what HG_JOINT is built on */
+#endif
+#ifndef HG_SPLIT
+#define HG_SPLIT 0      /* with HG_LEAN: 1: the row in the order of evaluation (bsx_rows.h) and read in two halves: the half that words 0 and 4 need is requested a read ahead (eight
+                           registers), the half of words 3, 2, 1 only once a chunk is still alive behind word 4.  0: the row of the other instantiations, all four quarters in front of
+                           the evaluation.  Measured level both ways — chunk-major 192.37 / 194.24 / 194.87 against 192.09 / 193.80 / 194.12 without, joint (HG_JOINT=3) 166.92 / 168.82 /
+                           169.42 against 167.69 / 168.49 / 169.18 — so it stays off.  HG_ROWPF of round 7 is the whole next row a read ahead, in the other loop */
+#endif
+#ifndef HG_JOINT
+#define HG_JOINT 3      /* with HG_LEAN: how a read leaves the step's HG_C chunks.  0: chunk-major — a chunk's words one after the other — in two phases: words 0 and 4 of the four chunks,
+                           then words 3, 2, 1 of the chunks still alive.  1: evaluated word i of the four chunks back to back, and the read left for the step once no chunk is alive; a
+                           chunk that is not alive takes no further part (a scalar test per chunk).  2: it is evaluated all the same and ignored: four independent chains and no test
+                           between them.  3: as 2, and where every lane holds a candidate in every chunk (all steps of a window but its last) ONE test per word: the smallest of a lane's
+                           four counts against the threshold; the chunks' own ballots are formed behind the last word.  C3 ms per step on one box, alternating, beside the parent's
+                           193.20 / 194.16 / 195.41: 0: 192.37 / 194.24 / 194.87; 1: 179.86 / 182.72 / 182.76; 2: 174.08 / 176.48 / 176.74; second box, parent 190.01 / 191.77 / 193.08:
+                           2: 176.69 / 177.67 / 179.07; 3: 166.92 / 168.82 / 169.42 */
+#endif
+#ifndef HG_JOINT_FIRST
+#define HG_JOINT_FIRST 0  /* with HG_JOINT >= 2: 1: no test behind the first evaluated word.  With 2: 173.22 / 173.46 / 175.62 against 176.69 / 177.67 / 179.07; with 3: 167.30 / 168.90 / 171.02
+                             against 166.92 / 168.82 / 169.42: level, off */
 #endif
 struct SameLds {
     // per read of a group (row of 20 dwords): X0 Y0 M0 X1 | Y1 M1 X2 Y2 | M2 threshold X3 Y3 | M3 X4 Y4 M4 | task, first list ordinal, -, -
+    // (threshold: | plain << 16 | offset class << 17).  The groups of 129-160 nt reads without the work counters hold their rows in the order of evaluation: bsx_rows.h (HG_SPLIT)
     union {
         __attribute__((aligned(16))) uint32_t UW[HG_R][20];
         struct { uint32_t TAB[4][32]; uint2 PT[HP_PAIRS * 32]; uint2 Q[HP_QCAP]; } one;   // one-task path (hp_task); 4 KB per wave: k_hctrl's blocks (58 KB paired) have to fit beside 20 waves of this kernel
@@ -2837,6 +2871,109 @@ __device__ __forceinline__ void hs_eval_read(const uint32_t (&flo)[HG_C][5], con
     }
 }
 
+// Round 11 (HG_LEAN): one 129-160 nt read of a WGBS group against the step's chunks, work counters off.  The words and the tests are same_exit's — the order
+// 0, 4, 3, 2, 1, a wave-uniform test behind every word, a chunk that holds a survivor never left early — but nothing that only a survivor needs is done before
+// one is found: al[u] is the ballot of chunk u's candidates still within the threshold (scalar), tot[u] their counts, and the task's id and output address, its
+// survivor count nsv (lane k's), the list ordinal (cb + 64 u + lane) and the position (the frame's plus 32 dcur) are formed behind the last word, where a chunk
+// is still alive.  Survivors are written in chunk order and then lane order, as hs_eval_read writes them.
+// SPLIT: the row in evaluation order (bsx_rows.h); q0, q1 are its first half, and the second is requested from `row` once a chunk is alive behind the second
+// evaluated word (p2, p3 are not read).  !SPLIT: the row of the other instantiations, whole, in q0, q1, p2, p3.
+// JOINT (HG_JOINT): evaluated word i of all chunks back to back, and the read left once no chunk is alive; 1: a chunk that is not alive is skipped under a scalar
+// test, 2: it is evaluated and ignored — four independent chains with no test between them —, 3 (shipped): as 2, and in the steps where every lane of every chunk
+// holds a candidate one test per word, on the smallest of the lane's four counts.  0: chunk-major in two phases (words 0 and 4 of the four chunks; words 3, 2, 1 of
+// those still alive): every (read, chunk) evaluation takes exactly the words same_exit takes, as it does with 1; with 2 and 3 a chunk takes the words of the step's
+// longest-lived chunk (2.24 instead of 2.00 per evaluation, C3).  What the loop was bound by is the chain bitop, bitop, bcnt, compare, branch per word and chunk at
+// 3.5 waves per SIMD, not the number of instructions: 0 measured level with round 10's loop, 3 takes 12-15 % off C3's step.
+// Results cannot change in any form: a count only grows, so a chunk that holds a survivor is alive behind every word, reaches the last word with its whole count,
+// and a chunk that was ignored has no lane within the threshold behind the last word.  dgw (BSX_SCAN_WORDS builds): (read, chunk) evaluations | words << 16
+template <bool PLAIN, bool SPLIT>
+__device__ __forceinline__ uint32_t lean_word(int i, const uint32_t (&flo)[5], const uint32_t (&fhi)[5], const uint4 &q0, const uint4 &q1, const uint4 &q2, const uint4 &q3)
+{
+    const int j = bsx_row_eval_word(i);   // (i is a constant wherever this is inlined)
+    if (!SPLIT) return same_word<PLAIN>(j, flo, fhi, q0, q1, q2, q3);
+    uint32_t X, Y, M;
+    bsx_row_word(i, q0, q1, q2, q3, X, Y, M);
+    return (PLAIN && j < 4) ? bsx_plane_mismatch_full(flo[j], fhi[j], X, Y) : bsx_plane_mismatch(flo[j], fhi[j], X, Y, M);
+}
+template <bool PLAIN, bool FULL, bool SPLIT, int JOINT>
+__device__ __forceinline__ void hs_eval_lean(const HeavyArgs &H, const uint32_t (&flo)[HG_C][5], const uint32_t (&fhi)[HG_C][5], const u64 (&vm)[HG_C], const uint32_t (&hloc)[HG_C],
+                                             const uint4 &q0, const uint4 &q1, const uint4 &p2, const uint4 &p3, const uint4 *row, uint32_t thr, uint32_t k, uint32_t tid, uint32_t &nsv,
+                                             int lane, uint32_t cb, uint32_t dcur, uint32_t strand, uint32_t &dgw)
+{
+    u64 al[HG_C];
+    uint32_t tot[HG_C];
+    uint4 q2 = p2, q3 = p3;
+#pragma unroll
+    for (int u = 0; u < HG_C; u++) { al[u] = FULL ? ~0ull : vm[u]; tot[u] = 0; }
+#ifdef BSX_SCAN_WORDS
+#pragma unroll
+    for (int u = 0; u < HG_C; u++) if (al[u]) dgw += 1u;
+#define LEAN_DG dgw += 1u << 16;
+#else
+#define LEAN_DG
+#endif
+    // (a count only grows: the lanes within the threshold behind a word were within it behind every word before, so the ballot needs no AND with the last one)
+#define LEAN_WORD(u, i) {                                                                                \
+        tot[u] = popc_acc(lean_word<PLAIN, SPLIT>(i, flo[u], fhi[u], q0, q1, q2, q3), tot[u]);           \
+        const u64 b_ = bsx_ballot(tot[u] <= thr);                                                        \
+        al[u] = (FULL && JOINT < 2) ? b_ : (b_ & al[u]);                                                 \
+        LEAN_DG }
+#define LEAN_ANY() (al[0] | al[1] | al[2] | al[3])
+    // (the second half as two 16-byte reads: left to itself the compiler requests the dwords of each word where it is evaluated, in 8- and 4-byte reads that cost the LDS path more)
+#define LEAN_HALF() asm volatile("" : "+v"(q2.x), "+v"(q2.y), "+v"(q2.z), "+v"(q2.w), "+v"(q3.x), "+v"(q3.y), "+v"(q3.z), "+v"(q3.w));
+    static_assert(HG_C == 4, "written out for four chunks");
+    if (JOINT == 3 && FULL) {
+        // one test per word for the four chunks: a candidate of the step is within the threshold iff the smallest of its lane's four counts is (every lane holds a
+        // candidate in every chunk); the chunks' own ballots are formed behind the last word only
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            if (SPLIT && i == 2) { q2 = row[2]; q3 = row[3]; LEAN_HALF() }
+#pragma unroll
+            for (int u = 0; u < HG_C; u++) { tot[u] = popc_acc(lean_word<PLAIN, SPLIT>(i, flo[u], fhi[u], q0, q1, q2, q3), tot[u]); LEAN_DG }
+            if (HG_JOINT_FIRST && i == 0) continue;
+            if (!bsx_ballot(min(min(tot[0], tot[1]), min(tot[2], tot[3])) <= thr)) return;
+        }
+#pragma unroll
+        for (int u = 0; u < HG_C; u++) al[u] = bsx_ballot(tot[u] <= thr);
+    } else if (JOINT) {
+#pragma unroll
+        for (int i = 0; i < 5; i++) {
+            if (SPLIT && i == 2) { q2 = row[2]; q3 = row[3]; LEAN_HALF() }
+#pragma unroll
+            for (int u = 0; u < HG_C; u++) if (JOINT >= 2 || al[u]) LEAN_WORD(u, i)
+            if (HG_JOINT_FIRST && i == 0) continue;
+            if (!LEAN_ANY()) return;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < HG_C; u++) if (al[u]) { LEAN_WORD(u, 0) if (al[u]) LEAN_WORD(u, 1) }
+        if (!LEAN_ANY()) return;
+        if (SPLIT) { q2 = row[2]; q3 = row[3]; LEAN_HALF() }
+#pragma unroll
+        for (int u = 0; u < HG_C; u++) if (al[u]) { LEAN_WORD(u, 2) if (al[u]) { LEAN_WORD(u, 3) if (al[u]) LEAN_WORD(u, 4) } }
+        if (!LEAN_ANY()) return;
+    }
+#undef LEAN_WORD
+#undef LEAN_ANY
+#undef LEAN_HALF
+#undef LEAN_DG
+    // a chunk holds a survivor
+    SurvRec *const sv = H.tout[rl_u(tid, k)].surv;   // (wave-uniform: the address arithmetic stays on the scalar unit)
+    uint32_t nsk = rl_u(nsv, k);
+#pragma unroll
+    for (int u = 0; u < HG_C; u++) {
+        const u64 bp = al[u];
+        if (bp) {
+            const uint32_t pos = __builtin_amdgcn_mbcnt_hi((uint32_t)(bp >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bp, nsk));
+            if (__builtin_amdgcn_inverse_ballot_w64(bp) && pos < HS_SCAP) {
+                SurvRec r; r.w_ord = tot[u] | ((cb + (uint32_t)(u * 64 + lane)) << 8); r.hchr = strand; r.hloc = hloc[u] + 32u * dcur; r.hkey = 0; sv[pos] = r;
+            }
+            nsk += (uint32_t)__builtin_popcountll(bp);
+        }
+    }
+    if ((uint32_t)lane == k) nsv = nsk;
+}
+
 // one group of K (1 .. HG_R) tasks: lane j < K holds task j's id, unit | slot and first list ordinal; they cover the n index entries
 // from `key` on with read offset `hh` (RRBS: and tag filter tag_xor / tag_want).  NWR: the reads' 32-nt words where the length class has
 // its own code (5: 129-160 nt, the headline configuration; 4: 97-128 nt; 3: 65-96 nt, RRBS), 0 for any length.
@@ -2851,8 +2988,18 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     // need beyond the six of the three 16-byte gathers
     constexpr int XD = (!RRBS && NWR == 5) ? HG_D : 0, XP = XD;
     static_assert(HG_D >= 0 && HG_D <= 2 && 6 + HG_D <= BSX_PLANE_PAD, "the gather holds two pairs more at most, and stays inside the pad behind the strand copy");
+    // round 11: the headline's instantiation (reads of 129-160 nt, work counters off) has a read loop of its own (hs_eval_lean) and its rows in evaluation order
+    constexpr bool LEAN = HG_LEAN && HG_EXIT == 15 && NWR == 5 && !RRBS && !STATS, SPLIT = LEAN && HG_SPLIT;
+    static_assert(BSX_ROW_DWORDS == 20 && sizeof(L.W[0].UW[0]) == 4 * BSX_ROW_DWORDS, "bsx_rows.h describes a row of SameLds");
 #ifdef BSX_SIGHIST_DUPS
     u64 rowsig = 0;
+#endif
+#ifdef BSX_SCAN_CLOCKS
+    // diagnostic build (tools/build_variant.sh clocks -DBSX_SCAN_CLOCKS, tools/scan_clocks.sh): where a wave of the headline's instantiation spends its cycles — from the
+    // issue of a step's gathers to the frame being built (the gather wait), the read loop, and the whole of hs_group (the rest is the difference).  Not in the shipped kernel
+    constexpr bool CLK = NWR == 5 && !RRBS && !STATS;
+    u64 ck_gather = 0, ck_reads = 0;
+    const u64 ck_begin = __builtin_amdgcn_s_memtime();
 #endif
     if ((uint32_t)lane < K) {   // the read of this lane's task -> its row
         const ListReq &R = H.state[th & 0x3fffffffu].req[th >> 30];
@@ -2862,11 +3009,14 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
         for (int j = 0; j < 5; j++) {
             const int f = 3 * j, o = j < 3 ? 0 : 1;
             const uint32_t pm = R.pm[j];
-            row[f + o] = R.px[j]; row[f + 1 + o] = R.py[j]; row[f + 2 + o] = pm;
+            if (!SPLIT) { row[f + o] = R.px[j]; row[f + 1 + o] = R.py[j]; row[f + 2 + o] = pm; }
             if (j < nwr - 1) inner &= pm;
         }
         // (bits 17 and up: the row's offset class d — the group's frame is that of slot 0, whose d is 0, and the rows are sorted by d)
-        row[9] = R.thres | (inner == 0xFFFFFFFFu ? 0x10000u : 0u) | (XD ? ((sub_h - hh) >> 5) << 17 : 0u); row[16] = tid; row[17] = tc0;
+        const uint32_t tword = R.thres | (inner == 0xFFFFFFFFu ? 0x10000u : 0u) | (XD ? ((sub_h - hh) >> 5) << 17 : 0u);
+        if (SPLIT) bsx_row_pack(row, R.px, R.py, R.pm, tword);   // (the row in evaluation order: bsx_rows.h)
+        else row[9] = tword;
+        row[BSX_ROW_TASK] = tid; row[BSX_ROW_ORD] = tc0;
 #ifdef BSX_SIGHIST_DUPS
         u64 hsh = R.thres;
 #pragma unroll
@@ -2915,6 +3065,11 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     for (int u = 0; u < HG_C; u++) en[u] = same_entry<RRBS>(W, (uint32_t)(u * 64 + lane));
 #endif
     for (uint32_t cb = 0; cb < n; cb += STEP) {
+#ifdef BSX_SCAN_CLOCKS
+        __builtin_amdgcn_sched_barrier(0);
+        const u64 ck_step = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+#endif
 #if !HG_PREFETCH
 #pragma unroll
         for (int u = 0; u < HG_C; u++) nx[u] = same_load<RRBS, XP>(W, en[u]);
@@ -2951,12 +3106,73 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
         }
 #endif
         const bool full = !RRBS && cb + STEP <= n;   // (RRBS: the filters decide per entry)
-#if HG_ROWPF
+#ifdef BSX_SCAN_CLOCKS
+        // (the frame's words are made to exist — and the gathers to have landed — before the stamp)
+#pragma unroll
+        for (int u = 0; u < HG_C; u++) asm volatile("" :: "v"(flo[u][0]), "v"(fhi[u][4]), "v"(xlo[u][XD ? XD - 1 : 0]), "v"(xhi[u][XD ? XD - 1 : 0]));
+        __builtin_amdgcn_sched_barrier(0);
+        const u64 ck_frame = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+        ck_gather += ck_frame - ck_step;
+#endif
+#if HG_ROWPF   /* (the loop of hs_eval_read below; not with HG_LEAN's instantiation) */
         // (the next read's row is requested before this read is evaluated: its LDS round trip — four 16-byte reads of a wave — hides behind ~50 vector instructions)
         uint4 p0, p1, p2, p3 = make_uint4(0u, 0u, 0u, 0u);
         { const uint4 *row = reinterpret_cast<const uint4 *>(uw); p0 = row[0]; p1 = row[1]; p2 = row[2]; if (nwr > 3) p3 = row[3]; }
 #endif
         uint32_t dcur = 0;   // the offset class the frame stands at
+        if constexpr (LEAN) {
+            // Round 11.  Nothing of a survivor's is kept per read: hloc stays the frame's and the class a scalar (the position is formed where a survivor is written).
+            // SPLIT: the half of the row that words 0 and 4 need is requested a read ahead — on every path; the last member requests its own row again, never row K: at K = HG_R that row lies outside UW (see below)
+            const uint4 *const rows = reinterpret_cast<const uint4 *>(uw);
+            const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+            // read k of the group with its first half (SPLIT) in q0, q1
+            auto one_read = [&](uint32_t k, const uint4 &h0, const uint4 &h1) __attribute__((always_inline)) {
+                const uint4 *const row = rows + k * 5u;
+                uint4 q0 = h0, q1 = h1, p2 = zero4, p3 = zero4;
+                if (!SPLIT) { q0 = row[0]; q1 = row[1]; p2 = row[2]; p3 = row[3]; }
+                const uint32_t tp = rfl(SPLIT ? bsx_row_t(q0) : p2.y), thr = tp & 0xffffu;
+                const bool plain = ((tp >> 16) & 1u) != 0;
+                for (; dcur < (tp >> 17); dcur++) {   // the first row of the next offset class: the frame moves down a word (see below)
+#pragma unroll
+                    for (int u = 0; u < HG_C; u++) {
+#pragma unroll
+                        for (int t = 0; t < 4; t++) { flo[u][t] = flo[u][t + 1]; fhi[u][t] = fhi[u][t + 1]; }
+                        flo[u][4] = xlo[u][0]; fhi[u][4] = xhi[u][0];
+#pragma unroll
+                        for (int t = 0; t + 1 < XD; t++) { xlo[u][t] = xlo[u][t + 1]; xhi[u][t] = xhi[u][t + 1]; }
+                    }
+                }
+                uint32_t dgw = 0;
+                if (full) {
+                    if (plain) hs_eval_lean<true, true, SPLIT, HG_JOINT>(H, flo, fhi, vm, hloc, q0, q1, p2, p3, row, thr, k, tid, nsv, lane, cb, dcur, strand, dgw);
+                    else hs_eval_lean<false, true, SPLIT, HG_JOINT>(H, flo, fhi, vm, hloc, q0, q1, p2, p3, row, thr, k, tid, nsv, lane, cb, dcur, strand, dgw);
+                } else {
+                    if (plain) hs_eval_lean<true, false, SPLIT, HG_JOINT>(H, flo, fhi, vm, hloc, q0, q1, p2, p3, row, thr, k, tid, nsv, lane, cb, dcur, strand, dgw);
+                    else hs_eval_lean<false, false, SPLIT, HG_JOINT>(H, flo, fhi, vm, hloc, q0, q1, p2, p3, row, thr, k, tid, nsv, lane, cb, dcur, strand, dgw);
+                }
+#ifdef BSX_SCAN_WORDS
+                dg_ev += dgw & 0xffffu; dg_words += dgw >> 16;
+#else
+                (void)dgw;
+#endif
+            };
+            if (SPLIT) {
+                // Two reads per turn: the half in use and the half requested ahead change places without a copy.  The request is made on every path — the last member
+                // requests its own row again, never the row behind it, which at K = HG_R lies outside UW — so that the wait in front of a half's first use counts
+                // the requests behind it and does not wait for them too (a request under a test made every wait the join of both paths: the coming half's as well)
+                uint4 a0 = rows[0], a1 = rows[1], b0, b1;
+                for (uint32_t k = 0;; k += 2) {
+                    { const uint4 *const nr = rows + min(k + 1u, K - 1u) * 5u; b0 = nr[0]; b1 = nr[1]; }
+                    one_read(k, a0, a1);
+                    if (k + 1 >= K) break;
+                    { const uint4 *const nr = rows + min(k + 2u, K - 1u) * 5u; a0 = nr[0]; a1 = nr[1]; }
+                    one_read(k + 1, b0, b1);
+                    if (k + 2 >= K) break;
+                }
+            } else
+                for (uint32_t k = 0; k < K; k++) one_read(k, zero4, zero4);
+        } else
         for (uint32_t k = 0; k < K; k++) {
             // (a 16-byte LDS read of a wave moves 1 KB, 8 cycles of the CU's LDS path: one read of the row per step, not per chunk)
 #if HG_ROWPF
@@ -2999,6 +3215,12 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
             if (!STATS) { dg_ev += add15 & 0xffffu; dg_words += add15 >> 16; }
 #endif
         }
+#ifdef BSX_SCAN_CLOCKS
+        asm volatile("" :: "v"(nsv));
+        __builtin_amdgcn_sched_barrier(0);
+        ck_reads += __builtin_amdgcn_s_memtime() - ck_frame;
+        __builtin_amdgcn_sched_barrier(0);
+#endif
     }
     wave_fence();
     // results: lane j < K holds read j's counters
@@ -3018,7 +3240,7 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
         atomicAdd((u64 *)&sh[0], (u64)kk * n_cand);
         if (STATS) { atomicAdd((u64 *)&sh[1], 2ull * kk * n_cand - s1 + 3ull * s5); atomicAdd((u64 *)&sh[2], (u64)s1); atomicAdd((u64 *)&sh[3], (u64)s5); }
         if (K > 1) atomicAdd((u64 *)&sh[4], (u64)kk * n_cand);   // counter 15: candidates evaluated in groups of two reads and more
-#ifndef BSX_SCAN_WORDS
+#if !defined(BSX_SCAN_WORDS) && !defined(BSX_SCAN_CLOCKS)
         atomicAdd((u64 *)&sh[5], (u64)kk * n_cand * K); if (K >= 4) atomicAdd((u64 *)&sh[6], (u64)kk * n_cand); if (n_dup) atomicAdd((u64 *)&sh[7], (u64)n_dup * n_cand);  // diagnostics (BSX_SIGHIST)
 #endif
     }
@@ -3026,6 +3248,12 @@ __device__ __forceinline__ void hs_group(const AlignArgs &A, const HeavyArgs &H,
     if (lane == 0 && dg_ev) {   // (slots 5 and 6 of shard 0, which in this build nothing else writes: hs_group's own diagnostics above are the only other writer of slots 5-7)
         u64 *sh = (u64 *)A.scan_stats;
         atomicAdd((u64 *)&sh[5], dg_ev); atomicAdd((u64 *)&sh[6], dg_words);
+    }
+#endif
+#ifdef BSX_SCAN_CLOCKS
+    if (CLK && lane == 0) {   // (slots 5-7 of shard 0, as the words' build uses them: cycles of the gather wait, of the read loop and of the whole of hs_group, summed over the waves)
+        u64 *sh = (u64 *)A.scan_stats;
+        atomicAdd((u64 *)&sh[5], ck_gather); atomicAdd((u64 *)&sh[6], ck_reads); atomicAdd((u64 *)&sh[7], (u64)__builtin_amdgcn_s_memtime() - ck_begin);
     }
 #endif
     wave_fence();

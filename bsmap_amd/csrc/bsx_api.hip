@@ -1171,6 +1171,13 @@ extern "C" int bsx_batch_counters(bsx_batch *b, uint64_t c[BSX_N_COUNTERS])
     if (sh[5])
         fprintf(stderr, "[scanwords] 129-160 nt: %llu (read, 64-candidate chunk) evaluations, %llu words, mean %.3f words per evaluation\n",
                 (unsigned long long)sh[5], (unsigned long long)sh[6], (double)sh[6] / (double)sh[5]);
+#elif defined(BSX_SCAN_CLOCKS)
+    // diagnostic build: slots 5-7 of shard 0 hold the cycles that the waves of the group scan of 129-160 nt reads (work counters off) spent from the issue of a step's gathers
+    // to its frame, in the read loop, and in hs_group as a whole (tools/scan_clocks.sh).  The [sighist] line is not printed by this build either
+    for (int i = 0; i < 64; i++) { for (int k = 0; k < 4; k++) c[7 + k] += sh[i * 8 + k]; c[15] += sh[i * 8 + 4]; }
+    if (sh[7])
+        fprintf(stderr, "[scanclocks] 129-160 nt: %llu wave cycles in hs_group: gather wait %.4f, read loop %.4f, the rest %.4f\n", (unsigned long long)sh[7],
+                (double)sh[5] / (double)sh[7], (double)sh[6] / (double)sh[7], 1.0 - ((double)sh[5] + (double)sh[6]) / (double)sh[7]);
 #else
     uint64_t dg[3] = {0, 0, 0};
     for (int i = 0; i < 64; i++) { for (int k = 0; k < 4; k++) c[7 + k] += sh[i * 8 + k]; c[15] += sh[i * 8 + 4]; for (int k = 0; k < 3; k++) dg[k] += sh[i * 8 + 5 + k]; }
