@@ -8,6 +8,8 @@
 //   k_meth_pile    trim, bounds test, compare read and reference letters, atomicAdd on depth / methylated counters
 //   k_meth_pile_mbias   the same pile-up in a persistent grid that also tallies every call by strand, context and read cycle (M-bias, --mbias) in LDS
 //   k_meth_cpg     fold the G of every CG into its C
+// With the C/T-SNP mode on (bsx_meth_set_ct_snp, an extension: -i of later BSMAP releases) the same pile-up pass also counts, per reference position, what the reads
+// of the OTHER reference strand show there (G over an intact C, A over a C->T SNP), and the row selection and the table use those two counters.
 //   k_meth_count / k_meth_emit   ordered compaction of the positions the table will list
 // The host side (bsmap_amd/methratio.py) parses the option surface, the FASTA and the BSP / SAM lines, and prints the
 // table with the reference's arithmetic.  All counters are integers: results are exact.
@@ -61,6 +63,10 @@ struct AlnBatch {
     uint32_t n, index_base, trim_fillin;
     uint32_t trim5, trim3;     // calls of the first trim5 / last trim3 sequencing cycles of every read are ignored
 };
+
+// C/T-SNP mode: the kernels take `rev`, one cell per reference position: low word rev_GA (opposite-strand calls that show the unconverted or the converted
+// letter), high word rev_G (those that show the unconverted letter); null when the mode is off.  (A kernel argument of its own, not a field of MethDev: the
+// kernels' other arguments stay where they were.)
 
 // M-bias tally: cells[strand code 0..3][context 0..3][cycle 0..BSX_MBIAS_CYCLES-1][methylated ? 1 : 0], then one counter of the calls at later cycles
 struct MbiasDev {
@@ -156,8 +162,11 @@ __device__ __forceinline__ uint32_t meth_context(const uint8_t *ref, u64 g, u64 
 // Cycle of letter j of the untrimmed read = its 0-based index in sequencing direction: j for '++' and '--', n0-1-j for '-+' and '+-'.  (methratio.py:52-63:
 // the fragment end of '+-' / '-+' is the displayed right end, '+-' loses its fill-in at the displayed right = its first cycles, '--' at the displayed left.)
 // A call at cycle c is dropped when c < trim5 or c >= n0 - trim3; the window, and with it pos, the bounds tests and the duplicate filter, does not move.
-template <bool MBIAS>
-__device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, uint32_t i, const MethWindow &W, int lane, uint32_t *s_tally, const MbiasDev &D, u64 &over)
+// With SNP a letter over the OTHER strand's cytosine (reference G under a '+' read, C under a '-' read) makes a reverse call: one 64-bit add on the position's
+// packed cell, rev_G and rev_GA for the unconverted letter, rev_GA alone for the converted one.  A reference letter is C or G or neither, so a lane makes at most
+// one call per letter; the cycle mask drops a reverse call like a forward one, and a reverse call enters nothing else.
+template <bool MBIAS, bool SNP>
+__device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, uint32_t i, const MethWindow &W, int lane, uint32_t *s_tally, const MbiasDev &D, u64 &over, u64 *rev)
 {
     if (W.pos < 0) return;         // (a negative position would make the reference slice from the chromosome's end: never produced by bsmap)
     const uint32_t st = W.st;
@@ -167,7 +176,19 @@ __device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, 
     const u64 c0 = M.chr_off[W.c], c1 = M.chr_off[W.c + 1], g0 = c0 + (u64)W.pos;
     const int64_t len = W.hi - W.lo, cyc_lo = (int64_t)B.trim5, cyc_hi = W.n0 - (int64_t)B.trim3;
     for (int64_t k = lane; k < len; k += 64) {
-        if (M.ref[g0 + k] != match) continue;
+        const uint8_t rl = M.ref[g0 + k];
+        if (rl != match) {
+            if (SNP) {
+                const uint8_t rc_match = plus ? 'G' : 'C', rc_convert = plus ? 'A' : 'T';
+                if (rl != rc_match) continue;
+                const uint8_t rch = s[k];
+                if (rch != rc_convert && rch != rc_match) continue;
+                const int64_t rj = W.lo + k, rcyc = backward ? W.n0 - 1 - rj : rj;
+                if (rcyc < cyc_lo || rcyc >= cyc_hi) continue;
+                atomicAdd(&rev[g0 + k], rch == rc_match ? ((1ull << 32) | 1ull) : 1ull);  // < 2^32 alignments per handle: the low word cannot carry
+            }
+            continue;
+        }
         const uint8_t ch = s[k];
         if (ch != convert && ch != match) continue;
         const int64_t j = W.lo + k, cyc = backward ? W.n0 - 1 - j : j;  // 0 <= cyc < n0
@@ -186,7 +207,8 @@ __device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, 
 }
 
 // one wave per alignment
-__global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n_valid)
+template <bool SNP>
+__global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n_valid, u64 *rev)
 {
     const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -195,14 +217,15 @@ __global__ __launch_bounds__(256) void k_meth_pile(MethDev M, AlnBatch B, u64 *n
     if (!meth_window(M, B, i, W)) return;
     if (lane == 0) atomicAdd(n_valid, 1ull);
     u64 over = 0;
-    meth_calls<false>(M, B, i, W, lane, nullptr, MbiasDev{nullptr, nullptr}, over);
+    meth_calls<false, SNP>(M, B, i, W, lane, nullptr, MbiasDev{nullptr, nullptr}, over, rev);
 }
 
 // The twin of k_meth_pile with the M-bias tally: a grid sized by the CU count, every wave walks the alignments with the grid's stride.  The cells of the
 // first MB_LDS_CYCLES cycles are private to the block in LDS (a wave's 64 lanes are 64 cycles of one read: distinct cells) and reach HBM once, when the
 // block is done, as one 64-bit atomicAdd per non-zero cell; the count of valid mappings and the overflow count take the same way.  An LDS cell gets at
 // most one call per alignment and a batch has fewer than 2^32 alignments, so 32 bits hold it.
-__global__ __launch_bounds__(MB_BLOCK) void k_meth_pile_mbias(MethDev M, AlnBatch B, u64 *n_valid, MbiasDev D)
+template <bool SNP>
+__global__ __launch_bounds__(MB_BLOCK) void k_meth_pile_mbias(MethDev M, AlnBatch B, u64 *n_valid, MbiasDev D, u64 *rev)
 {
     __shared__ uint32_t s_tally[MB_LDS_CELLS];
     __shared__ u64 s_over;
@@ -218,7 +241,7 @@ __global__ __launch_bounds__(MB_BLOCK) void k_meth_pile_mbias(MethDev M, AlnBatc
         MethWindow W;
         if (!meth_window(M, B, (uint32_t)i, W)) continue;
         valid++;
-        meth_calls<true>(M, B, (uint32_t)i, W, lane, s_tally, D, over);
+        meth_calls<true, SNP>(M, B, (uint32_t)i, W, lane, s_tally, D, over, rev);
     }
     if (lane == 0 && valid) atomicAdd(&s_valid, valid);
     if (over) atomicAdd(&s_over, over);
@@ -235,7 +258,7 @@ __global__ __launch_bounds__(MB_BLOCK) void k_meth_pile_mbias(MethDev M, AlnBatc
     }
 }
 
-__global__ void k_meth_cpg(MethDev M)
+__global__ void k_meth_cpg(MethDev M, u64 *rev)
 {
     // every "CG" of every chromosome (occurrences cannot overlap): the G's counters move onto the C  (methratio.py:118-128)
     for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g + 1 < M.total; g += (u64)gridDim.x * blockDim.x) {
@@ -246,11 +269,39 @@ __global__ void k_meth_cpg(MethDev M)
         if (g + 1 >= M.chr_off[lo + 1]) continue;
         M.depth[g] += M.depth[g + 1]; M.meth[g] += M.meth[g + 1];
         M.depth[g + 1] = 0; M.meth[g + 1] = 0;
+        if (rev) { rev[g] += rev[g + 1]; rev[g + 1] = 0; }  // both halves at once: each sum stays below 2^32
     }
 }
 
+// What the table lists (bsx_meth_report_chr): the lowest depth, -z, the C/T-SNP mode (0 off, 1 correct, 2 skip) and the context mask (bit 0 CG, 1 CHG, 2 CHH,
+// 3 other; 0 and 0xF: no filter)
+struct RowRule {
+    uint32_t min_depth, ctx_mask;
+    int meth0, snp;
+};
+
+// Whether position k of the chromosome [g0, g0 + n) is covered, with its counters.  Integer tests only, in this order: depth, context class of the position's own
+// letter (C: '+' strand, G: '-' strand; another letter is in no class), then the SNP tests: mode 2 drops a position with any converted opposite-strand call, mode 1
+// one whose opposite-strand calls are all converted (its effective depth is 0), and both drop depth 0.
+__device__ __forceinline__ bool meth_covered(const MethDev &M, const u64 *rev, u64 g0, u64 n, u64 k, const RowRule &R, uint32_t &d, uint32_t &m, uint32_t &g, uint32_t &ga)
+{
+    d = M.depth[g0 + k]; m = M.meth[g0 + k]; g = ga = 0;
+    // (one flag, no early return: with a return per test the compiler's unrolled k_meth_count lost the depth of its first position in the SNP path)
+    bool ok = d >= R.min_depth;
+    if (ok && R.ctx_mask != 0 && R.ctx_mask != 0xF) {
+        const uint8_t l = M.ref[g0 + k];
+        ok = (l == 'C' || l == 'G') && ((R.ctx_mask >> meth_context(M.ref, g0 + k, g0, g0 + n, l == 'C')) & 1);
+    }
+    if (ok && R.snp) {
+        const u64 cell = rev[g0 + k];
+        ga = (uint32_t)cell; g = (uint32_t)(cell >> 32);
+        ok = d != 0 && (R.snp == 2 ? g == ga : (g != 0 || ga == 0));
+    }
+    return ok;
+}
+
 // table rows of one chromosome, in position order: blocks of 1024 positions are counted, scanned, and emitted
-__global__ __launch_bounds__(256) void k_meth_count(MethDev M, u64 g0, u64 n, uint32_t min_depth, int meth0, uint32_t *blk_rows, u64 *nc_nd)
+__global__ __launch_bounds__(256) void k_meth_count(MethDev M, u64 g0, u64 n, RowRule R, uint32_t *blk_rows, u64 *nc_nd, const u64 *rev)
 {
     __shared__ uint32_t s_rows;
     __shared__ u64 s_nc, s_nd;
@@ -260,27 +311,27 @@ __global__ __launch_bounds__(256) void k_meth_count(MethDev M, u64 g0, u64 n, ui
     for (int r = 0; r < 4; r++) {
         const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
         if (k >= n) continue;
-        const uint32_t d = M.depth[g0 + k], m = M.meth[g0 + k];
-        if (d < min_depth) continue;
-        nc++; nd += d;
-        if (m != 0 || meth0) rows++;
+        uint32_t d, m, g, ga;
+        const bool ok = meth_covered(M, rev, g0, n, k, R, d, m, g, ga);
+        nc += ok; nd += ok ? d : 0u;  // the raw depth in every mode
+        rows += ok && (m != 0 || R.meth0);
     }
     atomicAdd(&s_rows, rows); atomicAdd(&s_nc, nc); atomicAdd(&s_nd, nd);
     __syncthreads();
     if (threadIdx.x == 0) { blk_rows[blockIdx.x] = s_rows; if (s_nc) { atomicAdd(&nc_nd[0], s_nc); atomicAdd(&nc_nd[1], s_nd); } }
 }
 
-__global__ __launch_bounds__(256) void k_meth_emit(MethDev M, u64 g0, u64 n, uint32_t min_depth, int meth0, const uint32_t *blk_start, uint32_t *out_pos,
-                                                   uint32_t *out_depth, uint32_t *out_meth, u64 *out_ctx)
+__global__ __launch_bounds__(256) void k_meth_emit(MethDev M, u64 g0, u64 n, RowRule R, const uint32_t *blk_start, uint32_t *out_pos, uint32_t *out_depth,
+                                                   uint32_t *out_meth, u64 *out_ctx, uint32_t *out_rev_g, uint32_t *out_rev_ga, const u64 *rev)
 {
     __shared__ uint32_t s_wave[4];
     uint32_t base = blk_start[blockIdx.x];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int r = 0; r < 4; r++) {  // positions blockIdx*1024 + r*256 + thread: ascending with (r, thread)
         const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        uint32_t d = 0, m = 0;
+        uint32_t d = 0, m = 0, g = 0, ga = 0;
         bool row = false;
-        if (k < n) { d = M.depth[g0 + k]; m = M.meth[g0 + k]; row = d >= min_depth && (m != 0 || meth0); }
+        if (k < n) row = meth_covered(M, rev, g0, n, k, R, d, m, g, ga) && (m != 0 || R.meth0);
         const u64 bal = __ballot(row);
         if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
         __syncthreads();
@@ -289,6 +340,7 @@ __global__ __launch_bounds__(256) void k_meth_emit(MethDev M, u64 g0, u64 n, uin
         if (row) {
             const uint32_t o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
             out_pos[o] = (uint32_t)k; out_depth[o] = d; out_meth[o] = m;
+            if (R.snp) { out_rev_g[o] = g; out_rev_ga[o] = ga; }
             if (out_ctx) {  // refcr[i-2:i+3] with Python's slice rules, byte 7 = the letter at i.  For i < 2 the start i-2 is negative and counts from the
                             // chromosome's end: empty on a chromosome of at least five letters, but not below that ("CCGG": position 1 -> "G", "C": -> "C")
                 u64 ctx = 0;
@@ -315,6 +367,10 @@ struct bsx_meth {
     uint32_t *d_depth = nullptr, *d_meth = nullptr, *d_first = nullptr;
     uint32_t index_base = 0;
     uint32_t trim5 = 0, trim3 = 0;  // bsx_meth_set_cycle_trim
+    int snp = 0;                    // bsx_meth_set_ct_snp: 0 off, 1 correct, 2 skip
+    uint32_t ctx_mask = 0;          // bsx_meth_set_contexts
+    u64 *d_rev = nullptr;           // the packed opposite-strand counters, (total + 16) cells, or null when snp == 0
+    uint32_t *d_out_rev[2] = {nullptr, nullptr};  // rev_G / rev_GA of the rows of the last report, allocated with d_out when snp != 0
     u64 *d_mbias = nullptr;         // bsx_meth_set_mbias: MB_CELLS cells and the overflow counter, or null
     int n_cu = 0;
     hipStream_t stream = nullptr;
@@ -333,7 +389,7 @@ extern "C" void bsx_meth_destroy(bsx_meth *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     for (void *q : {(void *)m->d_ref, (void *)m->d_chr_off, (void *)m->d_counts, (void *)m->d_depth, (void *)m->d_meth, (void *)m->d_first, (void *)m->d_blk,
-                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias})
+                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias, (void *)m->d_rev, (void *)m->d_out_rev[0], (void *)m->d_out_rev[1]})
         if (q) (void)hipFree(q);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
@@ -404,9 +460,13 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
         if (m->d_first) hipLaunchKernelGGL(k_meth_first, dim3((n + 255) / 256), dim3(256), 0, m->stream, M, B);
         if (m->d_mbias) {  // the grid comes from the CU count; a batch too small to give every wave an alignment gets fewer blocks (fewer flushes)
             const unsigned waves = MB_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * MB_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
-            hipLaunchKernelGGL(k_meth_pile_mbias, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, m->d_counts, MbiasDev{m->d_mbias, m->d_mbias + MB_CELLS});
-        } else
-            hipLaunchKernelGGL(k_meth_pile, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts);
+            const MbiasDev D{m->d_mbias, m->d_mbias + MB_CELLS};
+            if (m->d_rev) hipLaunchKernelGGL(k_meth_pile_mbias<true>, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, m->d_counts, D, m->d_rev);
+            else hipLaunchKernelGGL(k_meth_pile_mbias<false>, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, m->d_counts, D, m->d_rev);
+        } else if (m->d_rev)
+            hipLaunchKernelGGL(k_meth_pile<true>, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts, m->d_rev);
+        else
+            hipLaunchKernelGGL(k_meth_pile<false>, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts, m->d_rev);
         chk(hipGetLastError());
         chk(hipStreamSynchronize(m->stream));
         m->index_base += n;
@@ -437,6 +497,33 @@ extern "C" int bsx_meth_set_mbias(bsx_meth *m, int on)
     hipError_t e = hipMemsetAsync(m->d_mbias, 0, (MB_CELLS + 1) * 8, m->stream);  // on the handle's stream: it does not wait for the null stream
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
     if (e != hipSuccess) { (void)hipFree(m->d_mbias); m->d_mbias = nullptr; HIP_TRY(e); }
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_set_ct_snp(bsx_meth *m, int mode)
+{
+    if (!m || mode < 0 || mode > 2) return BSX_ERR_ARG;
+    if ((mode != 0) == (m->snp != 0)) { m->snp = mode; return BSX_OK; }  // 1 <-> 2 at any time: the counters are the same
+    if (m->index_base) { g_bsx_err = "bsx_meth_set_ct_snp on or off after alignments have been added"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!mode) {
+        if (m->d_rev) (void)hipFree(m->d_rev);
+        m->d_rev = nullptr; m->snp = 0;
+        return BSX_OK;
+    }
+    const size_t bytes = (size_t)(m->chr_off.back() + 16) * 8;
+    if (hipMalloc((void **)&m->d_rev, bytes) != hipSuccess) { (void)hipGetLastError(); m->d_rev = nullptr; return BSX_ERR_NOMEM; }
+    hipError_t e = hipMemsetAsync(m->d_rev, 0, bytes, m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) { (void)hipFree(m->d_rev); m->d_rev = nullptr; HIP_TRY(e); }
+    m->snp = mode;
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_set_contexts(bsx_meth *m, uint32_t mask)
+{
+    if (!m || mask > 0xF) return BSX_ERR_ARG;
+    m->ctx_mask = mask;
     return BSX_OK;
 }
 
@@ -496,7 +583,7 @@ extern "C" int bsx_meth_combine_cpg(bsx_meth *m)
 {
     if (!m) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
-    hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev());
+    hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev(), m->d_rev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m->stream));
     return BSX_OK;
@@ -530,7 +617,8 @@ extern "C" int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth
     HIP_TRY(hipMemsetAsync(m->d_counts + 1, 0, 16, m->stream));
     HIP_TRY(hipMemsetAsync(m->d_blk + nblk, 0, 4, m->stream));
     const MethDev M = m->dev();
-    hipLaunchKernelGGL(k_meth_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, min_depth, meth0, m->d_blk, m->d_counts + 1);
+    const RowRule R{min_depth, m->ctx_mask, meth0, m->snp};
+    hipLaunchKernelGGL(k_meth_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk, m->d_counts + 1, m->d_rev);
     HIP_TRY(hipGetLastError());
     size_t need = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
@@ -540,17 +628,21 @@ extern "C" int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth
     HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipMemcpyAsync(cnt, m->d_counts + 1, 16, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    if (rows > m->out_cap) {
+    if (rows > m->out_cap || (m->snp && rows && !m->d_out_rev[0])) {
         for (int k = 0; k < 3; k++) { if (m->d_out[k]) (void)hipFree(m->d_out[k]); m->d_out[k] = nullptr; }
+        for (int k = 0; k < 2; k++) { if (m->d_out_rev[k]) (void)hipFree(m->d_out_rev[k]); m->d_out_rev[k] = nullptr; }
         if (m->d_ctx) (void)hipFree(m->d_ctx);
         m->d_ctx = nullptr;
+        const size_t cap = std::max<size_t>(rows, m->out_cap);
         m->out_cap = 0;
-        for (int k = 0; k < 3; k++) HIP_TRY(hipMalloc((void **)&m->d_out[k], (size_t)rows * 4));
-        HIP_TRY(hipMalloc((void **)&m->d_ctx, (size_t)rows * 8));
-        m->out_cap = rows;
+        for (int k = 0; k < 3; k++) HIP_TRY(hipMalloc((void **)&m->d_out[k], cap * 4));
+        if (m->snp) for (int k = 0; k < 2; k++) HIP_TRY(hipMalloc((void **)&m->d_out_rev[k], cap * 4));
+        HIP_TRY(hipMalloc((void **)&m->d_ctx, cap * 8));
+        m->out_cap = cap;
     }
     if (rows) {
-        hipLaunchKernelGGL(k_meth_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, min_depth, meth0, m->d_blk_start, m->d_out[0], m->d_out[1], m->d_out[2], m->d_ctx);
+        hipLaunchKernelGGL(k_meth_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk_start, m->d_out[0], m->d_out[1], m->d_out[2], m->d_ctx,
+                           m->d_out_rev[0], m->d_out_rev[1], m->d_rev);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(m->stream));
     }
@@ -568,6 +660,17 @@ extern "C" int bsx_meth_fetch_rows(bsx_meth *m, uint32_t *pos, uint32_t *depth, 
     HIP_TRY(hipMemcpy(pos, m->d_out[0], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(depth, m->d_out[1], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(meth, m->d_out[2], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_fetch_rows_snp(bsx_meth *m, uint32_t *rev_g, uint32_t *rev_ga)
+{
+    if (!m || !rev_g || !rev_ga) return BSX_ERR_ARG;
+    if (!m->snp) { g_bsx_err = "the C/T-SNP mode is off (bsx_meth_set_ct_snp)"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!m->last_rows) return BSX_OK;
+    HIP_TRY(hipMemcpy(rev_g, m->d_out_rev[0], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rev_ga, m->d_out_rev[1], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -654,11 +757,13 @@ static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const ui
     struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
     FILE *f = closer.f;
     if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-    fputs("chr\tpos\tstrand\tcontext\tratio\ttotal_C\tmethy_C\tCI_lower\tCI_upper\n", f);
+    const bool snp = m->snp != 0;  // C/T-SNP mode: the 12-column table of later BSMAP releases
+    fputs(snp ? "chr\tpos\tstrand\tcontext\tratio\teff_CT_count\tC_count\tCT_count\trev_G_count\trev_GA_count\tCI_lower\tCI_upper\n"
+              : "chr\tpos\tstrand\tcontext\tratio\ttotal_C\tmethy_C\tCI_lower\tCI_upper\n", f);
     u64 nc = 0, nd = 0;
     int rc = BSX_OK;
     const double z95 = 1.96, z95sq = 1.96 * 1.96;
-    std::vector<uint32_t> pos, dep, met; std::vector<u64> ctx;
+    std::vector<uint32_t> pos, dep, met, rvg, rvga; std::vector<u64> ctx;
     std::string buf;
     for (uint32_t k = 0; k < n_order && rc == BSX_OK; k++) {
         const uint32_t c = order[k];
@@ -671,6 +776,11 @@ static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const ui
         pos.resize(rows); dep.resize(rows); met.resize(rows); ctx.resize(rows);
         rc = bsx_meth_fetch_rows(m, pos.data(), dep.data(), met.data());
         if (rc) break;
+        if (snp) {
+            rvg.resize(rows); rvga.resize(rows);
+            rc = bsx_meth_fetch_rows_snp(m, rvg.data(), rvga.data());
+            if (rc) break;
+        }
         if (hipMemcpy(ctx.data(), m->d_ctx, (size_t)rows * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = BSX_ERR_DEVICE; break; }
         const char *name = chr_names ? chr_names[c] : m->names[c].c_str();
         // rows are formatted by a pool of threads, each a contiguous range, and written in order
@@ -679,11 +789,12 @@ static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const ui
         auto fmt = [&](unsigned t) {
             std::string &o = parts[t];
             const size_t lo = (size_t)rows * t / nt, hi = (size_t)rows * (t + 1) / nt;
-            o.reserve((hi - lo) * 56);
+            o.reserve((hi - lo) * (snp ? 72 : 56));
             char line[256];
             for (size_t i = lo; i < hi; i++) {
-                const double d = dep[i], mm = met[i];
-                const double ratio = mm / d;
+                // with the mode on, d is the effective depth: the share of the raw depth that the opposite strand shows to be a real C
+                const double d = (snp && rvg[i] != rvga[i]) ? ((double)dep[i] * rvg[i]) / rvga[i] : (double)dep[i], mm = met[i];
+                const double ratio = snp ? (mm < d ? mm : d) / d : mm / d;
                 const double pmid = ratio + z95sq / (2 * d);
                 const double sd = z95 * pow(ratio * (1 - ratio) / d + z95sq / (4 * d * d), 0.5);
                 const double norminator = 1 + z95sq / d;
@@ -691,8 +802,10 @@ static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const ui
                 for (; nb < 5; nb++) { const char ch = (char)((ctx[i] >> (8 * nb)) & 0xff); if (!ch) break; cx[nb] = ch; }
                 cx[nb] = 0;
                 const char letter = (char)(ctx[i] >> 56);
-                const int w = snprintf(line, sizeof(line), "%s\t%u\t%c\t%s\t%.3f\t%u\t%u\t%.3f\t%.3f\n", name, pos[i] + 1, letter == 'C' ? '+' : '-', cx, ratio, dep[i], met[i],
-                                       (pmid - sd) / norminator, (pmid + sd) / norminator);
+                const int w = snp ? snprintf(line, sizeof(line), "%s\t%u\t%c\t%s\t%.3f\t%.2f\t%u\t%u\t%u\t%u\t%.3f\t%.3f\n", name, pos[i] + 1, letter == 'C' ? '+' : '-', cx, ratio,
+                                         d, met[i], dep[i], rvg[i], rvga[i], (pmid - sd) / norminator, (pmid + sd) / norminator)
+                                  : snprintf(line, sizeof(line), "%s\t%u\t%c\t%s\t%.3f\t%u\t%u\t%.3f\t%.3f\n", name, pos[i] + 1, letter == 'C' ? '+' : '-', cx, ratio, dep[i], met[i],
+                                             (pmid - sd) / norminator, (pmid + sd) / norminator);
                 o.append(line, (size_t)w);
             }
         };

@@ -13,7 +13,10 @@ fallback: without the library and a gfx950 device this fails.
 Differences from the reference: SAM and BAM files are read directly (numeric flags: 0x4 = 'u', 0x100 = 's', 0x2 = 'P' of
 `samtools view -X`; BGZF through zlib), no samtools is spawned and `-s` is accepted and ignored.  Extensions: `--mbias=FILE`
 writes the M-bias table (methylated / all calls per sequencing cycle, strand and cytosine context, tallied by the pile-up
-kernel), `--trim-5p=N` / `--trim-3p=N` ignore the calls of the first / last N cycles of every read."""
+kernel), `--trim-5p=N` / `--trim-3p=N` ignore the calls of the first / last N cycles of every read.  From later BSMAP releases:
+`-i/--ct-snp {no-action,correct,skip}` counts, in the same pile-up, what the reads of the other reference strand show over every C (G: intact, A: a C->T
+SNP) and corrects the depth by that share or skips the position, with their 12-column table (default here: no-action, the table above); `-x/--context
+CG,CHG,CHH` lists the cytosines of those contexts only."""
 import ctypes as C
 import sys
 import time
@@ -25,6 +28,8 @@ from . import lib, _check
 MBIAS_CYCLES = 1024  # BSX_MBIAS_CYCLES of include/bsx.h: bsx_meth_mbias_fetch fills [4][4][MBIAS_CYCLES][2] uint64
 MBIAS_STRANDS = ("++", "-+", "+-", "--")
 MBIAS_CONTEXTS = ("CG", "CHG", "CHH", "CN")
+CT_SNP_MODES = ("no-action", "correct", "skip")  # bsx_meth_set_ct_snp modes 0, 1, 2
+CONTEXT_BITS = {"CG": 1, "CHG": 2, "CHH": 4}      # bsx_meth_set_contexts
 
 def _bind():
     L = lib()
@@ -46,6 +51,9 @@ def _bind():
     L.bsx_meth_set_mbias.argtypes = [vp, i32]
     L.bsx_meth_mbias_fetch.argtypes = [vp, vp, vp]
     L.bsx_meth_write_mbias.argtypes = [vp, C.c_char_p]
+    L.bsx_meth_set_ct_snp.argtypes = [vp, i32]
+    L.bsx_meth_set_contexts.argtypes = [vp, u32]
+    L.bsx_meth_fetch_rows_snp.argtypes = [vp, vp, vp]
     L._meth_bound = True
     return L
 
@@ -75,8 +83,12 @@ def load_reference(path, chroms):
 
 
 def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=False, rm_dup=False, trim_fillin=2, combine_CpG=False,
-        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0):
-    """returns the summary line the reference prints on stdout"""
+        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0, ct_snp="no-action", context=None):
+    """returns the summary line the reference prints on stdout; ct_snp: one of CT_SNP_MODES, context: names of CONTEXT_BITS to list (None: all)"""
+    if ct_snp not in CT_SNP_MODES:
+        raise ValueError("ct_snp must be one of %s" % ", ".join(CT_SNP_MODES))
+    if context is not None and (not context or any(x not in CONTEXT_BITS for x in context)):
+        raise ValueError("context must be a non-empty subset of %s" % ", ".join(CONTEXT_BITS))
     def disp(txt):
         if not quiet:
             sys.stderr.write("@ %s: %s\n" % (time.asctime(), txt))
@@ -90,6 +102,10 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
             _check(L.bsx_meth_set_mbias(h, 1))
         if trim5 or trim3:
             _check(L.bsx_meth_set_cycle_trim(h, trim5, trim3))
+        if ct_snp != "no-action":
+            _check(L.bsx_meth_set_ct_snp(h, CT_SNP_MODES.index(ct_snp)))
+        if context is not None:
+            _check(L.bsx_meth_set_contexts(h, sum(CONTEXT_BITS[x] for x in set(context))))
         for infile in infiles:
             disp("reading %s ..." % infile)
             ext = infile[-4:].upper()
@@ -114,8 +130,8 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
         L.bsx_meth_destroy(h)
 
 
-def main(argv=None):
-    """command line with the reference's option letters (methratio.py:3-17)"""
+def build_parser():
+    """the command line with the reference's option letters (methratio.py:3-17) and the extensions"""
     import argparse
     ap = argparse.ArgumentParser(prog="methratio", description="methylation ratios from BSMAP mapping files (BSP, SAM or BAM), pile-up on the GPU")
     ap.add_argument("-o", "--out", dest="outfile", required=True, help="table to write")
@@ -139,11 +155,24 @@ def main(argv=None):
     ap.add_argument("--mbias", dest="mbias", default=None, metavar="FILE", help="write the M-bias table: methylated / all calls per read cycle, strand and context (extension)")
     ap.add_argument("--trim-5p", dest="trim5", type=cycles, default=0, metavar="N", help="ignore the calls of the first N sequencing cycles of every read (extension, default 0)")
     ap.add_argument("--trim-3p", dest="trim3", type=cycles, default=0, metavar="N", help="ignore the calls of the last N sequencing cycles of every read (extension, default 0)")
+    def contexts(txt):
+        names = txt.split(",")
+        if any(x not in CONTEXT_BITS for x in names):
+            raise argparse.ArgumentTypeError("a comma-separated list of CG, CHG, CHH is expected")
+        return names
+    ap.add_argument("-i", "--ct-snp", dest="ct_snp", choices=CT_SNP_MODES, default="no-action",
+                    help="C/T SNPs, told from unmethylated C by the reads of the other strand: correct the depth, skip the position, or no-action (default)")
+    ap.add_argument("-x", "--context", dest="context", type=contexts, default=None, metavar="CG,CHG,CHH", help="list cytosines of these contexts only (default: all)")
     ap.add_argument("infiles", nargs="+", help="mapping files written by bsmap: *.sam / *.bam by their format, anything else as BSP")
-    o = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    """the command line: parses argv (default sys.argv[1:]) and prints run()'s summary line"""
+    o = build_parser().parse_args(argv)
     sys.stdout.write(run(o.reffile, o.infiles, o.outfile, chroms=o.chroms.split(",") if o.chroms else None, unique=o.unique, pair=o.pair, meth0=o.meth0,
                          rm_dup=o.rm_dup, trim_fillin=o.trim_fillin, combine_CpG=o.combine_CpG, min_depth=o.min_depth, device=o.device, quiet=o.quiet,
-                         mbias=o.mbias, trim5=o.trim5, trim3=o.trim3))
+                         mbias=o.mbias, trim5=o.trim5, trim3=o.trim3, ct_snp=o.ct_snp, context=o.context))
 
 
 if __name__ == "__main__":

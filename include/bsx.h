@@ -366,12 +366,30 @@ int bsx_meth_mbias_fetch(bsx_meth *m, uint64_t *cells /* [4][4][BSX_MBIAS_CYCLES
  * 1-based cycle up to the last cycle with a call in any group, ratio "%.3f" or NA at depth 0; then "# total <context> <meth> <depth> <ratio>"
  * per context (tab-separated, over the cells) and "# calls beyond cycle 1024: <n>".  BSX_ERR_STATE when the M-bias is off */
 int bsx_meth_write_mbias(bsx_meth *m, const char *path);
+/* C/T-SNP correction (extension; -i of later BSMAP releases): a genomic C->T SNP looks like an unmethylated C on the strand that carries the C, and
+ * the reads of the OTHER reference strand tell the two apart: G over an intact C, A over a SNP.  mode 0 off, 1 correct, 2 skip; another value is
+ * BSX_ERR_ARG.  A non-zero mode allocates (zeroed) one uint64 per reference letter — low word rev_GA, high word rev_G — and every later add makes, beside
+ * the calls of depth / meth and under the same window and cycle mask, one 64-bit atomic add per opposite-strand letter: a "+?" read over a reference G
+ * that shows G adds to rev_G and rev_GA, one that shows A to rev_GA; a "-?" read over a reference C likewise with C and T.  bsx_meth_combine_cpg folds
+ * the cells like depth / meth.  Rows (bsx_meth_report_chr, bsx_meth_write_table), tested in this order: depth >= min_depth; the context filter; mode 2
+ * drops a position with rev_G != rev_GA, mode 1 one with rev_G == 0 < rev_GA, both one with depth 0; then n_covered += 1 and sum_depth += depth (the raw
+ * depth); then methylated > 0 or meth0.  The table gets the columns chr pos strand context ratio eff_CT_count C_count CT_count rev_G_count rev_GA_count
+ * CI_lower CI_upper with eff = rev_G != rev_GA ? depth * rev_G / rev_GA : depth ("%.2f"), ratio = min(methylated, eff) / eff and the Wilson interval over
+ * eff.  Going between 0 and non-zero is BSX_ERR_STATE once alignments have been added, between 1 and 2 is allowed at any time (the counters are the
+ * same: one pile-up can write both tables); BSX_ERR_NOMEM when the array cannot be had; mode 0 before any add frees it. */
+int bsx_meth_set_ct_snp(bsx_meth *m, int mode);
+/* Context filter (extension; -x of later BSMAP releases) of the later report / write calls, at any time: bit 0 CG, 1 CHG, 2 CHH, 3 other (the classes
+ * of the M-bias tally, from the position's own letter: C looks right, G looks left).  A position whose class is not in the mask is not covered: no
+ * row, not in n_covered / sum_depth.  0 and 0xF: no filter.  mask > 0xF is BSX_ERR_ARG. */
+int bsx_meth_set_contexts(bsx_meth *m, uint32_t mask);
 int bsx_meth_combine_cpg(bsx_meth *m);                      /* -g, methratio.py:118-128 */
 int bsx_meth_valid_mappings(bsx_meth *m, uint64_t *n);      /* "total %d valid mappings" */
 /* rows of one chromosome's table in position order: positions with depth >= min_depth and (methylated > 0 or meth0);
  * n_covered / sum_depth count every position with depth >= min_depth (methratio.py:138-142) */
 int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth, int meth0, uint32_t *n_rows, uint64_t *n_covered, uint64_t *sum_depth);
 int bsx_meth_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *depth, uint32_t *meth);   /* the rows of the last report_chr */
+/* rev_G / rev_GA of the same rows; BSX_ERR_STATE when the C/T-SNP mode is 0 */
+int bsx_meth_fetch_rows_snp(bsx_meth *m, uint32_t *rev_g, uint32_t *rev_ga);
 /* the whole table file of methratio.py:130-151 (header, chromosomes in the given order — the reference sorts the names —,
  * ratio and Wilson interval with the reference's arithmetic, "%.3f"); returns the counts of the summary line */
 int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_order, const uint32_t *order, const char *const *chr_names, uint32_t min_depth, int meth0,

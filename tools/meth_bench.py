@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Throughput of the methylation pile-up kernels (bsx_meth_add) on an hg38-sized random reference: N alignments of L nt
 at uniform positions, all four strands, reads = reference letters with bisulfite-like conversion.  Prints one JSON line;
-run under `rocprofv3 --kernel-trace --stats` for the kernel-only times.  usage: meth_bench.py [--aln 16777216] [--len 100]"""
+run under `rocprofv3 --kernel-trace --stats` for the kernel-only times.  `--ct-snp correct|skip` turns the C/T-SNP mode on (one more 64-bit cell per
+reference letter, reverse calls in the pile-up, the SNP tests in the report).  usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +15,7 @@ def main():
     ap.add_argument("--aln", type=int, default=16 << 20)
     ap.add_argument("--len", type=int, default=100)
     ap.add_argument("--genome", type=float, default=1.0)
+    ap.add_argument("--ct-snp", dest="ct_snp", choices=MR.CT_SNP_MODES, default="no-action")
     a = ap.parse_args()
     L = MR._bind()
     rng = np.random.default_rng(1)
@@ -22,6 +24,8 @@ def main():
                                                 46709983, 50818468, 156040895, 57227415)], np.uint64)
     h = C.c_void_p()
     B._check(L.bsx_meth_create(len(lens), lens.ctypes.data, 1, 0, C.byref(h)))
+    if a.ct_snp != "no-action":
+        B._check(L.bsx_meth_set_ct_snp(h, MR.CT_SNP_MODES.index(a.ct_snp)))
     letters = np.frombuffer(b"ACGT", np.uint8)
     chunks = []
     for c, n in enumerate(lens.tolist()):
@@ -57,7 +61,7 @@ def main():
         rows += nr.value; cov += cv.value
     dt_rep = time.perf_counter() - t1
     L.bsx_meth_destroy(h)
-    print(json.dumps({"alignments": n, "read_len": ln, "add_s_incl_pcie": round(dt, 3), "alignments_per_s_incl_pcie": round(n / dt),
+    print(json.dumps({"alignments": n, "read_len": ln, "ct_snp": a.ct_snp, "add_s_incl_pcie": round(dt, 3), "alignments_per_s_incl_pcie": round(n / dt),
                       "report_s_all_chromosomes": round(dt_rep, 3), "rows": rows, "covered": cov, "genome_bp": int(lens.sum())}))
 
 
