@@ -73,6 +73,7 @@ EXPORTS = [
     "bsx_meth_report_chr", "bsx_meth_fetch_rows", "bsx_meth_add_file", "bsx_meth_write_table", "bsx_meth_create_from_fasta", "bsx_meth_n_chr", "bsx_meth_chr_name",
     "bsx_meth_set_cycle_trim", "bsx_meth_set_mbias", "bsx_meth_mbias_fetch", "bsx_meth_write_mbias",
     "bsx_meth_set_ct_snp", "bsx_meth_set_contexts", "bsx_meth_fetch_rows_snp",
+    "bsx_meth_region_tile", "bsx_meth_regions", "bsx_meth_bins", "bsx_meth_write_regions", "bsx_meth_write_wig",
 ]
 
 

@@ -11,6 +11,7 @@
 // With the C/T-SNP mode on (bsx_meth_set_ct_snp, an extension: -i of later BSMAP releases) the same pile-up pass also counts, per reference position, what the reads
 // of the OTHER reference strand show there (G over an intact C, A over a C->T SNP), and the row selection and the table use those two counters.
 //   k_meth_count / k_meth_emit   ordered compaction of the positions the table will list
+//   k_meth_bins / k_meth_regions   pooled sums per fixed bin (wiggle track, -w / -b) and per interval (BED, --regions) under the table's row rule
 // The host side (bsmap_amd/methratio.py) parses the option surface, the FASTA and the BSP / SAM lines, and prints the
 // table with the reference's arithmetic.  All counters are integers: results are exact.
 #include <fcntl.h>
@@ -38,6 +39,7 @@
 #include "bsx_cpus.h"
 #include "bsx_internal.h"
 #include "bsx_meth_parse.h"
+#include "bsx_meth_tiles.h"
 
 namespace {
 
@@ -354,6 +356,141 @@ __global__ __launch_bounds__(256) void k_meth_emit(MethDev M, u64 g0, u64 n, Row
         base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
         __syncthreads();
     }
+}
+
+// ---- pooled methylation per bin and per interval (bsx_meth_bins, bsx_meth_regions) ----
+// A position is a site when meth_covered says so and its raw depth is above 0 (-z plays no part).  A site gives five values: 1, m, d, the effective depth
+// e in units of 1/65536 (d << 16, or with the SNP mode on and g != ga the table's own double expression d * g / ga, scaled and rounded to nearest-even) and
+// mc = min(m << 16, e), the table's min(mm, d) clip in those units.  All integers: sums of them are the same bits in any order.
+// The one place that forms them; both kernels below call it, and it calls meth_covered for the row rule.  SNP = false: R.snp is 0, rev is not read, and the
+// double division is not in the code.
+template <bool SNP>
+__device__ __forceinline__ bool meth_site(const MethDev &M, const u64 *rev, u64 g0, u64 n, u64 k, const RowRule &R, uint32_t &d, uint32_t &m, u64 &e, u64 &mc)
+{
+    uint32_t g, ga;
+    const bool ok = meth_covered(M, rev, g0, n, k, R, d, m, g, ga) && d != 0;
+    e = (u64)d << 16;
+    if (SNP && ok && g != ga) e = (u64)rint((((double)d * g) / ga) * 65536.0);
+    const u64 m16 = (u64)m << 16;
+    mc = m16 < e ? m16 : e;
+    return ok;
+}
+
+// Position-major: a block takes rounds * 256 consecutive positions of the chromosome [g0, g0 + n), a wave 64 consecutive ones per round.  The five values
+// are reduced by bin inside the wave (a segmented reduction: the lanes' bins ascend, a lane adds its neighbour at distance 1, 2, .. 32 while that one is
+// in the same bin, and the first lane of every bin ends with the bin's sum; with B >= 64 that is one or two segments, with B = 1 sixty-four), then
+// across the waves in an LDS table of the bins the block touches, and reach HBM once per block and bin: plain stores for a bin that lies inside the
+// block's positions (no other block touches it), 64-bit atomic adds for the one or two it shares with its neighbours.  A wave step without a site
+// (the common case on sparse data) skips all of it.  LDS: ((P - 1) / B + 2) x 5 x 8 bytes, at most 40 KiB (B = 1, P = 1 024), given at the launch.
+template <bool SNP>
+__global__ __launch_bounds__(256) void k_meth_bins(MethDev M, u64 g0, u64 n, RowRule R, const u64 *rev, uint32_t B, uint32_t rounds, u64 *bins)
+{
+    extern __shared__ u64 s_bins[];  // [bins of the block][N, M, D, E, MC]
+    const u64 P = (u64)rounds * 256, k0 = (u64)blockIdx.x * P, k1 = k0 + P < n ? k0 + P : n;  // k0 < n: the grid is ceil(n / P)
+    const u64 bin_lo = k0 / B, rem0 = k0 % B;
+    const uint32_t nb = (uint32_t)((k1 - 1) / B - bin_lo) + 1;
+    for (uint32_t t = threadIdx.x; t < nb * 5; t += 256) s_bins[t] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (uint32_t r0 = 0; r0 < rounds; r0 += 4) {  // (rounds is a multiple of 4)
+        // the raw depths of four rounds first, so that a wave has four loads in flight, not one; a wave step whose depths are all zero holds no site (the
+        // site's own definition) and ends here, the others go through meth_site, which finds the depth in the cache
+        uint32_t ahead[4];
+        for (int q = 0; q < 4; q++) { const u64 ka = k0 + (u64)(r0 + q) * 256 + threadIdx.x; ahead[q] = ka < k1 ? M.depth[g0 + ka] : 0u; }
+        for (int q = 0; q < 4; q++) {
+            if (!__ballot(ahead[q] != 0)) continue;  // (uniform over the wave)
+            const uint32_t o = (r0 + q) * 256 + threadIdx.x;
+            const u64 k = k0 + o;
+            uint32_t d = 0, m = 0;
+            u64 e = 0, mc = 0;
+            bool ok = false;
+            if (k < k1) ok = meth_site<SNP>(M, rev, g0, n, k, R, d, m, e, mc);
+            if (!__ballot(ok)) continue;
+            // the lane's bin, counted from the block's first: (rem0 + o) / B without a 64-bit division (the sum is below 2 B whenever it is above 2^32)
+            const u64 t = rem0 + (k < k1 ? o : (uint32_t)(k1 - 1 - k0));  // lanes behind the end hold zeroes in the last position's bin
+            const uint32_t key = t <= 0xffffffffull ? (uint32_t)t / B : 1u;
+            uint32_t vn = ok;
+            u64 vm = ok ? m : 0u, vd = ok ? d : 0u, ve = ok ? e : 0ull, vmc = ok ? mc : 0ull;
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t ko = __shfl_down(key, off);
+                const uint32_t an = __shfl_down(vn, off);
+                const u64 am = __shfl_down(vm, off), ad = __shfl_down(vd, off), amc = __shfl_down(vmc, off);
+                u64 ae = 0;
+                if (SNP) ae = __shfl_down(ve, off);
+                if (lane + off < 64 && ko == key) { vn += an; vm += am; vd += ad; vmc += amc; ve += ae; }
+            }
+            const uint32_t kp = __shfl_up(key, 1);
+            if ((lane == 0 || kp != key) && vn) {
+                if (!SNP) ve = vd << 16;  // the sum of d << 16
+                u64 *c = &s_bins[key * 5];
+                atomicAdd(&c[0], (u64)vn); atomicAdd(&c[1], vm); atomicAdd(&c[2], vd); atomicAdd(&c[3], ve); atomicAdd(&c[4], vmc);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < nb; t += 256) {
+        const u64 *c = &s_bins[t * 5];
+        if (!c[0]) continue;  // no site: the cells in HBM stay zero
+        const u64 b = bin_lo + t, lo = b * B, hi = lo + B < n ? lo + B : n;
+        u64 *out = bins + b * 5;
+        if (lo >= k0 && hi <= k1) { for (int q = 0; q < 5; q++) out[q] = c[q]; }
+        else { for (int q = 0; q < 5; q++) atomicAdd(&out[q], c[q]); }
+    }
+}
+
+// Interval-major: one wave per tile of at most bsx_meth_tiles::TILE positions (the host cuts the intervals: bsx_meth_tiles.h), the lanes stride the
+// tile, so a wave's loads are 64 consecutive cells.  The context class near a tile's or an interval's border is the chromosome's: meth_context gets the
+// chromosome's bounds through meth_site.  Lane 0 of the wave holds the tile's sums: where the tile is the interval's only one it writes them with plain
+// stores.  The tiles of a longer interval follow each other in the tile list, so the block's REGION_WAVES waves mostly hold tiles of one interval: their
+// sums meet in LDS, and the first wave of each run of equal intervals adds the run's total with five 64-bit atomic adds into the interval's zeroed
+// cells (one set per block and interval, not one per tile: the five cells of an interval share a cache line, and a 2^27-nt interval has 65 536 tiles).
+// Blocks of 4 waves where the launch is mostly short intervals (every wave of a block waits for its slowest at the barrier), of 16 where it is mostly
+// long ones (a quarter of the adds): the host chooses per launch.
+template <bool SNP, int REGION_WAVES>
+__global__ __launch_bounds__(REGION_WAVES * 64) void k_meth_regions(MethDev M, RowRule R, const u64 *rev, const bsx_meth_tiles::Tile *tiles, uint32_t n_tiles,
+                                                                   const uint32_t *iv_chr, const uint32_t *iv_start, u64 *sums)
+{
+    __shared__ u64 s_part[REGION_WAVES][5];
+    __shared__ uint32_t s_iv[REGION_WAVES];  // the interval of the wave's tile where it has to be added, ~0 otherwise
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t t = blockIdx.x * REGION_WAVES + wv;
+    uint32_t shared_iv = ~0u;
+    if (t < n_tiles) {  // (uniform over the wave)
+        const bsx_meth_tiles::Tile T = tiles[t];
+        const uint32_t len = T.len & ~bsx_meth_tiles::SINGLE, c = iv_chr[T.iv];
+        const u64 g0 = M.chr_off[c], n = M.chr_off[c + 1] - g0, k0 = (u64)iv_start[T.iv] + T.off;  // the host has clipped the interval: k0 + len <= n
+        uint32_t vn = 0;
+        u64 vm = 0, vd = 0, ve = 0, vmc = 0;
+        for (uint32_t j0 = lane; j0 < len; j0 += 256) {  // four strides at a time: their raw depths first (four loads in flight); no site without depth
+            uint32_t ahead[4];
+            for (int q = 0; q < 4; q++) ahead[q] = j0 + 64 * q < len ? M.depth[g0 + k0 + j0 + 64 * q] : 0u;
+            for (int q = 0; q < 4; q++) {
+                if (!ahead[q]) continue;
+                uint32_t d, m;
+                u64 e, mc;
+                if (!meth_site<SNP>(M, rev, g0, n, k0 + j0 + 64 * q, R, d, m, e, mc)) continue;
+                vn++; vm += m; vd += d; vmc += mc;
+                if (SNP) ve += e;
+            }
+        }
+        for (int off = 32; off; off >>= 1) {
+            vn += __shfl_down(vn, off); vm += __shfl_down(vm, off); vd += __shfl_down(vd, off); vmc += __shfl_down(vmc, off);
+            if (SNP) ve += __shfl_down(ve, off);
+        }
+        if (!SNP) ve = vd << 16;
+        if (lane == 0) {
+            if (T.len & bsx_meth_tiles::SINGLE) { u64 *out = sums + (u64)T.iv * 5; out[0] = vn; out[1] = vm; out[2] = vd; out[3] = ve; out[4] = vmc; }
+            else { shared_iv = T.iv; s_part[wv][0] = vn; s_part[wv][1] = vm; s_part[wv][2] = vd; s_part[wv][3] = ve; s_part[wv][4] = vmc; }
+        }
+    }
+    if (lane == 0) s_iv[wv] = shared_iv;
+    __syncthreads();
+    if (lane != 0 || shared_iv == ~0u || (wv > 0 && s_iv[wv - 1] == shared_iv)) return;  // the first wave of a run of tiles of one interval goes on
+    u64 tot[5] = {0, 0, 0, 0, 0};
+    for (int w = wv; w < REGION_WAVES && s_iv[w] == shared_iv; w++) for (int q = 0; q < 5; q++) tot[q] += s_part[w][q];
+    if (!tot[0]) return;
+    u64 *out = sums + (u64)shared_iv * 5;
+    for (int q = 0; q < 5; q++) atomicAdd(&out[q], tot[q]);
 }
 
 }  // namespace
@@ -869,3 +1006,237 @@ extern "C" int bsx_meth_create_from_fasta(const char *path, const char *chroms_c
 
 extern "C" uint32_t bsx_meth_n_chr(const bsx_meth *m) { return m ? m->n_chr : 0; }
 extern "C" const char *bsx_meth_chr_name(const bsx_meth *m, uint32_t c) { return (m && c < m->names.size()) ? m->names[c].c_str() : ""; }
+
+// ---- pooled methylation per interval and per bin ----
+namespace {
+
+struct DevBuf {  // device memory that is freed on every way out
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    bool alloc(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; } return true; }
+};
+
+constexpr size_t REGION_CHUNK = (size_t)1 << 22;  // a launch takes intervals until it holds this many of them or of their tiles
+
+}  // namespace
+
+extern "C" uint32_t bsx_meth_region_tile(void) { return bsx_meth_tiles::TILE; }
+
+static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums)
+{
+    std::vector<uint32_t> cs(n), ce(n);  // the clipped intervals
+    for (uint32_t i = 0; i < n; i++) {
+        if (chr[i] >= m->n_chr || start[i] > end[i]) return BSX_ERR_ARG;
+        const u64 clen = m->chr_off[chr[i] + 1] - m->chr_off[chr[i]];
+        ce[i] = (uint32_t)std::min<u64>(end[i], clen);
+        cs[i] = std::min(start[i], ce[i]);
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    // launches: [a, b) of the intervals each
+    std::vector<uint32_t> cut_at(1, 0);
+    size_t max_iv = 0, max_tiles = 0;
+    for (uint32_t a = 0; a < n;) {
+        uint32_t b = a;
+        size_t nt = 0;
+        while (b < n && (size_t)(b - a) < REGION_CHUNK && nt < REGION_CHUNK) nt += (size_t)bsx_meth_tiles::n_tiles(ce[b] - cs[b]), b++;
+        max_iv = std::max<size_t>(max_iv, b - a); max_tiles = std::max(max_tiles, nt);
+        cut_at.push_back(b);
+        a = b;
+    }
+    DevBuf d_tiles, d_chr, d_start, d_sums;
+    if (!d_tiles.alloc(max_tiles * sizeof(bsx_meth_tiles::Tile)) || !d_chr.alloc(max_iv * 4) || !d_start.alloc(max_iv * 4) || !d_sums.alloc(max_iv * 40)) {
+        g_bsx_err = "bsx_meth_regions: no device memory for the intervals"; return BSX_ERR_NOMEM;
+    }
+    const MethDev M = m->dev();
+    const RowRule R{min_depth, m->ctx_mask, 1, m->snp};
+    std::vector<bsx_meth_tiles::Tile> tiles;
+    for (size_t q = 0; q + 1 < cut_at.size(); q++) {
+        const uint32_t a = cut_at[q], b = cut_at[q + 1];
+        tiles.clear();
+        for (uint32_t i = a; i < b; i++) bsx_meth_tiles::cut(i - a, ce[i] - cs[i], tiles);
+        HIP_TRY(hipMemsetAsync(d_sums.p, 0, (size_t)(b - a) * 40, m->stream));
+        if (!tiles.empty()) {
+            HIP_TRY(hipMemcpyAsync(d_tiles.p, tiles.data(), tiles.size() * sizeof(bsx_meth_tiles::Tile), hipMemcpyHostToDevice, m->stream));
+            HIP_TRY(hipMemcpyAsync(d_chr.p, chr + a, (size_t)(b - a) * 4, hipMemcpyHostToDevice, m->stream));
+            HIP_TRY(hipMemcpyAsync(d_start.p, cs.data() + a, (size_t)(b - a) * 4, hipMemcpyHostToDevice, m->stream));
+            const uint32_t nt = (uint32_t)tiles.size();
+            size_t in_long = 0;  // tiles of intervals of 64 tiles and more
+            for (uint32_t i = a; i < b; i++) { const size_t k = (size_t)bsx_meth_tiles::n_tiles(ce[i] - cs[i]); if (k >= 64) in_long += k; }
+            const bool wide = 2 * in_long > nt;
+            const unsigned waves = wide ? 16 : 4;
+            auto kernel = m->snp ? (wide ? k_meth_regions<true, 16> : k_meth_regions<true, 4>) : (wide ? k_meth_regions<false, 16> : k_meth_regions<false, 4>);
+            hipLaunchKernelGGL(kernel, dim3((nt + waves - 1) / waves), dim3(waves * 64), 0, m->stream, M, R, (const u64 *)m->d_rev, (const bsx_meth_tiles::Tile *)d_tiles.p, nt,
+                               (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, (u64 *)d_sums.p);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(sums + (size_t)a * 5, d_sums.p, (size_t)(b - a) * 40, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));  // (the host vectors are reused by the next launch)
+    }
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums)
+{
+    if (!m || (n && (!chr || !start || !end || !sums))) return BSX_ERR_ARG;
+    if (!n) return BSX_OK;
+    try {
+        return meth_regions(m, n, chr, start, end, min_depth, sums);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = "bsx_meth_regions: out of host memory"; return BSX_ERR_NOMEM;
+    }
+}
+
+extern "C" int bsx_meth_bins(bsx_meth *m, uint32_t chr, uint32_t bin, uint32_t min_depth, uint64_t n_bins_cap, uint64_t *sums, uint64_t *n_bins)
+{
+    if (!m || !n_bins || chr >= m->n_chr || !bin) return BSX_ERR_ARG;
+    const u64 g0 = m->chr_off[chr], n = m->chr_off[chr + 1] - g0, need = n / bin + 1;
+    *n_bins = need;
+    if (!sums || n_bins_cap < need) return BSX_ERR_ARG;
+    HIP_TRY(hipSetDevice(m->device));
+    DevBuf d_bins;
+    if (!d_bins.alloc((size_t)need * 40)) { g_bsx_err = "bsx_meth_bins: no device memory for the bins"; return BSX_ERR_NOMEM; }
+    HIP_TRY(hipMemsetAsync(d_bins.p, 0, (size_t)need * 40, m->stream));
+    if (n) {
+        // positions per block: 1 024 below B = 16 (the block's bin table is LDS), 4 096 from there on (fewer adds on the cells that wide bins share)
+        const uint32_t rounds = bin < 16 ? 4 : 16;
+        const u64 P = (u64)rounds * 256;
+        const size_t lds = (size_t)std::min<u64>(P, (P - 1) / bin + 2) * 40;
+        const MethDev M = m->dev();
+        const RowRule R{min_depth, m->ctx_mask, 1, m->snp};
+        if (m->snp) hipLaunchKernelGGL(k_meth_bins<true>, dim3((unsigned)((n + P - 1) / P)), dim3(256), lds, m->stream, M, g0, n, R, m->d_rev, bin, rounds, (u64 *)d_bins.p);
+        else hipLaunchKernelGGL(k_meth_bins<false>, dim3((unsigned)((n + P - 1) / P)), dim3(256), lds, m->stream, M, g0, n, R, m->d_rev, bin, rounds, (u64 *)d_bins.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(sums, d_bins.p, (size_t)need * 40, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return BSX_OK;
+}
+
+namespace {
+
+// the chromosomes in sorted name order: the table's
+std::vector<uint32_t> sorted_chromosomes(const bsx_meth *m)
+{
+    std::vector<uint32_t> o;
+    for (uint32_t c = 0; c < m->n_chr; c++) o.push_back(c);
+    std::sort(o.begin(), o.end(), [&](uint32_t a, uint32_t b) { return m->names[a] < m->names[b]; });
+    return o;
+}
+
+// `rows` lines formatted by a pool of host threads, each a contiguous range, appended to `f` in order (as write_table does)
+template <class Fmt>
+void format_rows(FILE *f, size_t rows, size_t reserve_per_row, Fmt fmt_row)
+{
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(32u, std::max(1u, bsx_usable_cpus())), rows / 65536 + 1));
+    std::vector<std::string> parts(nt);
+    auto fmt = [&](unsigned t) {
+        std::string &o = parts[t];
+        const size_t lo = rows * t / nt, hi = rows * (t + 1) / nt;
+        o.reserve((hi - lo) * reserve_per_row);
+        for (size_t i = lo; i < hi; i++) fmt_row(i, o);
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(fmt, t);
+    fmt(0);
+    for (std::thread &x : th) x.join();
+    for (const std::string &o : parts) fwrite(o.data(), 1, o.size(), f);
+}
+
+int write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth)
+{
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
+    FILE *f = closer.f;
+    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    fputs("track type=wiggle_0\n", f);
+    std::vector<uint64_t> sums;
+    for (const uint32_t c : sorted_chromosomes(m)) {
+        fprintf(f, "variableStep chrom=%s span=%u\n", m->names[c].c_str(), bin);
+        const u64 need = (m->chr_off[c + 1] - m->chr_off[c]) / bin + 1;
+        sums.resize((size_t)need * 5);
+        uint64_t nb = 0;
+        const int rc = bsx_meth_bins(m, c, bin, min_depth, need, sums.data(), &nb);
+        if (rc) return rc;
+        format_rows(f, (size_t)nb, 8, [&](size_t j, std::string &o) {
+            const uint64_t *s = &sums[j * 5];
+            if (!s[0] || !s[3]) return;  // (E == 0 with a site: d * g / ga below 2^-17, no real pile-up; no ratio to print)
+            char line[64];
+            o.append(line, (size_t)snprintf(line, sizeof(line), "%llu\t%.3f\n", (u64)j * bin + 1, (double)s[4] / (double)s[3]));
+        });
+    }
+    closer.f = nullptr;
+    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    return BSX_OK;
+}
+
+int write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
+{
+    bsx_meth_parse::BedRecords bed;
+    {
+        Mapping map;
+        const int rc_open = map.open(bed_path);
+        if (rc_open != BSX_OK) return rc_open;
+        std::unordered_map<std::string, uint32_t> cid;
+        std::vector<bsx_meth_parse::u64> lens;
+        for (uint32_t c = 0; c < m->n_chr; c++) { cid.emplace(m->names[c], c); lens.push_back(m->chr_off[c + 1] - m->chr_off[c]); }
+        const u64 bad = map.len ? bsx_meth_parse::parse_bed(map.base, map.len, cid, lens, bed) : 0;
+        if (bad) { g_bsx_err = std::string(bed_path) + ": line " + std::to_string(bad) + ": not a BED record (name, start <= end as numbers)"; return BSX_ERR_IO; }
+    }
+    if (bed.chr.size() > 0xffffffffull) { g_bsx_err = std::string(bed_path) + ": more than 2^32 - 1 records"; return BSX_ERR_LIMIT; }
+    const size_t n = bed.chr.size();
+    std::vector<uint64_t> sums(n * 5 + 1);
+    const int rc = bsx_meth_regions(m, (uint32_t)n, bed.chr.data(), bed.start.data(), bed.end.data(), min_depth, sums.data());
+    if (rc) return rc;
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(out_path, "w")};
+    FILE *f = closer.f;
+    if (!f) { g_bsx_err = std::string("cannot write ") + out_path; return BSX_ERR_IO; }
+    fputs("chr\tstart\tend\tname\tn_C\tmethy_C\ttotal_C\teff_CT\tratio\tCI_lower\tCI_upper\n", f);
+    const double z95 = 1.96, z95sq = 1.96 * 1.96;
+    format_rows(f, n, 64, [&](size_t i, std::string &o) {
+        const uint64_t *s = &sums[i * 5];
+        char num[256];
+        o += m->names[bed.chr[i]];
+        o.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t", bed.start[i], bed.end[i]));
+        o += bed.label[i];
+        const double d = (double)s[3] / 65536.0;
+        if (!s[0] || !s[3]) { o.append(num, (size_t)snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%.2f\tNA\tNA\tNA\n", (u64)s[0], (u64)s[1], (u64)s[2], d)); return; }
+        const double ratio = (double)s[4] / (double)s[3];  // the table's interval (write_table) over the pooled effective depth
+        const double pmid = ratio + z95sq / (2 * d);
+        const double sd = z95 * pow(ratio * (1 - ratio) / d + z95sq / (4 * d * d), 0.5);
+        const double norminator = 1 + z95sq / d;
+        o.append(num, (size_t)snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%.2f\t%.3f\t%.3f\t%.3f\n", (u64)s[0], (u64)s[1], (u64)s[2], d, ratio, (pmid - sd) / norminator,
+                                       (pmid + sd) / norminator));
+    });
+    closer.f = nullptr;
+    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + out_path; return BSX_ERR_IO; }
+    if (n_written) *n_written = n;
+    if (n_dropped) *n_dropped = bed.dropped;
+    return BSX_OK;
+}
+
+}  // namespace
+
+extern "C" int bsx_meth_write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth)
+{
+    if (!m || !path || !bin || m->names.size() != m->n_chr) return BSX_ERR_ARG;
+    try {
+        return write_wig(m, path, bin, min_depth);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
+    }
+}
+
+extern "C" int bsx_meth_write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
+{
+    if (!m || !bed_path || !out_path || m->names.size() != m->n_chr) return BSX_ERR_ARG;
+    if (n_written) *n_written = 0;
+    if (n_dropped) *n_dropped = 0;
+    try {
+        return write_regions(m, bed_path, out_path, min_depth, n_written, n_dropped);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + out_path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("writing ") + out_path + ": " + x.what(); return BSX_ERR_IO;
+    }
+}

@@ -345,4 +345,62 @@ inline int parse_fasta(const char *base, size_t len, const char *chroms_csv, std
     return 0;
 }
 
+// The intervals of a BED file (bsx_meth_write_regions), in the file's order.  A line ends at '\n'; one '\r' in front of it is dropped.  Skipped: an empty
+// line, a line of blanks, a line that starts with '#', "track" or "browser".  Columns are separated by runs of tabs and spaces: name, start (0-based), end
+// (exclusive), an optional label ("." when absent); further columns are ignored.  start and end are 1 to 18 decimal digits and nothing else.  A record
+// whose name `cid` does not hold is dropped and counted (after its numbers have been checked).  end is clipped to the sequence's length, then start to end.
+struct BedRecords {
+    std::vector<uint32_t> chr, start, end;
+    std::vector<std::string> label;
+    u64 dropped = 0;
+};
+
+inline bool bed_number(const char *b, size_t n, u64 &v)
+{
+    if (n < 1 || n > 18) return false;
+    v = 0;
+    for (size_t i = 0; i < n; i++) { if (b[i] < '0' || b[i] > '9') return false; v = v * 10 + (u64)(b[i] - '0'); }
+    return true;
+}
+
+// Returns 0, or the 1-based number of the first line with fewer than three columns, a start or end that is no number, or start > end (`o` is then void).
+// chr_len[id]: the sequences' lengths (below 2^32).
+inline u64 parse_bed(const char *base, size_t len, const std::unordered_map<std::string, uint32_t> &cid, const std::vector<u64> &chr_len, BedRecords &o)
+{
+    const char *p = base, *const e = base + len;
+    u64 line = 0;
+    std::string key;
+    while (p < e) {
+        const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
+        const char *le = nl ? nl : e;  // line without its newline
+        const char *b = p;
+        p = nl ? nl + 1 : e;
+        line++;
+        if (le > b && le[-1] == '\r') le--;
+        const size_t n = (size_t)(le - b);
+        if (!n || b[0] == '#' || (n >= 5 && !memcmp(b, "track", 5)) || (n >= 7 && !memcmp(b, "browser", 7))) continue;
+        const char *tok[4]; size_t tlen[4];
+        int nt = 0;
+        for (const char *q = b; q < le && nt < 4;) {
+            while (q < le && (*q == ' ' || *q == '\t')) q++;
+            if (q == le) break;
+            tok[nt] = q;
+            while (q < le && *q != ' ' && *q != '\t') q++;
+            tlen[nt] = (size_t)(q - tok[nt]);
+            nt++;
+        }
+        if (!nt) continue;
+        u64 s, t;
+        if (nt < 3 || !bed_number(tok[1], tlen[1], s) || !bed_number(tok[2], tlen[2], t) || s > t) return line;
+        key.assign(tok[0], tlen[0]);
+        const auto it = cid.find(key);
+        if (it == cid.end() || it->second >= chr_len.size()) { o.dropped++; continue; }
+        const u64 cl = std::min<u64>(chr_len[it->second], 0xffffffffull);
+        t = std::min(t, cl); s = std::min(s, t);
+        o.chr.push_back(it->second); o.start.push_back((uint32_t)s); o.end.push_back((uint32_t)t);
+        o.label.push_back(nt > 3 ? std::string(tok[3], tlen[3]) : std::string("."));
+    }
+    return 0;
+}
+
 }  // namespace bsx_meth_parse

@@ -16,7 +16,10 @@ writes the M-bias table (methylated / all calls per sequencing cycle, strand and
 kernel), `--trim-5p=N` / `--trim-3p=N` ignore the calls of the first / last N cycles of every read.  From later BSMAP releases:
 `-i/--ct-snp {no-action,correct,skip}` counts, in the same pile-up, what the reads of the other reference strand show over every C (G: intact, A: a C->T
 SNP) and corrects the depth by that share or skips the position, with their 12-column table (default here: no-action, the table above); `-x/--context
-CG,CHG,CHH` lists the cytosines of those contexts only."""
+CG,CHG,CHH` lists the cytosines of those contexts only; `-w/--wig FILE` with `-b/--wig-bin N` (default 25) writes a wiggle track of the pooled
+methylation ratio per bin of N nt.  Extension: `--regions BED --region-out FILE` writes one pooled ratio per BED interval (promoters, CpG islands, capture
+targets).  Both are sums of the counters on the GPU (bsx_meth_bins, bsx_meth_regions) under the table's row rule (-m, -x, -i; after -g), not a pass
+over the table's text."""
 import ctypes as C
 import sys
 import time
@@ -54,6 +57,11 @@ def _bind():
     L.bsx_meth_set_ct_snp.argtypes = [vp, i32]
     L.bsx_meth_set_contexts.argtypes = [vp, u32]
     L.bsx_meth_fetch_rows_snp.argtypes = [vp, vp, vp]
+    L.bsx_meth_region_tile.argtypes = []; L.bsx_meth_region_tile.restype = u32
+    L.bsx_meth_regions.argtypes = [vp, u32, vp, vp, vp, u32, vp]
+    L.bsx_meth_bins.argtypes = [vp, u32, u32, u32, u64, vp, vp]
+    L.bsx_meth_write_regions.argtypes = [vp, C.c_char_p, C.c_char_p, u32, vp, vp]
+    L.bsx_meth_write_wig.argtypes = [vp, C.c_char_p, u32, u32]
     L._meth_bound = True
     return L
 
@@ -83,8 +91,13 @@ def load_reference(path, chroms):
 
 
 def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=False, rm_dup=False, trim_fillin=2, combine_CpG=False,
-        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0, ct_snp="no-action", context=None):
-    """returns the summary line the reference prints on stdout; ct_snp: one of CT_SNP_MODES, context: names of CONTEXT_BITS to list (None: all)"""
+        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0, ct_snp="no-action", context=None, wig=None, wig_bin=25, regions=None, region_out=None):
+    """returns the summary line the reference prints on stdout; ct_snp: one of CT_SNP_MODES, context: names of CONTEXT_BITS to list (None: all);
+    wig: wiggle file of the pooled ratio per bin of wig_bin nt; regions / region_out: BED file in, one pooled ratio per interval out"""
+    if wig_bin < 1:
+        raise ValueError("wig_bin must be at least 1")
+    if (regions is None) != (region_out is None):
+        raise ValueError("regions and region_out go together")
     if ct_snp not in CT_SNP_MODES:
         raise ValueError("ct_snp must be one of %s" % ", ".join(CT_SNP_MODES))
     if context is not None and (not context or any(x not in CONTEXT_BITS for x in context)):
@@ -121,6 +134,14 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
         nc, nd, nmap = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(L.bsx_meth_write_table(h, outfile.encode(), 0, None, None, min_depth, 1 if meth0 else 0, C.byref(nc), C.byref(nd)))
         _check(L.bsx_meth_valid_mappings(h, C.byref(nmap)))
+        if wig is not None:
+            disp("writing %s ..." % wig)
+            _check(L.bsx_meth_write_wig(h, wig.encode(), wig_bin, min_depth))
+        if regions is not None:
+            disp("writing %s ..." % region_out)
+            nw, ndrop = C.c_uint64(), C.c_uint64()
+            _check(L.bsx_meth_write_regions(h, regions.encode(), region_out.encode(), min_depth, C.byref(nw), C.byref(ndrop)))
+            disp("%d intervals of %s written, %d on sequences that are not loaded dropped" % (nw.value, regions, ndrop.value))
         disp("done.")
         # (with nothing covered the reference dies here on a division by zero; that is reported instead)
         if nc.value == 0:
@@ -163,6 +184,15 @@ def build_parser():
     ap.add_argument("-i", "--ct-snp", dest="ct_snp", choices=CT_SNP_MODES, default="no-action",
                     help="C/T SNPs, told from unmethylated C by the reads of the other strand: correct the depth, skip the position, or no-action (default)")
     ap.add_argument("-x", "--context", dest="context", type=contexts, default=None, metavar="CG,CHG,CHH", help="list cytosines of these contexts only (default: all)")
+    def bin_width(txt):
+        n = int(txt)
+        if n < 1:
+            raise argparse.ArgumentTypeError("a bin is at least 1 nt wide")
+        return n
+    ap.add_argument("-w", "--wig", dest="wig", default=None, metavar="FILE", help="write a wiggle track of the pooled methylation ratio per bin")
+    ap.add_argument("-b", "--wig-bin", dest="wig_bin", type=bin_width, default=25, metavar="N", help="bin width of the wiggle track in nt (default 25)")
+    ap.add_argument("--regions", dest="regions", default=None, metavar="BED", help="intervals (BED: name, start, end, optional label) to pool the methylation over (extension)")
+    ap.add_argument("--region-out", dest="region_out", default=None, metavar="FILE", help="table to write for --regions: one pooled ratio per interval, in the BED file's order")
     ap.add_argument("infiles", nargs="+", help="mapping files written by bsmap: *.sam / *.bam by their format, anything else as BSP")
     return ap
 
@@ -172,7 +202,8 @@ def main(argv=None):
     o = build_parser().parse_args(argv)
     sys.stdout.write(run(o.reffile, o.infiles, o.outfile, chroms=o.chroms.split(",") if o.chroms else None, unique=o.unique, pair=o.pair, meth0=o.meth0,
                          rm_dup=o.rm_dup, trim_fillin=o.trim_fillin, combine_CpG=o.combine_CpG, min_depth=o.min_depth, device=o.device, quiet=o.quiet,
-                         mbias=o.mbias, trim5=o.trim5, trim3=o.trim3, ct_snp=o.ct_snp, context=o.context))
+                         mbias=o.mbias, trim5=o.trim5, trim3=o.trim3, ct_snp=o.ct_snp, context=o.context, wig=o.wig, wig_bin=o.wig_bin,
+                         regions=o.regions, region_out=o.region_out))
 
 
 if __name__ == "__main__":

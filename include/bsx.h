@@ -394,6 +394,36 @@ int bsx_meth_fetch_rows_snp(bsx_meth *m, uint32_t *rev_g, uint32_t *rev_ga);
  * ratio and Wilson interval with the reference's arithmetic, "%.3f"); returns the counts of the summary line */
 int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_order, const uint32_t *order, const char *const *chr_names, uint32_t min_depth, int meth0,
                          uint64_t *n_covered, uint64_t *sum_depth);
+/* Pooled methylation per interval and per fixed bin (extensions; -w / -b of later BSMAP releases, and BED intervals), from the counters as they stand,
+ * under the handle's current C/T-SNP mode and context mask.  A position is a SITE when the row rule above holds for it (min_depth, the context filter,
+ * the SNP tests) and its raw depth is above 0; meth0 plays no part.  Per site, with d the raw depth, m the methylated count, g / ga the rev cells:
+ * e = d << 16, or with the mode on and g != ga rint(((double)d * g / ga) * 65536.0) — the table's effective depth in units of 1/65536 —, and
+ * mc = min(m << 16, e).  Per interval five uint64 sums over its sites: N (sites), M = sum m, D = sum d, E = sum e, MC = sum mc; the pooled ratio is
+ * (double)MC / (double)E and the effective depth E / 65536.0.  Integer sums: the same bits on every call.  The calls change no counter and may be made
+ * any number of times, before or after bsx_meth_write_table and bsx_meth_combine_cpg. */
+uint32_t bsx_meth_region_tile(void);   /* positions per wave of bsx_meth_regions: a longer interval is cut into tiles of this size (csrc/bsx_meth_tiles.h) */
+/* n intervals [start, end) of chromosome chr, 0-based, in any order, overlapping or repeated; end beyond the chromosome is clipped to its length, start
+ * then to end.  BSX_ERR_ARG: chr out of range, start > end, a null pointer with n > 0.  n == 0 is BSX_OK.  BSX_ERR_NOMEM */
+int bsx_meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end,
+                     uint32_t min_depth, uint64_t *sums /* [n][5]: N, M, D, E, MC */);
+/* the bins of one chromosome: bin j holds the positions [j * bin, min((j + 1) * bin, length)), there are length / bin + 1 of them (the last may be
+ * empty) and that number comes back in n_bins.  BSX_ERR_ARG: chr out of range, bin == 0, a null m or n_bins; also sums == NULL or n_bins_cap below the
+ * number of bins, with n_bins set (a call with sums == NULL asks for the size).  BSX_ERR_NOMEM when the bin array cannot be had on the device */
+int bsx_meth_bins(bsx_meth *m, uint32_t chr, uint32_t bin, uint32_t min_depth, uint64_t n_bins_cap,
+                  uint64_t *sums /* [n_bins][5] */, uint64_t *n_bins);
+/* The intervals of a BED file (columns separated by tabs or spaces: name, start, end, optional label; empty lines and lines that start with '#', "track"
+ * or "browser" are skipped; CRLF and a last line without newline are accepted) as a table in the file's order: header
+ * "chr start end name n_C methy_C total_C eff_CT ratio CI_lower CI_upper" (tab-separated), then per record the clipped coordinates, the label or ".",
+ * N, M, D, E / 65536.0 ("%.2f"), the pooled ratio ("%.3f") and the table's Wilson interval over that depth and ratio; "0 0 0 0.00 NA NA NA" without a
+ * site.  A record on a sequence the handle does not hold is dropped and counted in n_dropped.  A line with fewer than three columns, a start or end that
+ * is not 1-18 decimal digits, or start > end: BSX_ERR_IO with the line's number in bsx_last_error_detail, and nothing is written.  Needs a handle that
+ * knows its names (bsx_meth_create_from_fasta), else BSX_ERR_ARG.  n_written / n_dropped may be NULL. */
+int bsx_meth_write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint32_t min_depth,
+                           uint64_t *n_written, uint64_t *n_dropped);
+/* A wiggle track of the pooled ratio per bin: "track type=wiggle_0", then for every chromosome in sorted name order (the table's)
+ * "variableStep chrom=<name> span=<bin>" and for every bin with a site, ascending, "<j * bin + 1><TAB><ratio %.3f>".  BSX_ERR_ARG for bin == 0 or a
+ * handle without names. */
+int bsx_meth_write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth);
 
 #ifdef __cplusplus
 }

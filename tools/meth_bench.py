@@ -2,7 +2,10 @@
 """Throughput of the methylation pile-up kernels (bsx_meth_add) on an hg38-sized random reference: N alignments of L nt
 at uniform positions, all four strands, reads = reference letters with bisulfite-like conversion.  Prints one JSON line;
 run under `rocprofv3 --kernel-trace --stats` for the kernel-only times.  `--ct-snp correct|skip` turns the C/T-SNP mode on (one more 64-bit cell per
-reference letter, reverse calls in the pile-up, the SNP tests in the report).  usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE]"""
+reference letter, reverse calls in the pile-up, the SNP tests in the report).  `--wig-bin B[,B...]` times bsx_meth_bins over all chromosomes and
+`--regions N,LEN[;N,LEN...]` bsx_meth_regions over N intervals of LEN nt at uniform positions (made here, no file), both with their copies to the host and
+`--repeat` times each, in the order given (the order of their launches in a kernel trace).
+usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,6 +19,9 @@ def main():
     ap.add_argument("--len", type=int, default=100)
     ap.add_argument("--genome", type=float, default=1.0)
     ap.add_argument("--ct-snp", dest="ct_snp", choices=MR.CT_SNP_MODES, default="no-action")
+    ap.add_argument("--wig-bin", dest="wig_bin", default="")
+    ap.add_argument("--regions", dest="regions", default="")
+    ap.add_argument("--repeat", type=int, default=1)
     a = ap.parse_args()
     L = MR._bind()
     rng = np.random.default_rng(1)
@@ -60,9 +66,34 @@ def main():
         B._check(L.bsx_meth_report_chr(h, c, 1, 1, C.byref(nr), C.byref(cv), C.byref(sd)))
         rows += nr.value; cov += cv.value
     dt_rep = time.perf_counter() - t1
+    extra = {}
+    for width in [int(x) for x in a.wig_bin.split(",") if x]:
+        out = np.zeros((int(lens.max()) // width + 1, 5), np.uint64)
+        nb, took = C.c_uint64(), []
+        for _ in range(a.repeat):
+            sites, t2 = 0, time.perf_counter()
+            for c in range(len(lens)):
+                B._check(L.bsx_meth_bins(h, c, width, 1, len(out), out.ctypes.data, C.byref(nb)))
+                sites += int(out[:nb.value, 0].sum())
+            took.append(round(time.perf_counter() - t2, 3))
+        extra.setdefault("bins_s_all_chromosomes", []).append({"wig_bin": width, "s": took, "sites": sites})
+    for spec in [x for x in a.regions.split(";") if x]:
+        n_iv, iv_len = (int(x) for x in spec.split(","))
+        fits = np.nonzero(lens >= iv_len)[0]
+        if len(fits) and fits[0] < 2:
+            fits = fits[fits < 2]  # on the chromosomes that carry the alignments, where one of them is long enough
+        ic = fits[rng.integers(0, len(fits), n_iv)].astype(np.uint32)
+        start = (rng.random(n_iv) * (lens[ic] - iv_len + 1)).astype(np.uint32)
+        end = (start + iv_len).astype(np.uint32)
+        sums, took = np.zeros((n_iv, 5), np.uint64), []
+        for _ in range(a.repeat):
+            t3 = time.perf_counter()
+            B._check(L.bsx_meth_regions(h, n_iv, ic.ctypes.data, start.ctypes.data, end.ctypes.data, 1, sums.ctypes.data))
+            took.append(round(time.perf_counter() - t3, 3))
+        extra.setdefault("regions_s", []).append({"intervals": n_iv, "len": iv_len, "s": took, "sites": int(sums[:, 0].sum())})
     L.bsx_meth_destroy(h)
-    print(json.dumps({"alignments": n, "read_len": ln, "ct_snp": a.ct_snp, "add_s_incl_pcie": round(dt, 3), "alignments_per_s_incl_pcie": round(n / dt),
-                      "report_s_all_chromosomes": round(dt_rep, 3), "rows": rows, "covered": cov, "genome_bp": int(lens.sum())}))
+    print(json.dumps(dict({"alignments": n, "read_len": ln, "ct_snp": a.ct_snp, "add_s_incl_pcie": round(dt, 3), "alignments_per_s_incl_pcie": round(n / dt),
+                           "report_s_all_chromosomes": round(dt_rep, 3), "rows": rows, "covered": cov, "genome_bp": int(lens.sum())}, **extra)))
 
 
 if __name__ == "__main__":
