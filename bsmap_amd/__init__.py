@@ -74,6 +74,8 @@ EXPORTS = [
     "bsx_meth_set_cycle_trim", "bsx_meth_set_mbias", "bsx_meth_mbias_fetch", "bsx_meth_write_mbias",
     "bsx_meth_set_ct_snp", "bsx_meth_set_contexts", "bsx_meth_fetch_rows_snp",
     "bsx_meth_region_tile", "bsx_meth_regions", "bsx_meth_bins", "bsx_meth_write_regions", "bsx_meth_write_wig",
+    "bsx_meth_set_nonconv", "bsx_meth_nonconv_dropped", "bsx_meth_set_read_stats", "bsx_meth_read_stats_fetch", "bsx_meth_write_read_stats",
+    "bsx_meth_set_pdr", "bsx_meth_pdr_report_chr", "bsx_meth_pdr_fetch_rows", "bsx_meth_write_pdr",
 ]
 
 

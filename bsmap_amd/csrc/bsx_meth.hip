@@ -8,6 +8,7 @@
 //   k_meth_pile    trim, bounds test, compare read and reference letters, atomicAdd on depth / methylated counters
 //   k_meth_pile_mbias   the same pile-up in a persistent grid that also tallies every call by strand, context and read cycle (M-bias, --mbias) in LDS
 //   k_meth_cpg     fold the G of every CG into its C
+//   k_meth_reads   per-read call counts ahead of the pile-up: non-conversion filter, read histogram, PDR cells; off by default
 // With the C/T-SNP mode on (bsx_meth_set_ct_snp, an extension: -i of later BSMAP releases) the same pile-up pass also counts, per reference position, what the reads
 // of the OTHER reference strand show there (G over an intact C, A over a C->T SNP), and the row selection and the table use those two counters.
 //   k_meth_count / k_meth_emit   ordered compaction of the positions the table will list
@@ -64,6 +65,7 @@ struct AlnBatch {
     const u64 *seq_off;
     uint32_t n, index_base, trim_fillin;
     uint32_t trim5, trim3;     // calls of the first trim5 / last trim3 sequencing cycles of every read are ignored
+    const uint8_t *drop;       // [n] non-zero: dropped by the non-conversion filter (written by k_meth_reads), or null when the filter is off
 };
 
 // C/T-SNP mode: the kernels take `rev`, one cell per reference position: low word rev_GA (opposite-strand calls that show the unconverted or the converted
@@ -117,6 +119,7 @@ struct MethWindow {
 
 __device__ __forceinline__ bool meth_window(const MethDev &M, const AlnBatch &B, uint32_t i, MethWindow &W)
 {
+    if (B.drop && B.drop[i]) return false;  // the non-conversion filter took it: not a valid mapping, no call of any kind
     if (M.first) {
         u64 slot;
         if (dup_slot(M, B, i, slot) && M.first[slot] != B.index_base + i) return false;  // an earlier alignment owns this fragment end
@@ -260,7 +263,135 @@ __global__ __launch_bounds__(MB_BLOCK) void k_meth_pile_mbias(MethDev M, AlnBatc
     }
 }
 
-__global__ void k_meth_cpg(MethDev M, u64 *rev)
+// ---- per-read calls: non-conversion filter, read histogram, PDR ----
+// What k_meth_reads gets beside the batch.  hist: cg[32][32], ch[64], then the four totals (reads, cg_over, ch_calls, ch_meth), or null; pdr: one cell per
+// reference position, low word reads, high word discordant, or null; drop: the batch's flags to write, or null when the filter is off.
+struct ReadsDev {
+    u64 *hist, *pdr, *dropped;
+    uint8_t *drop;
+    uint32_t nonconv, min_cpg;
+};
+constexpr int RS_CG = BSX_RS_CG_MAX + 1, RS_CH = BSX_RS_CH_MAX + 1;
+constexpr int RS_LDS_CELLS = RS_CG * RS_CG + RS_CH;  // the cells a block tallies in LDS: 1 088 x 4 B
+constexpr size_t RS_CELLS = (size_t)RS_LDS_CELLS + 4;
+constexpr int RS_BLOCK = 512, RS_BLOCKS_PER_CU = 3;  // 78 VGPRs: 6 waves per SIMD, 24 per CU
+
+// Letter k of the window as a call: its context class 0..3 and in `m` whether it shows the unconverted letter; -1 where meth_calls makes no forward call
+// (the same tests in the same order: own cytosine, one of the two letters, cycle mask).
+__device__ __forceinline__ int meth_call_class(const MethDev &M, const AlnBatch &B, const MethWindow &W, const uint8_t *s, u64 c0, u64 c1, u64 g0, int64_t k, bool &m)
+{
+    const bool plus = !(W.st & 1), backward = W.st == 1 || W.st == 2;
+    const uint8_t match = plus ? 'C' : 'G', convert = plus ? 'T' : 'A';
+    if (M.ref[g0 + k] != match) return -1;
+    const uint8_t ch = s[k];
+    if (ch != convert && ch != match) return -1;
+    const int64_t j = W.lo + k, cyc = backward ? W.n0 - 1 - j : j;
+    if (cyc < (int64_t)B.trim5 || cyc >= W.n0 - (int64_t)B.trim3) return -1;
+    m = ch == match;
+    return (int)meth_context(M.ref, g0 + k, c0, c1, plus);
+}
+
+// One wave per alignment in a persistent grid (the shape of k_meth_pile_mbias), ahead of the pile-up.  The wave walks the window 64 letters at a time; a lane
+// classifies its letter, four ballots and popcounts give the wave n_cg, m_cg, n_ch, m_ch of the step as uniform values, summed over the steps of a read
+// longer than 64.  Then, uniform over the wave: lane 0 tallies the read in the block's LDS histogram (cg[0..1][..] and ch[0] receive nearly every read: one
+// atomic per read on them in HBM would serialise; the block flushes its non-zero cells once, as 64-bit atomic adds), lane 0 writes the drop flag the
+// pile-up kernels read through AlnBatch::drop, and for an eligible read a second walk adds one packed 64-bit value per CG call to the PDR cells.
+// The totals are uniform too and stay in registers until the block is done.  B.drop is null here: the window is the unfiltered one.
+__global__ __launch_bounds__(RS_BLOCK) void k_meth_reads(MethDev M, AlnBatch B, ReadsDev R)
+{
+    __shared__ uint32_t s_hist[RS_LDS_CELLS];
+    __shared__ u64 s_tot[5];  // reads, cg_over, ch_calls, ch_meth, dropped
+    for (uint32_t t = threadIdx.x; t < (uint32_t)RS_LDS_CELLS; t += blockDim.x) s_hist[t] = 0;
+    if (threadIdx.x < 5) s_tot[threadIdx.x] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const uint32_t waves = blockDim.x >> 6;
+    u64 tot[5] = {0, 0, 0, 0, 0};
+    for (u64 i = (u64)blockIdx.x * waves + (threadIdx.x >> 6); i < B.n; i += (u64)gridDim.x * waves) {
+        MethWindow W;
+        bool drop = false;
+        if (meth_window(M, B, (uint32_t)i, W)) {
+            uint32_t n_cg = 0, m_cg = 0, n_ch = 0, m_ch = 0;
+            const uint8_t *s = B.seq + B.seq_off[i] + W.lo;
+            const u64 c0 = M.chr_off[W.c], c1 = M.chr_off[W.c + 1], g0 = c0 + (u64)W.pos;
+            const int64_t len = W.pos < 0 ? 0 : W.hi - W.lo;  // (a negative position makes no call: meth_calls)
+            for (int64_t k0 = 0; k0 < len; k0 += 64) {  // uniform bounds: every lane takes part in the ballots
+                bool m = false;
+                const int cls = k0 + lane < len ? meth_call_class(M, B, W, s, c0, c1, g0, k0 + lane, m) : -1;
+                const bool cg = cls == 0, chx = cls == 1 || cls == 2;
+                n_cg += (uint32_t)__builtin_popcountll(__ballot(cg)); m_cg += (uint32_t)__builtin_popcountll(__ballot(cg && m));
+                n_ch += (uint32_t)__builtin_popcountll(__ballot(chx)); m_ch += (uint32_t)__builtin_popcountll(__ballot(chx && m));
+            }
+            if (R.hist) {
+                if (lane == 0) {
+                    if (n_cg <= BSX_RS_CG_MAX) atomicAdd(&s_hist[n_cg * RS_CG + m_cg], 1u);
+                    atomicAdd(&s_hist[RS_CG * RS_CG + (m_ch < BSX_RS_CH_MAX ? m_ch : BSX_RS_CH_MAX)], 1u);
+                }
+                tot[0]++; tot[1] += n_cg > BSX_RS_CG_MAX; tot[2] += n_ch; tot[3] += m_ch;
+            }
+            drop = R.nonconv && m_ch >= R.nonconv;
+            tot[4] += drop;
+            if (R.pdr && !drop && n_cg >= R.min_cpg) {  // eligible (min_cpg >= 1: n_cg > 0, so the position is not negative)
+                const u64 add = (m_cg != 0 && m_cg != n_cg) ? ((1ull << 32) | 1ull) : 1ull;  // < 2^32 alignments per handle: the low word cannot carry
+                for (int64_t k = lane; k < len; k += 64) {
+                    bool m = false;
+                    if (meth_call_class(M, B, W, s, c0, c1, g0, k, m) == 0) atomicAdd(&R.pdr[g0 + k], add);
+                }
+            }
+        }
+        if (R.drop && lane == 0) R.drop[i] = drop;
+    }
+    if (lane == 0) for (int q = 0; q < 5; q++) if (tot[q]) atomicAdd(&s_tot[q], tot[q]);
+    __syncthreads();
+    if (R.hist) {
+        for (uint32_t t = threadIdx.x; t < (uint32_t)RS_LDS_CELLS; t += blockDim.x) { const uint32_t v = s_hist[t]; if (v) atomicAdd(&R.hist[t], (u64)v); }
+        if (threadIdx.x < 4 && s_tot[threadIdx.x]) atomicAdd(&R.hist[RS_LDS_CELLS + threadIdx.x], s_tot[threadIdx.x]);
+    }
+    if (threadIdx.x == 0 && s_tot[4]) atomicAdd(R.dropped, s_tot[4]);
+}
+
+// PDR rows of one chromosome in position order (bsx_meth_pdr_report_chr): the count / scan / emit scheme of k_meth_count / k_meth_emit below with the rule
+// reads >= min_reads (min_reads >= 1) on the cell's low word
+__global__ __launch_bounds__(256) void k_pdr_count(const u64 *pdr, u64 g0, u64 n, uint32_t min_reads, uint32_t *blk_rows)
+{
+    __shared__ uint32_t s_rows;
+    if (threadIdx.x == 0) s_rows = 0;
+    __syncthreads();
+    uint32_t rows = 0;
+    for (int r = 0; r < 4; r++) {
+        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
+        if (k < n) rows += (uint32_t)pdr[g0 + k] >= min_reads;
+    }
+    if (rows) atomicAdd(&s_rows, rows);
+    __syncthreads();
+    if (threadIdx.x == 0) blk_rows[blockIdx.x] = s_rows;
+}
+
+__global__ __launch_bounds__(256) void k_pdr_emit(const uint8_t *ref, const u64 *pdr, u64 g0, u64 n, uint32_t min_reads, const uint32_t *blk_start, uint32_t *out_pos,
+                                                  uint32_t *out_reads, uint32_t *out_disc, uint8_t *out_letter)
+{
+    __shared__ uint32_t s_wave[4];
+    uint32_t base = blk_start[blockIdx.x];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int r = 0; r < 4; r++) {  // positions blockIdx*1024 + r*256 + thread: ascending with (r, thread)
+        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
+        const u64 cell = k < n ? pdr[g0 + k] : 0ull;
+        const bool row = k < n && (uint32_t)cell >= min_reads;
+        const u64 bal = __ballot(row);
+        if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int w = 0; w < wv; w++) off += s_wave[w];
+        if (row) {
+            const uint32_t o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
+            out_pos[o] = (uint32_t)k; out_reads[o] = (uint32_t)cell; out_disc[o] = (uint32_t)(cell >> 32); out_letter[o] = ref[g0 + k];
+        }
+        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+}
+
+__global__ void k_meth_cpg(MethDev M, u64 *rev, u64 *pdr)
 {
     // every "CG" of every chromosome (occurrences cannot overlap): the G's counters move onto the C  (methratio.py:118-128)
     for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g + 1 < M.total; g += (u64)gridDim.x * blockDim.x) {
@@ -272,6 +403,7 @@ __global__ void k_meth_cpg(MethDev M, u64 *rev)
         M.depth[g] += M.depth[g + 1]; M.meth[g] += M.meth[g + 1];
         M.depth[g + 1] = 0; M.meth[g + 1] = 0;
         if (rev) { rev[g] += rev[g + 1]; rev[g + 1] = 0; }  // both halves at once: each sum stays below 2^32
+        if (pdr) { pdr[g] += pdr[g + 1]; pdr[g + 1] = 0; }  // likewise
     }
 }
 
@@ -500,7 +632,7 @@ struct bsx_meth {
     uint32_t n_chr = 0;
     std::vector<u64> chr_off;
     uint8_t *d_ref = nullptr;
-    u64 *d_chr_off = nullptr, *d_counts = nullptr;  // d_counts: [0] valid alignments, [1] nc, [2] nd
+    u64 *d_chr_off = nullptr, *d_counts = nullptr;  // d_counts: [0] valid alignments, [1] nc, [2] nd, [3] dropped by the non-conversion filter
     uint32_t *d_depth = nullptr, *d_meth = nullptr, *d_first = nullptr;
     uint32_t index_base = 0;
     uint32_t trim5 = 0, trim3 = 0;  // bsx_meth_set_cycle_trim
@@ -509,6 +641,13 @@ struct bsx_meth {
     u64 *d_rev = nullptr;           // the packed opposite-strand counters, (total + 16) cells, or null when snp == 0
     uint32_t *d_out_rev[2] = {nullptr, nullptr};  // rev_G / rev_GA of the rows of the last report, allocated with d_out when snp != 0
     u64 *d_mbias = nullptr;         // bsx_meth_set_mbias: MB_CELLS cells and the overflow counter, or null
+    uint32_t nonconv = 0, min_cpg = 0;  // bsx_meth_set_nonconv, bsx_meth_set_pdr
+    u64 *d_hist = nullptr;          // bsx_meth_set_read_stats: RS_CELLS cells, or null
+    u64 *d_pdr = nullptr;           // the packed PDR cells, (total + 16) of them, or null when min_cpg == 0
+    uint32_t *d_pdr_out[3] = {nullptr, nullptr, nullptr};  // pos, reads, discordant of the rows of the last bsx_meth_pdr_report_chr
+    uint8_t *d_pdr_letter = nullptr;                       // and their reference letters
+    size_t pdr_out_cap = 0;
+    uint32_t pdr_last_rows = 0;
     int n_cu = 0;
     hipStream_t stream = nullptr;
     // report buffers of the last bsx_meth_report_chr
@@ -526,7 +665,8 @@ extern "C" void bsx_meth_destroy(bsx_meth *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     for (void *q : {(void *)m->d_ref, (void *)m->d_chr_off, (void *)m->d_counts, (void *)m->d_depth, (void *)m->d_meth, (void *)m->d_first, (void *)m->d_blk,
-                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias, (void *)m->d_rev, (void *)m->d_out_rev[0], (void *)m->d_out_rev[1]})
+                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias, (void *)m->d_rev, (void *)m->d_out_rev[0], (void *)m->d_out_rev[1],
+                    (void *)m->d_hist, (void *)m->d_pdr, (void *)m->d_pdr_out[0], (void *)m->d_pdr_out[1], (void *)m->d_pdr_out[2], (void *)m->d_pdr_letter})
         if (q) (void)hipFree(q);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
@@ -579,11 +719,12 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
     for (uint32_t i = 0; i < n; i++) if (chr[i] >= m->n_chr || strand[i] > 3) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
     const u64 nbytes = seq_off[n];
-    uint32_t *d_chr = nullptr; int64_t *d_pos = nullptr, *d_cut = nullptr; uint8_t *d_strand = nullptr, *d_seq = nullptr; int32_t *d_ins = nullptr; u64 *d_off = nullptr;
+    uint32_t *d_chr = nullptr; int64_t *d_pos = nullptr, *d_cut = nullptr; uint8_t *d_strand = nullptr, *d_seq = nullptr, *d_drop = nullptr; int32_t *d_ins = nullptr; u64 *d_off = nullptr;
     int rc = BSX_OK;
     auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == BSX_OK) rc = bsx_hip_fail(e, "bsx_meth_add", __FILE__, __LINE__); };
     chk(hipMalloc((void **)&d_chr, (size_t)n * 4)); chk(hipMalloc((void **)&d_pos, (size_t)n * 8)); chk(hipMalloc((void **)&d_cut, (size_t)n * 8));
     chk(hipMalloc((void **)&d_strand, n)); chk(hipMalloc((void **)&d_ins, (size_t)n * 4)); chk(hipMalloc((void **)&d_seq, nbytes + 16)); chk(hipMalloc((void **)&d_off, ((size_t)n + 1) * 8));
+    if (m->nonconv) chk(hipMalloc((void **)&d_drop, n));
     if (rc == BSX_OK) {
         chk(hipMemcpyAsync(d_chr, chr, (size_t)n * 4, hipMemcpyHostToDevice, m->stream)); chk(hipMemcpyAsync(d_pos, pos, (size_t)n * 8, hipMemcpyHostToDevice, m->stream));
         chk(hipMemcpyAsync(d_cut, cut_at, (size_t)n * 8, hipMemcpyHostToDevice, m->stream)); chk(hipMemcpyAsync(d_strand, strand, n, hipMemcpyHostToDevice, m->stream));
@@ -592,9 +733,15 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
     }
     if (rc == BSX_OK) {
         AlnBatch B; B.chr = d_chr; B.pos = d_pos; B.strand = d_strand; B.insert = d_ins; B.cut_at = d_cut; B.seq = d_seq; B.seq_off = d_off;
-        B.n = n; B.index_base = m->index_base; B.trim_fillin = trim_fillin; B.trim5 = m->trim5; B.trim3 = m->trim3;
+        B.n = n; B.index_base = m->index_base; B.trim_fillin = trim_fillin; B.trim5 = m->trim5; B.trim3 = m->trim3; B.drop = nullptr;
         const MethDev M = m->dev();
         if (m->d_first) hipLaunchKernelGGL(k_meth_first, dim3((n + 255) / 256), dim3(256), 0, m->stream, M, B);
+        if (m->nonconv || m->d_hist || m->d_pdr) {  // the per-read pass: it sees the unfiltered window (B.drop is still null) and writes every flag of d_drop
+            const unsigned waves = RS_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * RS_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
+            const ReadsDev R{m->d_hist, m->d_pdr, m->d_counts + 3, d_drop, m->nonconv, m->min_cpg};
+            hipLaunchKernelGGL(k_meth_reads, dim3(grid), dim3(RS_BLOCK), 0, m->stream, M, B, R);
+            B.drop = d_drop;
+        }
         if (m->d_mbias) {  // the grid comes from the CU count; a batch too small to give every wave an alignment gets fewer blocks (fewer flushes)
             const unsigned waves = MB_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * MB_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
             const MbiasDev D{m->d_mbias, m->d_mbias + MB_CELLS};
@@ -608,7 +755,7 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
         chk(hipStreamSynchronize(m->stream));
         m->index_base += n;
     }
-    for (void *q : {(void *)d_chr, (void *)d_pos, (void *)d_cut, (void *)d_strand, (void *)d_ins, (void *)d_seq, (void *)d_off}) if (q) (void)hipFree(q);
+    for (void *q : {(void *)d_chr, (void *)d_pos, (void *)d_cut, (void *)d_strand, (void *)d_ins, (void *)d_seq, (void *)d_off, (void *)d_drop}) if (q) (void)hipFree(q);
     return rc;
 }
 
@@ -720,7 +867,7 @@ extern "C" int bsx_meth_combine_cpg(bsx_meth *m)
 {
     if (!m) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
-    hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev(), m->d_rev);
+    hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev(), m->d_rev, m->d_pdr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m->stream));
     return BSX_OK;
@@ -734,6 +881,29 @@ extern "C" int bsx_meth_valid_mappings(bsx_meth *m, uint64_t *n)
     return BSX_OK;
 }
 
+// the per-block row counts of a report over nblk blocks of 1 024 positions: d_blk[nblk + 1] (the last one zeroed here) and their exclusive scan d_blk_start
+static int meth_block_buffers(bsx_meth *m, size_t nblk)
+{
+    if (nblk + 1 > m->blk_cap) {
+        if (m->d_blk) (void)hipFree(m->d_blk);
+        if (m->d_blk_start) (void)hipFree(m->d_blk_start);
+        m->d_blk = m->d_blk_start = nullptr; m->blk_cap = 0;
+        HIP_TRY(hipMalloc((void **)&m->d_blk, (nblk + 1) * 4)); HIP_TRY(hipMalloc((void **)&m->d_blk_start, (nblk + 1) * 4));
+        m->blk_cap = nblk + 1;
+    }
+    HIP_TRY(hipMemsetAsync(m->d_blk + nblk, 0, 4, m->stream));
+    return BSX_OK;
+}
+
+static int meth_scan_blocks(bsx_meth *m, size_t nblk)
+{
+    size_t need = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
+    if (need > m->temp_cap) { if (m->d_temp) (void)hipFree(m->d_temp); m->d_temp = nullptr; m->temp_cap = 0; HIP_TRY(hipMalloc(&m->d_temp, need)); m->temp_cap = need; }
+    HIP_TRY(rocprim::exclusive_scan(m->d_temp, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
+    return BSX_OK;
+}
+
 extern "C" int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth, int meth0, uint32_t *n_rows, uint64_t *n_covered, uint64_t *sum_depth)
 {
     if (!m || chr >= m->n_chr || !n_rows) return BSX_ERR_ARG;
@@ -744,23 +914,15 @@ extern "C" int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth
     if (n_covered) *n_covered = 0;
     if (sum_depth) *sum_depth = 0;
     if (!nblk) return BSX_OK;
-    if (nblk + 1 > m->blk_cap) {
-        if (m->d_blk) (void)hipFree(m->d_blk);
-        if (m->d_blk_start) (void)hipFree(m->d_blk_start);
-        m->d_blk = m->d_blk_start = nullptr; m->blk_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->d_blk, (nblk + 1) * 4)); HIP_TRY(hipMalloc((void **)&m->d_blk_start, (nblk + 1) * 4));
-        m->blk_cap = nblk + 1;
-    }
+    int rc = meth_block_buffers(m, nblk);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(m->d_counts + 1, 0, 16, m->stream));
-    HIP_TRY(hipMemsetAsync(m->d_blk + nblk, 0, 4, m->stream));
     const MethDev M = m->dev();
     const RowRule R{min_depth, m->ctx_mask, meth0, m->snp};
     hipLaunchKernelGGL(k_meth_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk, m->d_counts + 1, m->d_rev);
     HIP_TRY(hipGetLastError());
-    size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
-    if (need > m->temp_cap) { if (m->d_temp) (void)hipFree(m->d_temp); m->d_temp = nullptr; m->temp_cap = 0; HIP_TRY(hipMalloc(&m->d_temp, need)); m->temp_cap = need; }
-    HIP_TRY(rocprim::exclusive_scan(m->d_temp, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
+    rc = meth_scan_blocks(m, nblk);
+    if (rc) return rc;
     uint32_t rows = 0; u64 cnt[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipMemcpyAsync(cnt, m->d_counts + 1, 16, hipMemcpyDeviceToHost, m->stream));
@@ -808,6 +970,156 @@ extern "C" int bsx_meth_fetch_rows_snp(bsx_meth *m, uint32_t *rev_g, uint32_t *r
     if (!m->last_rows) return BSX_OK;
     HIP_TRY(hipMemcpy(rev_g, m->d_out_rev[0], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rev_ga, m->d_out_rev[1], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// ---- per-read calls ----
+extern "C" int bsx_meth_set_nonconv(bsx_meth *m, uint32_t n)
+{
+    if (!m) return BSX_ERR_ARG;
+    m->nonconv = n;
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_nonconv_dropped(bsx_meth *m, uint64_t *n)
+{
+    if (!m || !n) return BSX_ERR_ARG;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpy(n, m->d_counts + 3, 8, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// a zeroed array of u64 cells on the handle's stream (it does not wait for the null stream); BSX_ERR_NOMEM when it cannot be had
+static int meth_zeroed_cells(bsx_meth *m, u64 **out, size_t cells)
+{
+    u64 *p = nullptr;
+    if (hipMalloc((void **)&p, cells * 8) != hipSuccess) { (void)hipGetLastError(); return BSX_ERR_NOMEM; }
+    hipError_t e = hipMemsetAsync(p, 0, cells * 8, m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
+    *out = p;
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_set_read_stats(bsx_meth *m, int on)
+{
+    if (!m) return BSX_ERR_ARG;
+    if (m->index_base) { g_bsx_err = "bsx_meth_set_read_stats after alignments have been added"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!on) {
+        if (m->d_hist) (void)hipFree(m->d_hist);
+        m->d_hist = nullptr;
+        return BSX_OK;
+    }
+    return m->d_hist ? BSX_OK : meth_zeroed_cells(m, &m->d_hist, RS_CELLS);
+}
+
+extern "C" int bsx_meth_read_stats_fetch(bsx_meth *m, uint64_t *cg, uint64_t *ch, uint64_t *totals)
+{
+    if (!m || !cg || !ch || !totals) return BSX_ERR_ARG;
+    if (!m->d_hist) { g_bsx_err = "the read histogram is off (bsx_meth_set_read_stats)"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipMemcpy(cg, m->d_hist, (size_t)RS_CG * RS_CG * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ch, m->d_hist + RS_CG * RS_CG, (size_t)RS_CH * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(totals, m->d_hist + RS_LDS_CELLS, 4 * 8, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// the whole text to `path`; BSX_ERR_IO when it cannot be written
+static int meth_write_text(const char *path, const std::string &o)
+{
+    FILE *f = fopen(path, "w");
+    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    const bool bad = fwrite(o.data(), 1, o.size(), f) != o.size();
+    if ((fclose(f) != 0) | bad) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_write_read_stats(bsx_meth *m, const char *path)
+{
+    if (!m || !path) return BSX_ERR_ARG;
+    try {
+        std::vector<uint64_t> cg((size_t)RS_CG * RS_CG), ch(RS_CH);
+        uint64_t tot[4] = {0, 0, 0, 0};
+        const int rc = bsx_meth_read_stats_fetch(m, cg.data(), ch.data(), tot);
+        if (rc) return rc;
+        std::string o = "kind\tcalls\tmeth\treads\n";
+        char line[96];
+        for (int n = 0; n < RS_CG; n++)
+            for (int me = 0; me <= n; me++)
+                if (cg[(size_t)n * RS_CG + me]) o.append(line, (size_t)snprintf(line, sizeof(line), "CG\t%d\t%d\t%llu\n", n, me, (u64)cg[(size_t)n * RS_CG + me]));
+        o.append(line, (size_t)snprintf(line, sizeof(line), "CG\t>%d\t.\t%llu\n", BSX_RS_CG_MAX, (u64)tot[1]));
+        for (int k = 0; k < BSX_RS_CH_MAX; k++) o.append(line, (size_t)snprintf(line, sizeof(line), "CH\t.\t%d\t%llu\n", k, (u64)ch[k]));
+        o.append(line, (size_t)snprintf(line, sizeof(line), "CH\t.\t%d+\t%llu\n", BSX_RS_CH_MAX, (u64)ch[BSX_RS_CH_MAX]));
+        o.append(line, (size_t)snprintf(line, sizeof(line), "# reads\t%llu\n# CH calls\t%llu\n# CH methylated\t%llu\n", (u64)tot[0], (u64)tot[2], (u64)tot[3]));
+        if (tot[2]) o.append(line, (size_t)snprintf(line, sizeof(line), "# CH ratio\t%.5f\n", (double)tot[3] / (double)tot[2]));
+        else o += "# CH ratio\tNA\n";
+        return meth_write_text(path, o);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
+    }
+}
+
+extern "C" int bsx_meth_set_pdr(bsx_meth *m, uint32_t min_cpg)
+{
+    if (!m) return BSX_ERR_ARG;
+    if ((min_cpg != 0) == (m->d_pdr != nullptr)) { m->min_cpg = min_cpg; return BSX_OK;}  // another threshold at any time: the cells are the same
+    if (m->index_base) { g_bsx_err = "bsx_meth_set_pdr on or off after alignments have been added"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!min_cpg) {
+        (void)hipFree(m->d_pdr);
+        m->d_pdr = nullptr; m->min_cpg = 0;
+        return BSX_OK;
+    }
+    const int rc = meth_zeroed_cells(m, &m->d_pdr, (size_t)(m->chr_off.back() + 16));
+    if (rc == BSX_OK) m->min_cpg = min_cpg;
+    return rc;
+}
+
+extern "C" int bsx_meth_pdr_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_reads, uint32_t *n_rows)
+{
+    if (!m || chr >= m->n_chr || !n_rows || !min_reads) return BSX_ERR_ARG;
+    if (!m->d_pdr) { g_bsx_err = "PDR is off (bsx_meth_set_pdr)"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    const u64 g0 = m->chr_off[chr], n = m->chr_off[chr + 1] - g0;
+    const size_t nblk = (size_t)((n + 1023) / 1024);
+    *n_rows = 0; m->pdr_last_rows = 0;
+    if (!nblk) return BSX_OK;
+    int rc = meth_block_buffers(m, nblk);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pdr_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const u64 *)m->d_pdr, g0, n, min_reads, m->d_blk);
+    HIP_TRY(hipGetLastError());
+    rc = meth_scan_blocks(m, nblk);
+    if (rc) return rc;
+    uint32_t rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (rows > m->pdr_out_cap) {
+        for (int k = 0; k < 3; k++) { if (m->d_pdr_out[k]) (void)hipFree(m->d_pdr_out[k]); m->d_pdr_out[k] = nullptr; }
+        if (m->d_pdr_letter) (void)hipFree(m->d_pdr_letter);
+        m->d_pdr_letter = nullptr; m->pdr_out_cap = 0;
+        for (int k = 0; k < 3; k++) HIP_TRY(hipMalloc((void **)&m->d_pdr_out[k], (size_t)rows * 4));
+        HIP_TRY(hipMalloc((void **)&m->d_pdr_letter, rows));
+        m->pdr_out_cap = rows;
+    }
+    if (rows) {
+        hipLaunchKernelGGL(k_pdr_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const uint8_t *)m->d_ref, (const u64 *)m->d_pdr, g0, n, min_reads,
+                           (const uint32_t *)m->d_blk_start, m->d_pdr_out[0], m->d_pdr_out[1], m->d_pdr_out[2], m->d_pdr_letter);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    *n_rows = rows; m->pdr_last_rows = rows;
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_pdr_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *reads, uint32_t *discordant)
+{
+    if (!m || !pos0 || !reads || !discordant) return BSX_ERR_ARG;
+    if (!m->d_pdr) { g_bsx_err = "PDR is off (bsx_meth_set_pdr)"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!m->pdr_last_rows) return BSX_OK;
+    uint32_t *const out[3] = {pos0, reads, discordant};
+    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpy(out[k], m->d_pdr_out[k], (size_t)m->pdr_last_rows * 4, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -1213,7 +1525,53 @@ int write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint3
     return BSX_OK;
 }
 
+int write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
+{
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
+    FILE *f = closer.f;
+    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    fputs("chr\tpos\tstrand\treads\tdiscordant\tPDR\n", f);
+    std::vector<uint32_t> pos, reads, disc;
+    std::vector<uint8_t> letter;
+    uint64_t total = 0;
+    for (const uint32_t c : sorted_chromosomes(m)) {
+        uint32_t rows = 0;
+        int rc = bsx_meth_pdr_report_chr(m, c, min_reads, &rows);
+        if (rc) return rc;
+        if (!rows) continue;
+        pos.resize(rows); reads.resize(rows); disc.resize(rows); letter.resize(rows);
+        rc = bsx_meth_pdr_fetch_rows(m, pos.data(), reads.data(), disc.data());
+        if (rc) return rc;
+        if (hipMemcpy(letter.data(), m->d_pdr_letter, rows, hipMemcpyDeviceToHost) != hipSuccess) return BSX_ERR_DEVICE;
+        const char *name = m->names[c].c_str();
+        format_rows(f, rows, 40, [&](size_t i, std::string &o) {
+            char num[96];
+            o += name;
+            o.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%c\t%u\t%u\t%.3f\n", pos[i] + 1, letter[i] == 'C' ? '+' : '-', reads[i], disc[i], (double)disc[i] / (double)reads[i]));
+        });
+        total += rows;
+    }
+    closer.f = nullptr;
+    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    if (n_rows) *n_rows = total;
+    return BSX_OK;
+}
+
 }  // namespace
+
+extern "C" int bsx_meth_write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
+{
+    if (!m || !path || !min_reads || m->names.size() != m->n_chr) return BSX_ERR_ARG;
+    if (n_rows) *n_rows = 0;
+    if (!m->d_pdr) { g_bsx_err = "PDR is off (bsx_meth_set_pdr)"; return BSX_ERR_STATE; }
+    try {
+        return write_pdr(m, path, min_reads, n_rows);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
+    }
+}
 
 extern "C" int bsx_meth_write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth)
 {

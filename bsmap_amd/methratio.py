@@ -19,7 +19,12 @@ SNP) and corrects the depth by that share or skips the position, with their 12-c
 CG,CHG,CHH` lists the cytosines of those contexts only; `-w/--wig FILE` with `-b/--wig-bin N` (default 25) writes a wiggle track of the pooled
 methylation ratio per bin of N nt.  Extension: `--regions BED --region-out FILE` writes one pooled ratio per BED interval (promoters, CpG islands, capture
 targets).  Both are sums of the counters on the GPU (bsx_meth_bins, bsx_meth_regions) under the table's row rule (-m, -x, -i; after -g), not a pass
-over the table's text."""
+over the table's text.  Per-read extensions (a call = a letter that enters a cytosine's depth, counted per alignment line by the k_meth_reads kernel
+ahead of the pile-up): `--nonconv-filter N` drops every read with N or more methylated non-CpG calls (Bismark's filter_non_conversion) from every output and
+from "valid mappings"; `--read-stats FILE` writes the histogram of reads by their CpG calls / methylated CpG calls and by their methylated non-CpG calls, the
+curve N is read off (it does not depend on N); `--pdr FILE` writes, per CpG position, the reads with at least `--pdr-min-cpg K` (default 4) CpG calls that
+cover it and how many of them are discordant (neither all methylated nor all unmethylated): the proportion of discordant reads of Landau et al. 2014, for
+positions with at least `--pdr-min-reads R` (default 1) such reads, after the `-g` fold."""
 import ctypes as C
 import sys
 import time
@@ -28,6 +33,7 @@ import numpy as np
 
 from . import lib, _check
 
+RS_CG, RS_CH = 32, 64  # BSX_RS_CG_MAX + 1, BSX_RS_CH_MAX + 1 of include/bsx.h: bsx_meth_read_stats_fetch fills cg[RS_CG][RS_CG], ch[RS_CH], totals[4]
 MBIAS_CYCLES = 1024  # BSX_MBIAS_CYCLES of include/bsx.h: bsx_meth_mbias_fetch fills [4][4][MBIAS_CYCLES][2] uint64
 MBIAS_STRANDS = ("++", "-+", "+-", "--")
 MBIAS_CONTEXTS = ("CG", "CHG", "CHH", "CN")
@@ -62,6 +68,15 @@ def _bind():
     L.bsx_meth_bins.argtypes = [vp, u32, u32, u32, u64, vp, vp]
     L.bsx_meth_write_regions.argtypes = [vp, C.c_char_p, C.c_char_p, u32, vp, vp]
     L.bsx_meth_write_wig.argtypes = [vp, C.c_char_p, u32, u32]
+    L.bsx_meth_set_nonconv.argtypes = [vp, u32]
+    L.bsx_meth_nonconv_dropped.argtypes = [vp, vp]
+    L.bsx_meth_set_read_stats.argtypes = [vp, i32]
+    L.bsx_meth_read_stats_fetch.argtypes = [vp, vp, vp, vp]
+    L.bsx_meth_write_read_stats.argtypes = [vp, C.c_char_p]
+    L.bsx_meth_set_pdr.argtypes = [vp, u32]
+    L.bsx_meth_pdr_report_chr.argtypes = [vp, u32, u32, vp]
+    L.bsx_meth_pdr_fetch_rows.argtypes = [vp, vp, vp, vp]
+    L.bsx_meth_write_pdr.argtypes = [vp, C.c_char_p, u32, vp]
     L._meth_bound = True
     return L
 
@@ -72,6 +87,13 @@ def mbias_fetch(L, h):
     over = C.c_uint64()
     _check(L.bsx_meth_mbias_fetch(h, cells.ctypes.data, C.byref(over)))
     return cells, over.value
+
+
+def read_stats_fetch(L, h):
+    """the read histogram of a handle: cg[n_cg][m_cg] and ch[min(m_ch, 63)] as uint64, and the totals (reads, cg_over, ch_calls, ch_meth)"""
+    cg, ch, tot = np.zeros((RS_CG, RS_CG), np.uint64), np.zeros(RS_CH, np.uint64), np.zeros(4, np.uint64)
+    _check(L.bsx_meth_read_stats_fetch(h, cg.ctypes.data, ch.ctypes.data, tot.ctypes.data))
+    return cg, ch, tuple(int(x) for x in tot)
 
 
 def load_reference(path, chroms):
@@ -91,9 +113,20 @@ def load_reference(path, chroms):
 
 
 def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=False, rm_dup=False, trim_fillin=2, combine_CpG=False,
-        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0, ct_snp="no-action", context=None, wig=None, wig_bin=25, regions=None, region_out=None):
+        min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0, ct_snp="no-action", context=None, wig=None, wig_bin=25, regions=None, region_out=None,
+        nonconv_filter=0, read_stats=None, pdr=None, pdr_min_cpg=None, pdr_min_reads=None):
     """returns the summary line the reference prints on stdout; ct_snp: one of CT_SNP_MODES, context: names of CONTEXT_BITS to list (None: all);
-    wig: wiggle file of the pooled ratio per bin of wig_bin nt; regions / region_out: BED file in, one pooled ratio per interval out"""
+    wig: wiggle file of the pooled ratio per bin of wig_bin nt; regions / region_out: BED file in, one pooled ratio per interval out;
+    nonconv_filter: drop reads with that many methylated non-CpG calls (0: off); read_stats: file of the read histogram; pdr: file of the proportion of
+    discordant reads, over reads with pdr_min_cpg (default 4) CpG calls, for positions with pdr_min_reads (default 1) of them"""
+    if nonconv_filter < 0:
+        raise ValueError("nonconv_filter cannot be negative")
+    if pdr is None and (pdr_min_cpg is not None or pdr_min_reads is not None):
+        raise ValueError("pdr_min_cpg and pdr_min_reads need pdr")
+    pdr_min_cpg = 4 if pdr_min_cpg is None else pdr_min_cpg
+    pdr_min_reads = 1 if pdr_min_reads is None else pdr_min_reads
+    if pdr_min_cpg < 1 or pdr_min_reads < 1:
+        raise ValueError("pdr_min_cpg and pdr_min_reads are at least 1")
     if wig_bin < 1:
         raise ValueError("wig_bin must be at least 1")
     if (regions is None) != (region_out is None):
@@ -119,6 +152,12 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
             _check(L.bsx_meth_set_ct_snp(h, CT_SNP_MODES.index(ct_snp)))
         if context is not None:
             _check(L.bsx_meth_set_contexts(h, sum(CONTEXT_BITS[x] for x in set(context))))
+        if nonconv_filter:
+            _check(L.bsx_meth_set_nonconv(h, nonconv_filter))
+        if read_stats is not None:
+            _check(L.bsx_meth_set_read_stats(h, 1))
+        if pdr is not None:
+            _check(L.bsx_meth_set_pdr(h, pdr_min_cpg))
         for infile in infiles:
             disp("reading %s ..." % infile)
             ext = infile[-4:].upper()
@@ -127,6 +166,13 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
         if mbias:
             disp("writing %s ..." % mbias)
             _check(L.bsx_meth_write_mbias(h, mbias.encode()))
+        if nonconv_filter:
+            ndropped = C.c_uint64()
+            _check(L.bsx_meth_nonconv_dropped(h, C.byref(ndropped)))
+            disp("%d reads with %d or more methylated non-CpG calls dropped" % (ndropped.value, nonconv_filter))
+        if read_stats is not None:
+            disp("writing %s ..." % read_stats)
+            _check(L.bsx_meth_write_read_stats(h, read_stats.encode()))
         if combine_CpG:
             disp("combining CpG methylation from both strands ...")
             _check(L.bsx_meth_combine_cpg(h))
@@ -134,6 +180,9 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
         nc, nd, nmap = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(L.bsx_meth_write_table(h, outfile.encode(), 0, None, None, min_depth, 1 if meth0 else 0, C.byref(nc), C.byref(nd)))
         _check(L.bsx_meth_valid_mappings(h, C.byref(nmap)))
+        if pdr is not None:
+            disp("writing %s ..." % pdr)
+            _check(L.bsx_meth_write_pdr(h, pdr.encode(), pdr_min_reads, None))
         if wig is not None:
             disp("writing %s ..." % wig)
             _check(L.bsx_meth_write_wig(h, wig.encode(), wig_bin, min_depth))
@@ -154,7 +203,17 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
 def build_parser():
     """the command line with the reference's option letters (methratio.py:3-17) and the extensions"""
     import argparse
-    ap = argparse.ArgumentParser(prog="methratio", description="methylation ratios from BSMAP mapping files (BSP, SAM or BAM), pile-up on the GPU")
+    class Parser(argparse.ArgumentParser):
+        def parse_args(self, args=None, namespace=None):
+            o = super().parse_args(args, namespace)
+            if o.pdr is None and o.pdr_only:
+                self.error("%s needs --pdr" % ", ".join(o.pdr_only))
+            return o
+    class PdrOnly(argparse.Action):  # stores the value and remembers that the option was given
+        def __call__(self, parser, namespace, values, option_string=None):
+            setattr(namespace, self.dest, values)
+            namespace.pdr_only = namespace.pdr_only + [option_string]
+    ap = Parser(prog="methratio", description="methylation ratios from BSMAP mapping files (BSP, SAM or BAM), pile-up on the GPU")
     ap.add_argument("-o", "--out", dest="outfile", required=True, help="table to write")
     ap.add_argument("-d", "--ref", dest="reffile", required=True, help="reference FASTA the reads were mapped to")
     ap.add_argument("-c", "--chr", dest="chroms", default="", help="comma-separated sequence names to keep (default: every sequence)")
@@ -193,6 +252,23 @@ def build_parser():
     ap.add_argument("-b", "--wig-bin", dest="wig_bin", type=bin_width, default=25, metavar="N", help="bin width of the wiggle track in nt (default 25)")
     ap.add_argument("--regions", dest="regions", default=None, metavar="BED", help="intervals (BED: name, start, end, optional label) to pool the methylation over (extension)")
     ap.add_argument("--region-out", dest="region_out", default=None, metavar="FILE", help="table to write for --regions: one pooled ratio per interval, in the BED file's order")
+    def at_least(lowest, what):
+        def parse(txt):
+            n = int(txt)
+            if n < lowest:
+                raise argparse.ArgumentTypeError("%s is at least %d" % (what, lowest))
+            return n
+        return parse
+    ap.add_argument("--nonconv-filter", dest="nonconv_filter", type=at_least(0, "the threshold"), default=0, metavar="N",
+                    help="drop reads with N or more methylated non-CpG calls: reads the bisulfite conversion missed (extension, default 0: off)")
+    ap.add_argument("--read-stats", dest="read_stats", default=None, metavar="FILE",
+                    help="write the histogram of reads by CpG calls / methylated CpG calls and by methylated non-CpG calls (extension)")
+    ap.add_argument("--pdr", dest="pdr", default=None, metavar="FILE", help="write the proportion of discordant reads per CpG position (extension)")
+    ap.set_defaults(pdr_only=[])
+    ap.add_argument("--pdr-min-cpg", dest="pdr_min_cpg", action=PdrOnly, type=at_least(1, "the number of CpG calls"), default=4, metavar="K",
+                    help="CpG calls a read needs to count for --pdr (default 4)")
+    ap.add_argument("--pdr-min-reads", dest="pdr_min_reads", action=PdrOnly, type=at_least(1, "the number of reads"), default=1, metavar="R",
+                    help="such reads a position needs for a row of --pdr (default 1)")
     ap.add_argument("infiles", nargs="+", help="mapping files written by bsmap: *.sam / *.bam by their format, anything else as BSP")
     return ap
 
@@ -203,7 +279,8 @@ def main(argv=None):
     sys.stdout.write(run(o.reffile, o.infiles, o.outfile, chroms=o.chroms.split(",") if o.chroms else None, unique=o.unique, pair=o.pair, meth0=o.meth0,
                          rm_dup=o.rm_dup, trim_fillin=o.trim_fillin, combine_CpG=o.combine_CpG, min_depth=o.min_depth, device=o.device, quiet=o.quiet,
                          mbias=o.mbias, trim5=o.trim5, trim3=o.trim3, ct_snp=o.ct_snp, context=o.context, wig=o.wig, wig_bin=o.wig_bin,
-                         regions=o.regions, region_out=o.region_out))
+                         regions=o.regions, region_out=o.region_out, nonconv_filter=o.nonconv_filter, read_stats=o.read_stats, pdr=o.pdr,
+                         pdr_min_cpg=o.pdr_min_cpg if o.pdr is not None else None, pdr_min_reads=o.pdr_min_reads if o.pdr is not None else None))
 
 
 if __name__ == "__main__":

@@ -424,6 +424,49 @@ int bsx_meth_write_regions(bsx_meth *m, const char *bed_path, const char *out_pa
  * "variableStep chrom=<name> span=<bin>" and for every bin with a site, ascending, "<j * bin + 1><TAB><ratio %.3f>".  BSX_ERR_ARG for bin == 0 or a
  * handle without names. */
 int bsx_meth_write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth);
+/* Per-read calls (extensions).  A CALL is what an add puts into depth: a letter of a valid alignment's window over the read strand's own
+ * cytosine (reference C under a "+?" read, G under a "-?" read) that shows the unconverted or the converted letter at a cycle that bsx_meth_set_cycle_trim
+ * does not mask; the reverse calls of the C/T-SNP mode are none.  Its context class is the M-bias tally's (0 CG, 1 CHG, 2 CHH, 3 other; a chromosome end
+ * counts as no letter).  Per valid alignment (per line: the mates of a pair are two reads): n_cg / m_cg = its class-0 calls and the methylated ones among
+ * them, n_ch / m_ch = the same over classes 1 and 2 together; class 3 enters nothing.  Three features use these counts, each off by default; with all three
+ * off an add does exactly what it did without them.
+ *
+ * Non-conversion filter (filter_non_conversion of Bismark): with n >= 1 a valid alignment with m_ch >= n in a LATER add is dropped: it adds nothing to depth,
+ * meth, the C/T-SNP cells, the M-bias tally or the PDR cells, is not a valid mapping (bsx_meth_valid_mappings) and is counted in bsx_meth_nonconv_dropped.
+ * The duplicate filter of rm_dup runs first, on all alignments: a dropped read that owns a fragment end still suppresses its duplicates.  n = 0: off.  May be
+ * set at any time. */
+int bsx_meth_set_nonconv(bsx_meth *m, uint32_t n);
+int bsx_meth_nonconv_dropped(bsx_meth *m, uint64_t *n);
+/* Read histogram: with on != 0 allocates (zeroed) the cells below and every later add tallies every valid alignment, those the filter then drops
+ * included (the histogram does not depend on the filter's threshold: it is what the threshold is read from).  cg[n][m], 0 <= m <= n <= BSX_RS_CG_MAX:
+ * reads with n_cg == n and m_cg == m; ch[k], k = min(m_ch, BSX_RS_CH_MAX): reads by methylated non-CpG calls, the last cell is "BSX_RS_CH_MAX or more";
+ * totals: reads, cg_over (reads with n_cg > BSX_RS_CG_MAX, in no cg cell), ch_calls (sum of n_ch), ch_meth (sum of m_ch).  on == 0 frees it.  BSX_ERR_STATE
+ * once alignments have been added. */
+#define BSX_RS_CG_MAX 31
+#define BSX_RS_CH_MAX 63
+int bsx_meth_set_read_stats(bsx_meth *m, int on);
+/* the histogram so far; every pointer is needed (BSX_ERR_ARG).  BSX_ERR_STATE when the histogram is off */
+int bsx_meth_read_stats_fetch(bsx_meth *m, uint64_t *cg /* [BSX_RS_CG_MAX + 1][BSX_RS_CG_MAX + 1] */, uint64_t *ch /* [BSX_RS_CH_MAX + 1] */,
+                              uint64_t *totals /* [4]: reads, cg_over, ch_calls, ch_meth */);
+/* the histogram as a tab-separated file: header "kind calls meth reads"; "CG <n> <m> <count>" per non-zero cg cell, n then m ascending; "CG >31 . <cg_over>";
+ * "CH . <k> <count>" for k = 0..62 and "CH . 63+ <count>", zeros included; then "# reads <reads>", "# CH calls <ch_calls>", "# CH methylated <ch_meth>" and
+ * "# CH ratio <ch_meth / ch_calls as %.5f, or NA without a call>".  BSX_ERR_STATE when the histogram is off */
+int bsx_meth_write_read_stats(bsx_meth *m, const char *path);
+/* Proportion of discordant reads (PDR; Landau et al., Cancer Cell 2014): with min_cpg >= 1 a valid, not dropped alignment with n_cg >= min_cpg is ELIGIBLE,
+ * and DISCORDANT when 0 < m_cg < n_cg.  Every CG call of an eligible read adds one to `reads` at the call's reference position (the C under "+?" reads,
+ * the G under "-?" reads) and, if the read is discordant, one to `discordant` there.  One zeroed uint64 per reference letter, low word reads, high word
+ * discordant, allocated by the first non-zero min_cpg (BSX_ERR_NOMEM when it cannot be had); bsx_meth_combine_cpg folds the cells like depth / meth.
+ * min_cpg = 0: off, frees the cells.  Going between 0 and non-zero is BSX_ERR_STATE once alignments have been added; another non-zero value applies to
+ * later adds at any time. */
+int bsx_meth_set_pdr(bsx_meth *m, uint32_t min_cpg);
+/* PDR rows of one chromosome in position order: the positions with reads >= min_reads (min_reads >= 1, else BSX_ERR_ARG), whatever min_depth, the context
+ * filter and the C/T-SNP mode are.  BSX_ERR_STATE when PDR is off */
+int bsx_meth_pdr_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_reads, uint32_t *n_rows);
+int bsx_meth_pdr_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *reads, uint32_t *discordant);   /* the rows of the last pdr_report_chr */
+/* the PDR rows of every chromosome in sorted name order (the table's) as a tab-separated file: header "chr pos strand reads discordant PDR", rows with the
+ * 1-based position, "+" over a C and "-" over a G, and discordant / reads as "%.3f".  Needs a handle that knows its names, else BSX_ERR_ARG; n_rows may be
+ * NULL.  BSX_ERR_STATE when PDR is off */
+int bsx_meth_write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows);
 
 #ifdef __cplusplus
 }

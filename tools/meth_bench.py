@@ -4,8 +4,11 @@ at uniform positions, all four strands, reads = reference letters with bisulfite
 run under `rocprofv3 --kernel-trace --stats` for the kernel-only times.  `--ct-snp correct|skip` turns the C/T-SNP mode on (one more 64-bit cell per
 reference letter, reverse calls in the pile-up, the SNP tests in the report).  `--wig-bin B[,B...]` times bsx_meth_bins over all chromosomes and
 `--regions N,LEN[;N,LEN...]` bsx_meth_regions over N intervals of LEN nt at uniform positions (made here, no file), both with their copies to the host and
-`--repeat` times each, in the order given (the order of their launches in a kernel trace).
-usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
+`--repeat` times each, in the order given (the order of their launches in a kernel trace).  `--nonconv-filter N`, `--read-stats` and `--pdr` (with
+`--pdr-min-cpg K`) turn the per-read pass on (k_meth_reads ahead of the pile-up: DESIGN §3.10); the JSON line then carries the dropped reads, the histogram's
+totals and the PDR rows.  (The reads here keep 30 % of ALL their cytosines, whatever the context: nearly every read has three methylated non-CpG calls, so
+`--nonconv-filter 3` drops nearly all of them and the pile-up behind it has little left to do; a threshold such as 40 drops nearly none.)
+usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,6 +25,10 @@ def main():
     ap.add_argument("--wig-bin", dest="wig_bin", default="")
     ap.add_argument("--regions", dest="regions", default="")
     ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--nonconv-filter", dest="nonconv_filter", type=int, default=0)
+    ap.add_argument("--read-stats", dest="read_stats", action="store_true")
+    ap.add_argument("--pdr", dest="pdr", action="store_true")
+    ap.add_argument("--pdr-min-cpg", dest="pdr_min_cpg", type=int, default=4)
     a = ap.parse_args()
     L = MR._bind()
     rng = np.random.default_rng(1)
@@ -32,6 +39,12 @@ def main():
     B._check(L.bsx_meth_create(len(lens), lens.ctypes.data, 1, 0, C.byref(h)))
     if a.ct_snp != "no-action":
         B._check(L.bsx_meth_set_ct_snp(h, MR.CT_SNP_MODES.index(a.ct_snp)))
+    if a.nonconv_filter:
+        B._check(L.bsx_meth_set_nonconv(h, a.nonconv_filter))
+    if a.read_stats:
+        B._check(L.bsx_meth_set_read_stats(h, 1))
+    if a.pdr:
+        B._check(L.bsx_meth_set_pdr(h, a.pdr_min_cpg))
     letters = np.frombuffer(b"ACGT", np.uint8)
     chunks = []
     for c, n in enumerate(lens.tolist()):
@@ -67,6 +80,19 @@ def main():
         rows += nr.value; cov += cv.value
     dt_rep = time.perf_counter() - t1
     extra = {}
+    if a.nonconv_filter:
+        nd = C.c_uint64()
+        B._check(L.bsx_meth_nonconv_dropped(h, C.byref(nd)))
+        extra.update(nonconv_filter=a.nonconv_filter, dropped=nd.value)
+    if a.read_stats:
+        extra["read_stats_totals"] = dict(zip(("reads", "cg_over", "ch_calls", "ch_meth"), MR.read_stats_fetch(L, h)[2]))
+    if a.pdr:
+        t4, pdr_rows = time.perf_counter(), 0
+        for c in range(len(lens)):
+            nr = C.c_uint32()
+            B._check(L.bsx_meth_pdr_report_chr(h, c, 1, C.byref(nr)))
+            pdr_rows += nr.value
+        extra.update(pdr_min_cpg=a.pdr_min_cpg, pdr_rows=pdr_rows, pdr_report_s_all_chromosomes=round(time.perf_counter() - t4, 3))
     for width in [int(x) for x in a.wig_bin.split(",") if x]:
         out = np.zeros((int(lens.max()) // width + 1, 5), np.uint64)
         nb, took = C.c_uint64(), []
