@@ -9,6 +9,8 @@
 //   k_meth_pile_mbias   the same pile-up in a persistent grid that also tallies every call by strand, context and read cycle (M-bias, --mbias) in LDS
 //   k_meth_cpg     fold the G of every CG into its C
 //   k_meth_reads   per-read call counts ahead of the pile-up: non-conversion filter, read histogram, PDR cells; off by default
+//   k_meth_epi     per read, the methylation pattern of every four neighbouring CpGs it covers, tallied per window (epialleles); off by default;
+//                  k_cpg_count / k_cpg_emit build the CpG index it needs, k_epi_count / k_epi_emit list its rows
 // With the C/T-SNP mode on (bsx_meth_set_ct_snp, an extension: -i of later BSMAP releases) the same pile-up pass also counts, per reference position, what the reads
 // of the OTHER reference strand show there (G over an intact C, A over a C->T SNP), and the row selection and the table use those two counters.
 //   k_meth_count / k_meth_emit   ordered compaction of the positions the table will list
@@ -39,6 +41,7 @@
 
 #include "bsx_cpus.h"
 #include "bsx_internal.h"
+#include "bsx_meth_epi.h"
 #include "bsx_meth_parse.h"
 #include "bsx_meth_tiles.h"
 
@@ -391,6 +394,186 @@ __global__ __launch_bounds__(256) void k_pdr_emit(const uint8_t *ref, const u64 
     }
 }
 
+// ---- epiallele patterns per window of four CpGs ----
+// The CpG index of the handle (meth_epi_index): the chromosome-relative positions of the C of every reference CpG, all chromosomes in order (a CpG's index in
+// that list is its GLOBAL ordinal; the host keeps the ordinal of every chromosome's first CpG), and the rank directory `dir`: the number of CpGs ahead of
+// every 64-letter block of the concatenated text, blocks counted from letter 0 of the text (not of a chromosome).  cells: 16 counters per CpG, those of the
+// window that STARTS at this CpG; n_cpg: the number of CpGs, the bound of every index into cells.
+struct EpiDev {
+    const uint32_t *dir;
+    uint32_t *cells;
+    u64 n_cpg;
+};
+
+// Whether letter x of the concatenated text is the C of a reference CpG.  The G must lie in x's own chromosome: a C at the end of one sequence and a G at
+// the start of the next are no CpG (the trap of k_meth_cpg; the search runs only behind a "CG").  The text is zero-padded behind M.total.
+__device__ __forceinline__ bool meth_is_cpg(const MethDev &M, u64 x)
+{
+    if (x + 1 >= M.total || M.ref[x] != 'C' || M.ref[x + 1] != 'G') return false;
+    uint32_t lo = 0, hi = M.n_chr;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (M.chr_off[mid] <= x) lo = mid; else hi = mid; }
+    return x + 1 < M.chr_off[lo + 1];
+}
+
+// The number of reference CpGs whose C lies ahead of letter g (g <= M.total): the directory's count for g's block, and for the rest of the way one 64-letter
+// load, a ballot and a masked popcount.  Every lane of the wave calls it with the same g.  (A CpG whose C is letter 63 of a block has its G in the next one:
+// meth_is_cpg reads it from there.)
+__device__ __forceinline__ uint32_t meth_cpg_rank(const MethDev &M, const uint32_t *dir, u64 g, int lane)
+{
+    const u64 bal = __ballot(meth_is_cpg(M, (g & ~63ull) + (u64)lane));
+    return dir[g >> 6] + (uint32_t)__builtin_popcountll(bal & ((1ull << (g & 63)) - 1));
+}
+
+// one wave per 64-letter block: its number of CpGs (cnt[block]; the directory is the exclusive scan of these) ...
+__global__ __launch_bounds__(256) void k_cpg_count(MethDev M, u64 n_blocks, uint32_t *cnt)
+{
+    const u64 b = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n_blocks) return;
+    const u64 bal = __ballot(meth_is_cpg(M, b * 64 + (threadIdx.x & 63)));
+    if ((threadIdx.x & 63) == 0) cnt[b] = (uint32_t)__builtin_popcountll(bal);
+}
+
+// ... and their positions, each CpG at its ordinal
+__global__ __launch_bounds__(256) void k_cpg_emit(MethDev M, u64 n_blocks, const uint32_t *dir, uint32_t *pos)
+{
+    const u64 b = (u64)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n_blocks) return;
+    const int lane = threadIdx.x & 63;
+    const u64 x = b * 64 + lane;
+    const bool cpg = meth_is_cpg(M, x);
+    const u64 bal = __ballot(cpg);
+    if (!cpg) return;
+    uint32_t lo = 0, hi = M.n_chr;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (M.chr_off[mid] <= x) lo = mid; else hi = mid; }
+    pos[dir[b] + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))] = (uint32_t)(x - M.chr_off[lo]);
+}
+
+// one wave per chromosome border: the global ordinal of the first CpG at or behind it
+__global__ __launch_bounds__(64) void k_cpg_chr_first(MethDev M, const uint32_t *dir, uint32_t *chr_first)
+{
+    const uint32_t r = meth_cpg_rank(M, dir, M.chr_off[blockIdx.x], (int)threadIdx.x);
+    if (threadIdx.x == 0) chr_first[blockIdx.x] = r;
+}
+
+// The tally: one wave per alignment, behind k_meth_reads (B.drop holds this add's verdicts, so meth_window admits the valid, not dropped alignments) and ahead
+// of the pile-up.  The CpGs of the read are the lanes at a reference CpG's call position (the C under a '+?' read, the G under a '-?' read); they have
+// consecutive ordinals from ord0, the rank of the first letter that can be the C of one of them.  Per 64-letter step three ballots: those lanes (cmask),
+// the lanes that make a class-0 call (vmask: state M or U; a CpG lane outside it is X) and the methylated ones among them (mmask).  A CpG lane forms the
+// window that ENDS at its CpG: it finds the three set bits of cmask below its own, reads their states from vmask / mmask, and where cmask has fewer it takes
+// them from the carry, the states of the last three CpGs of the steps before (bit 0 the latest).  So a window that straddles a step border is counted like
+// any other, and a read may have any number of CpGs.  One 32-bit atomic add per window without an X.
+__global__ __launch_bounds__(256) void k_meth_epi(MethDev M, AlnBatch B, EpiDev E)
+{
+    const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= B.n) return;
+    MethWindow W;
+    if (!meth_window(M, B, i, W) || W.pos < 0) return;  // (a negative position makes no call: meth_calls)
+    const int64_t len = W.hi - W.lo;
+    if (len < 7) return;                                // four CpGs have call positions at least 6 letters apart
+    const bool plus = !(W.st & 1);
+    const uint8_t *s = B.seq + B.seq_off[i] + W.lo;
+    const u64 c0 = M.chr_off[W.c], c1 = M.chr_off[W.c + 1], g0 = c0 + (u64)W.pos;
+    const uint32_t ord0 = meth_cpg_rank(M, E.dir, plus || g0 == c0 ? g0 : g0 - 1, lane);
+    uint32_t seen = 0, carry_n = 0;    // CpGs of the steps before, and how many of them the carry holds (at most 3)
+    uint32_t carry_v = 0, carry_m = 0;
+    for (int64_t k0 = 0; k0 < len; k0 += 64) {  // uniform bounds: every lane takes part in the ballots
+        const int64_t k = k0 + lane;
+        bool m = false, cpg = false;
+        int cls = -1;
+        if (k < len) {
+            const u64 g = g0 + (u64)k;
+            cpg = plus ? (M.ref[g] == 'C' && g + 1 < c1 && M.ref[g + 1] == 'G') : (M.ref[g] == 'G' && g >= c0 + 1 && M.ref[g - 1] == 'C');
+            if (cpg) cls = meth_call_class(M, B, W, s, c0, c1, g0, k, m);  // 0 or -1 here: the position's class is CG
+        }
+        const u64 cmask = __ballot(cpg);
+        if (!cmask) continue;
+        const u64 vmask = __ballot(cls == 0), mmask = __ballot(cls == 0 && m);
+        if (cpg) {
+            u64 below = cmask & ((1ull << lane) - 1);
+            const uint32_t r = (uint32_t)__builtin_popcountll(below);
+            bool ok = cls == 0 && seen + r >= 3;
+            uint32_t pattern = m ? 8u : 0u, q = 0;
+            for (int t = 2; t >= 0; t--) {  // the CpG 3 - t places to the left gives bit t
+                if (below) {
+                    const int p = 63 - __builtin_clzll(below);
+                    below &= ~(1ull << p);
+                    ok = ok && ((vmask >> p) & 1);
+                    pattern |= (uint32_t)((mmask >> p) & 1) << t;
+                } else {
+                    ok = ok && q < carry_n && ((carry_v >> q) & 1);
+                    pattern |= ((carry_m >> q) & 1) << t;
+                    q++;
+                }
+            }
+            const u64 w = (u64)ord0 + seen + r - 3;  // the window's first CpG
+            if (ok && w + 3 < E.n_cpg) atomicAdd(&E.cells[w * 16 + pattern], 1u);  // (the bound holds by construction: the lanes' CpG test is meth_is_cpg's)
+        }
+        // the carry for the next step: this step's last CpGs, then what the old carry still has to give (all uniform over the wave)
+        uint32_t nv = 0, nm = 0, cnt = 0;
+        for (u64 rem = cmask; rem && cnt < 3; cnt++) {
+            const int p = 63 - __builtin_clzll(rem);
+            rem &= ~(1ull << p);
+            nv |= (uint32_t)((vmask >> p) & 1) << cnt; nm |= (uint32_t)((mmask >> p) & 1) << cnt;
+        }
+        for (uint32_t q = 0; q < carry_n && cnt < 3; q++, cnt++) { nv |= ((carry_v >> q) & 1) << cnt; nm |= ((carry_m >> q) & 1) << cnt; }
+        carry_v = nv; carry_m = nm; carry_n = cnt;
+        seen += (uint32_t)__builtin_popcountll(cmask);
+    }
+}
+
+// Epiallele rows of one chromosome in ordinal order (bsx_meth_epi_report_chr): the count / scan / emit scheme of k_pdr_count / k_pdr_emit over the chromosome's
+// n windows, the first of them at the global ordinal o0, with the rule reads >= min_reads (min_reads >= 1) on the sum of a window's sixteen cells
+__device__ __forceinline__ uint32_t epi_reads(const uint32_t *cells, u64 o, uint4 v[4])
+{
+    const uint4 *c = (const uint4 *)(cells + o * 16);
+    uint32_t sum = 0;
+    for (int q = 0; q < 4; q++) { v[q] = c[q]; sum += v[q].x + v[q].y + v[q].z + v[q].w; }  // (< 2^32 alignments per handle: no carry)
+    return sum;
+}
+
+__global__ __launch_bounds__(256) void k_epi_count(const uint32_t *cells, u64 o0, u64 n, uint32_t min_reads, uint32_t *blk_rows)
+{
+    __shared__ uint32_t s_rows;
+    if (threadIdx.x == 0) s_rows = 0;
+    __syncthreads();
+    uint32_t rows = 0;
+    for (int r = 0; r < 4; r++) {
+        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
+        uint4 v[4];
+        if (k < n) rows += epi_reads(cells, o0 + k, v) >= min_reads;
+    }
+    if (rows) atomicAdd(&s_rows, rows);
+    __syncthreads();
+    if (threadIdx.x == 0) blk_rows[blockIdx.x] = s_rows;
+}
+
+__global__ __launch_bounds__(256) void k_epi_emit(const uint32_t *cells, const uint32_t *cpg_pos, u64 o0, u64 n, uint32_t min_reads, const uint32_t *blk_start,
+                                                  uint32_t *out_pos, uint32_t *out_counts)
+{
+    __shared__ uint32_t s_wave[4];
+    uint32_t base = blk_start[blockIdx.x];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int r = 0; r < 4; r++) {  // windows blockIdx*1024 + r*256 + thread: ascending with (r, thread)
+        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
+        uint4 v[4] = {};
+        const bool row = k < n && epi_reads(cells, o0 + k, v) >= min_reads;
+        const u64 bal = __ballot(row);
+        if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int w = 0; w < wv; w++) off += s_wave[w];
+        if (row) {
+            const u64 o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
+            for (int j = 0; j < 4; j++) out_pos[o * 4 + j] = cpg_pos[o0 + k + j];  // a window has its four CpGs in one chromosome
+            uint4 *oc = (uint4 *)(out_counts + o * 16);
+            for (int q = 0; q < 4; q++) oc[q] = v[q];
+        }
+        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+}
+
 __global__ void k_meth_cpg(MethDev M, u64 *rev, u64 *pdr)
 {
     // every "CG" of every chromosome (occurrences cannot overlap): the G's counters move onto the C  (methratio.py:118-128)
@@ -648,6 +831,13 @@ struct bsx_meth {
     uint8_t *d_pdr_letter = nullptr;                       // and their reference letters
     size_t pdr_out_cap = 0;
     uint32_t pdr_last_rows = 0;
+    int epi = 0;                    // bsx_meth_set_epi
+    bool cpg_built = false;         // the CpG index and the cells below exist (meth_epi_index builds them at the first add or report that needs them)
+    uint32_t *d_cpg_dir = nullptr, *d_cpg_pos = nullptr, *d_epi = nullptr;  // rank directory, positions by ordinal, 16 cells per CpG (EpiDev)
+    std::vector<uint32_t> cpg_first;  // [n_chr + 1] the global ordinal of every chromosome's first CpG, then the number of CpGs
+    uint32_t *d_epi_out[2] = {nullptr, nullptr};  // pos[rows][4], counts[rows][16] of the last bsx_meth_epi_report_chr
+    size_t epi_out_cap = 0;
+    uint32_t epi_last_rows = 0;
     int n_cu = 0;
     hipStream_t stream = nullptr;
     // report buffers of the last bsx_meth_report_chr
@@ -660,13 +850,60 @@ struct bsx_meth {
     MethDev dev() const { MethDev M; M.ref = d_ref; M.chr_off = d_chr_off; M.depth = d_depth; M.meth = d_meth; M.first = d_first; M.total = chr_off.back(); M.n_chr = n_chr; return M; }
 };
 
+// ---- the CpG index of the epiallele tally ----
+static int meth_scan_u32(bsx_meth *m, uint32_t *in, uint32_t *out, size_t n);
+
+static void meth_epi_drop_index(bsx_meth *m)
+{
+    for (uint32_t **q : {&m->d_cpg_dir, &m->d_cpg_pos, &m->d_epi}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    m->cpg_first.clear();
+    m->cpg_built = false; m->epi_last_rows = 0;
+}
+
+// Builds what is missing of EpiDev: per-block counts, their scan (the directory), the ordinal of every chromosome's first CpG, the positions, zeroed cells.
+// Ordinals are 32 bits wide: a text of 2^33 letters or more could hold more CpGs than that and is refused.
+static int meth_epi_index(bsx_meth *m)
+{
+    if (m->cpg_built) return BSX_OK;
+    const u64 total = m->chr_off.back(), n_blocks = (total + 63) / 64;
+    if (total >= (1ull << 33)) { g_bsx_err = "the epiallele tally takes a reference of fewer than 2^33 letters"; return BSX_ERR_LIMIT; }
+    uint32_t *d_cnt = nullptr, *d_first = nullptr;
+    int rc = BSX_OK;
+    auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == BSX_OK) rc = e == hipErrorOutOfMemory ? ((void)hipGetLastError(), BSX_ERR_NOMEM) : bsx_hip_fail(e, "meth_epi_index", __FILE__, __LINE__); };
+    const MethDev M = m->dev();
+    chk(hipMalloc((void **)&d_cnt, (n_blocks + 1) * 4)); chk(hipMalloc((void **)&m->d_cpg_dir, (n_blocks + 1) * 4)); chk(hipMalloc((void **)&d_first, ((size_t)m->n_chr + 1) * 4));
+    if (rc == BSX_OK) chk(hipMemsetAsync(d_cnt + n_blocks, 0, 4, m->stream));
+    if (rc == BSX_OK && n_blocks) { hipLaunchKernelGGL(k_cpg_count, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, m->stream, M, n_blocks, d_cnt); chk(hipGetLastError()); }
+    if (rc == BSX_OK) rc = meth_scan_u32(m, d_cnt, m->d_cpg_dir, (size_t)n_blocks + 1);
+    if (rc == BSX_OK) {
+        hipLaunchKernelGGL(k_cpg_chr_first, dim3(m->n_chr + 1), dim3(64), 0, m->stream, M, (const uint32_t *)m->d_cpg_dir, d_first);
+        chk(hipGetLastError());
+        m->cpg_first.assign((size_t)m->n_chr + 1, 0);
+        chk(hipMemcpyAsync(m->cpg_first.data(), d_first, ((size_t)m->n_chr + 1) * 4, hipMemcpyDeviceToHost, m->stream));
+        chk(hipStreamSynchronize(m->stream));
+    }
+    if (rc == BSX_OK) {
+        const size_t n_cpg = m->cpg_first.back();
+        chk(hipMalloc((void **)&m->d_cpg_pos, (n_cpg + 4) * 4)); chk(hipMalloc((void **)&m->d_epi, (n_cpg + 1) * 64));
+        if (rc == BSX_OK) chk(hipMemsetAsync(m->d_epi, 0, (n_cpg + 1) * 64, m->stream));
+        if (rc == BSX_OK && n_blocks) { hipLaunchKernelGGL(k_cpg_emit, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, m->stream, M, n_blocks, (const uint32_t *)m->d_cpg_dir, m->d_cpg_pos); chk(hipGetLastError()); }
+        if (rc == BSX_OK) chk(hipStreamSynchronize(m->stream));
+    }
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (d_first) (void)hipFree(d_first);
+    if (rc != BSX_OK) { meth_epi_drop_index(m); return rc; }
+    m->cpg_built = true;
+    return BSX_OK;
+}
+
 extern "C" void bsx_meth_destroy(bsx_meth *m)
 {
     if (!m) return;
     (void)hipSetDevice(m->device);
     for (void *q : {(void *)m->d_ref, (void *)m->d_chr_off, (void *)m->d_counts, (void *)m->d_depth, (void *)m->d_meth, (void *)m->d_first, (void *)m->d_blk,
                     (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias, (void *)m->d_rev, (void *)m->d_out_rev[0], (void *)m->d_out_rev[1],
-                    (void *)m->d_hist, (void *)m->d_pdr, (void *)m->d_pdr_out[0], (void *)m->d_pdr_out[1], (void *)m->d_pdr_out[2], (void *)m->d_pdr_letter})
+                    (void *)m->d_hist, (void *)m->d_pdr, (void *)m->d_pdr_out[0], (void *)m->d_pdr_out[1], (void *)m->d_pdr_out[2], (void *)m->d_pdr_letter,
+                    (void *)m->d_cpg_dir, (void *)m->d_cpg_pos, (void *)m->d_epi, (void *)m->d_epi_out[0], (void *)m->d_epi_out[1]})
         if (q) (void)hipFree(q);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
@@ -706,6 +943,7 @@ extern "C" int bsx_meth_set_reference(bsx_meth *m, uint32_t chr, const char *upp
 {
     if (!m || chr >= m->n_chr || !upper_seq) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
+    if (m->cpg_built) meth_epi_drop_index(m);  // other letters, other CpGs: the index and the cells are built again when they are next needed
     HIP_TRY(hipMemcpy(m->d_ref + m->chr_off[chr], upper_seq, m->chr_off[chr + 1] - m->chr_off[chr], hipMemcpyHostToDevice));
     return BSX_OK;
 }
@@ -718,6 +956,7 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
     if ((u64)m->index_base + n >= 0xFFFFFFFFull) return BSX_ERR_LIMIT;
     for (uint32_t i = 0; i < n; i++) if (chr[i] >= m->n_chr || strand[i] > 3) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
+    if (m->epi) { const int erc = meth_epi_index(m); if (erc) return erc; }
     const u64 nbytes = seq_off[n];
     uint32_t *d_chr = nullptr; int64_t *d_pos = nullptr, *d_cut = nullptr; uint8_t *d_strand = nullptr, *d_seq = nullptr, *d_drop = nullptr; int32_t *d_ins = nullptr; u64 *d_off = nullptr;
     int rc = BSX_OK;
@@ -742,6 +981,8 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
             hipLaunchKernelGGL(k_meth_reads, dim3(grid), dim3(RS_BLOCK), 0, m->stream, M, B, R);
             B.drop = d_drop;
         }
+        if (m->epi)  // behind the verdicts of the non-conversion filter, ahead of the pile-up
+            hipLaunchKernelGGL(k_meth_epi, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, EpiDev{m->d_cpg_dir, m->d_epi, (u64)m->cpg_first.back()});
         if (m->d_mbias) {  // the grid comes from the CU count; a batch too small to give every wave an alignment gets fewer blocks (fewer flushes)
             const unsigned waves = MB_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * MB_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
             const MbiasDev D{m->d_mbias, m->d_mbias + MB_CELLS};
@@ -895,14 +1136,17 @@ static int meth_block_buffers(bsx_meth *m, size_t nblk)
     return BSX_OK;
 }
 
-static int meth_scan_blocks(bsx_meth *m, size_t nblk)
+// out[k] = in[0] + .. + in[k - 1] for k < n, on the handle's stream and with its scratch buffer
+static int meth_scan_u32(bsx_meth *m, uint32_t *in, uint32_t *out, size_t n)
 {
     size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
+    HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0u, n, rocprim::plus<uint32_t>(), m->stream));
     if (need > m->temp_cap) { if (m->d_temp) (void)hipFree(m->d_temp); m->d_temp = nullptr; m->temp_cap = 0; HIP_TRY(hipMalloc(&m->d_temp, need)); m->temp_cap = need; }
-    HIP_TRY(rocprim::exclusive_scan(m->d_temp, need, m->d_blk, m->d_blk_start, 0u, nblk + 1, rocprim::plus<uint32_t>(), m->stream));
+    HIP_TRY(rocprim::exclusive_scan(m->d_temp, need, in, out, 0u, n, rocprim::plus<uint32_t>(), m->stream));
     return BSX_OK;
 }
+
+static int meth_scan_blocks(bsx_meth *m, size_t nblk) { return meth_scan_u32(m, m->d_blk, m->d_blk_start, nblk + 1); }
 
 extern "C" int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth, int meth0, uint32_t *n_rows, uint64_t *n_covered, uint64_t *sum_depth)
 {
@@ -1120,6 +1364,78 @@ extern "C" int bsx_meth_pdr_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *re
     if (!m->pdr_last_rows) return BSX_OK;
     uint32_t *const out[3] = {pos0, reads, discordant};
     for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpy(out[k], m->d_pdr_out[k], (size_t)m->pdr_last_rows * 4, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// ---- epiallele patterns ----
+static const char *const EPI_OFF = "the epiallele tally is off (bsx_meth_set_epi)";
+
+extern "C" int bsx_meth_set_epi(bsx_meth *m, int on)
+{
+    if (!m) return BSX_ERR_ARG;
+    if ((on != 0) == (m->epi != 0)) return BSX_OK;
+    if (m->index_base) { g_bsx_err = "bsx_meth_set_epi on or off after alignments have been added"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!on) meth_epi_drop_index(m);
+    m->epi = on != 0;  // the index and the cells are built by the first call that needs them
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_n_cpg(bsx_meth *m, uint32_t chr, uint64_t *n)
+{
+    if (!m || chr >= m->n_chr || !n) return BSX_ERR_ARG;
+    if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    const int rc = meth_epi_index(m);
+    if (rc) return rc;
+    *n = m->cpg_first[chr + 1] - m->cpg_first[chr];
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_epi_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_reads, uint32_t *n_rows)
+{
+    if (!m || chr >= m->n_chr || !n_rows || !min_reads) return BSX_ERR_ARG;
+    if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    int rc = meth_epi_index(m);
+    if (rc) return rc;
+    const u64 o0 = m->cpg_first[chr], n_cpg = m->cpg_first[chr + 1] - o0, n = n_cpg >= 4 ? n_cpg - 3 : 0;  // the chromosome's windows
+    const size_t nblk = (size_t)((n + 1023) / 1024);
+    *n_rows = 0; m->epi_last_rows = 0;
+    if (!nblk) return BSX_OK;
+    rc = meth_block_buffers(m, nblk);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_epi_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const uint32_t *)m->d_epi, o0, n, min_reads, m->d_blk);
+    HIP_TRY(hipGetLastError());
+    rc = meth_scan_blocks(m, nblk);
+    if (rc) return rc;
+    uint32_t rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (rows > m->epi_out_cap) {
+        for (int k = 0; k < 2; k++) { if (m->d_epi_out[k]) (void)hipFree(m->d_epi_out[k]); m->d_epi_out[k] = nullptr; }
+        m->epi_out_cap = 0;
+        HIP_TRY(hipMalloc((void **)&m->d_epi_out[0], (size_t)rows * 16)); HIP_TRY(hipMalloc((void **)&m->d_epi_out[1], (size_t)rows * 64));
+        m->epi_out_cap = rows;
+    }
+    if (rows) {
+        hipLaunchKernelGGL(k_epi_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const uint32_t *)m->d_epi, (const uint32_t *)m->d_cpg_pos, o0, n, min_reads,
+                           (const uint32_t *)m->d_blk_start, m->d_epi_out[0], m->d_epi_out[1]);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    *n_rows = rows; m->epi_last_rows = rows;
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_epi_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *counts)
+{
+    if (!m || !pos0 || !counts) return BSX_ERR_ARG;
+    if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(m->device));
+    if (!m->epi_last_rows) return BSX_OK;
+    HIP_TRY(hipMemcpy(pos0, m->d_epi_out[0], (size_t)m->epi_last_rows * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, m->d_epi_out[1], (size_t)m->epi_last_rows * 64, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -1557,7 +1873,47 @@ int write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_row
     return BSX_OK;
 }
 
+int write_epi(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
+{
+    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
+    FILE *f = closer.f;
+    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    fputs(bsx_meth_epi::header().c_str(), f);
+    std::vector<uint32_t> pos, counts;
+    uint64_t total = 0;
+    for (const uint32_t c : sorted_chromosomes(m)) {
+        uint32_t rows = 0;
+        int rc = bsx_meth_epi_report_chr(m, c, min_reads, &rows);
+        if (rc) return rc;
+        if (!rows) continue;
+        pos.resize((size_t)rows * 4); counts.resize((size_t)rows * 16);
+        rc = bsx_meth_epi_fetch_rows(m, pos.data(), counts.data());
+        if (rc) return rc;
+        const char *name = m->names[c].c_str();
+        format_rows(f, rows, 128, [&](size_t i, std::string &o) { bsx_meth_epi::append_row(o, name, &pos[i * 4], &counts[i * 16]); });
+        total += rows;
+    }
+    closer.f = nullptr;
+    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    if (n_rows) *n_rows = total;
+    return BSX_OK;
+}
+
 }  // namespace
+
+extern "C" int bsx_meth_write_epi(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
+{
+    if (!m || !path || !min_reads || m->names.size() != m->n_chr) return BSX_ERR_ARG;
+    if (n_rows) *n_rows = 0;
+    if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
+    try {
+        return write_epi(m, path, min_reads, n_rows);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
+    }
+}
 
 extern "C" int bsx_meth_write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
 {

@@ -24,7 +24,11 @@ ahead of the pile-up): `--nonconv-filter N` drops every read with N or more meth
 from "valid mappings"; `--read-stats FILE` writes the histogram of reads by their CpG calls / methylated CpG calls and by their methylated non-CpG calls, the
 curve N is read off (it does not depend on N); `--pdr FILE` writes, per CpG position, the reads with at least `--pdr-min-cpg K` (default 4) CpG calls that
 cover it and how many of them are discordant (neither all methylated nor all unmethylated): the proportion of discordant reads of Landau et al. 2014, for
-positions with at least `--pdr-min-reads R` (default 1) such reads, after the `-g` fold."""
+positions with at least `--pdr-min-reads R` (default 1) such reads, after the `-g` fold.  `--epi FILE` (the k_meth_epi kernel over a CpG index
+of the reference) writes, per window of four neighbouring reference CpGs, how many reads show each of the sixteen methylation patterns: a read counts for a
+window when it makes a CpG call at all four, and the `--nonconv-filter`, the cycle trims, `-r` and `-t` apply to it as to every call, while `-g`, `-x`, `-i`
+and `-m` do not touch it; each row carries the epipolymorphism (Landan et al. 2012) and the methylation entropy (Xie et al. 2011) of its sixteen counts,
+for windows with at least `--epi-min-reads R` (default 1) reads."""
 import ctypes as C
 import sys
 import time
@@ -77,6 +81,11 @@ def _bind():
     L.bsx_meth_pdr_report_chr.argtypes = [vp, u32, u32, vp]
     L.bsx_meth_pdr_fetch_rows.argtypes = [vp, vp, vp, vp]
     L.bsx_meth_write_pdr.argtypes = [vp, C.c_char_p, u32, vp]
+    L.bsx_meth_set_epi.argtypes = [vp, i32]
+    L.bsx_meth_n_cpg.argtypes = [vp, u32, vp]
+    L.bsx_meth_epi_report_chr.argtypes = [vp, u32, u32, vp]
+    L.bsx_meth_epi_fetch_rows.argtypes = [vp, vp, vp]
+    L.bsx_meth_write_epi.argtypes = [vp, C.c_char_p, u32, vp]
     L._meth_bound = True
     return L
 
@@ -94,6 +103,16 @@ def read_stats_fetch(L, h):
     cg, ch, tot = np.zeros((RS_CG, RS_CG), np.uint64), np.zeros(RS_CH, np.uint64), np.zeros(4, np.uint64)
     _check(L.bsx_meth_read_stats_fetch(h, cg.ctypes.data, ch.ctypes.data, tot.ctypes.data))
     return cg, ch, tuple(int(x) for x in tot)
+
+
+def epi_fetch(L, h, chr, min_reads=1):
+    """the epiallele rows of one sequence with at least min_reads reads: pos0 as uint32 [rows][4] (the 0-based positions of the four Cs) and counts as
+    uint32 [rows][16] (by pattern: bit j set = CpG j of the window methylated)"""
+    nr = C.c_uint32()
+    _check(L.bsx_meth_epi_report_chr(h, chr, min_reads, C.byref(nr)))
+    pos0, counts = np.zeros((nr.value, 4), np.uint32), np.zeros((nr.value, 16), np.uint32)
+    _check(L.bsx_meth_epi_fetch_rows(h, pos0.ctypes.data, counts.ctypes.data))
+    return pos0, counts
 
 
 def load_reference(path, chroms):
@@ -114,11 +133,12 @@ def load_reference(path, chroms):
 
 def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=False, rm_dup=False, trim_fillin=2, combine_CpG=False,
         min_depth=1, device=0, quiet=True, mbias=None, trim5=0, trim3=0, ct_snp="no-action", context=None, wig=None, wig_bin=25, regions=None, region_out=None,
-        nonconv_filter=0, read_stats=None, pdr=None, pdr_min_cpg=None, pdr_min_reads=None):
+        nonconv_filter=0, read_stats=None, pdr=None, pdr_min_cpg=None, pdr_min_reads=None, epi=None, epi_min_reads=None):
     """returns the summary line the reference prints on stdout; ct_snp: one of CT_SNP_MODES, context: names of CONTEXT_BITS to list (None: all);
     wig: wiggle file of the pooled ratio per bin of wig_bin nt; regions / region_out: BED file in, one pooled ratio per interval out;
     nonconv_filter: drop reads with that many methylated non-CpG calls (0: off); read_stats: file of the read histogram; pdr: file of the proportion of
-    discordant reads, over reads with pdr_min_cpg (default 4) CpG calls, for positions with pdr_min_reads (default 1) of them"""
+    discordant reads, over reads with pdr_min_cpg (default 4) CpG calls, for positions with pdr_min_reads (default 1) of them; epi: file of the
+    epiallele patterns per window of four CpGs, for windows with epi_min_reads (default 1) reads"""
     if nonconv_filter < 0:
         raise ValueError("nonconv_filter cannot be negative")
     if pdr is None and (pdr_min_cpg is not None or pdr_min_reads is not None):
@@ -127,6 +147,11 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
     pdr_min_reads = 1 if pdr_min_reads is None else pdr_min_reads
     if pdr_min_cpg < 1 or pdr_min_reads < 1:
         raise ValueError("pdr_min_cpg and pdr_min_reads are at least 1")
+    if epi is None and epi_min_reads is not None:
+        raise ValueError("epi_min_reads needs epi")
+    epi_min_reads = 1 if epi_min_reads is None else epi_min_reads
+    if epi_min_reads < 1:
+        raise ValueError("epi_min_reads is at least 1")
     if wig_bin < 1:
         raise ValueError("wig_bin must be at least 1")
     if (regions is None) != (region_out is None):
@@ -158,6 +183,8 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
             _check(L.bsx_meth_set_read_stats(h, 1))
         if pdr is not None:
             _check(L.bsx_meth_set_pdr(h, pdr_min_cpg))
+        if epi is not None:
+            _check(L.bsx_meth_set_epi(h, 1))
         for infile in infiles:
             disp("reading %s ..." % infile)
             ext = infile[-4:].upper()
@@ -183,6 +210,9 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
         if pdr is not None:
             disp("writing %s ..." % pdr)
             _check(L.bsx_meth_write_pdr(h, pdr.encode(), pdr_min_reads, None))
+        if epi is not None:
+            disp("writing %s ..." % epi)
+            _check(L.bsx_meth_write_epi(h, epi.encode(), epi_min_reads, None))
         if wig is not None:
             disp("writing %s ..." % wig)
             _check(L.bsx_meth_write_wig(h, wig.encode(), wig_bin, min_depth))
@@ -208,6 +238,8 @@ def build_parser():
             o = super().parse_args(args, namespace)
             if o.pdr is None and o.pdr_only:
                 self.error("%s needs --pdr" % ", ".join(o.pdr_only))
+            if o.epi is None and o.epi_min_reads is not None:
+                self.error("--epi-min-reads needs --epi")
             return o
     class PdrOnly(argparse.Action):  # stores the value and remembers that the option was given
         def __call__(self, parser, namespace, values, option_string=None):
@@ -269,6 +301,10 @@ def build_parser():
                     help="CpG calls a read needs to count for --pdr (default 4)")
     ap.add_argument("--pdr-min-reads", dest="pdr_min_reads", action=PdrOnly, type=at_least(1, "the number of reads"), default=1, metavar="R",
                     help="such reads a position needs for a row of --pdr (default 1)")
+    ap.add_argument("--epi", dest="epi", default=None, metavar="FILE",
+                    help="write the epiallele table: reads per methylation pattern of every four neighbouring CpGs, with epipolymorphism and entropy (extension)")
+    ap.add_argument("--epi-min-reads", dest="epi_min_reads", type=at_least(1, "the number of reads"), default=None, metavar="R",
+                    help="reads a window needs for a row of --epi (default 1)")
     ap.add_argument("infiles", nargs="+", help="mapping files written by bsmap: *.sam / *.bam by their format, anything else as BSP")
     return ap
 
@@ -280,7 +316,8 @@ def main(argv=None):
                          rm_dup=o.rm_dup, trim_fillin=o.trim_fillin, combine_CpG=o.combine_CpG, min_depth=o.min_depth, device=o.device, quiet=o.quiet,
                          mbias=o.mbias, trim5=o.trim5, trim3=o.trim3, ct_snp=o.ct_snp, context=o.context, wig=o.wig, wig_bin=o.wig_bin,
                          regions=o.regions, region_out=o.region_out, nonconv_filter=o.nonconv_filter, read_stats=o.read_stats, pdr=o.pdr,
-                         pdr_min_cpg=o.pdr_min_cpg if o.pdr is not None else None, pdr_min_reads=o.pdr_min_reads if o.pdr is not None else None))
+                         pdr_min_cpg=o.pdr_min_cpg if o.pdr is not None else None, pdr_min_reads=o.pdr_min_reads if o.pdr is not None else None,
+                         epi=o.epi, epi_min_reads=o.epi_min_reads))
 
 
 if __name__ == "__main__":

@@ -468,6 +468,36 @@ int bsx_meth_pdr_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *reads, uint32
  * NULL.  BSX_ERR_STATE when PDR is off */
 int bsx_meth_write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows);
 
+/* Epiallele patterns per window of four neighbouring CpGs (an extension; the input of epipolymorphism, Landan et al. 2012, methylation entropy, Xie et al.
+ * 2011, and methclone-style comparisons).  Off by default; with it off bsx_meth_add launches what it launches without it.
+ *
+ * A reference CpG is a C followed by a G inside one sequence (a C at the end of one sequence and a G at the start of the next are none).  The CpGs of a
+ * sequence are numbered 0, 1, .. in position order (the ORDINAL) and identified by the position of their C on both strands.  The CpGs of a read are the
+ * reference CpGs whose call position (the C under a "+?" read, the G under a "-?" read) lies in the read's window; the read shows each of them as M (a CG call
+ * with the unconverted letter), U (a CG call with the converted letter) or X (anything else: another letter, N, a cycle masked by bsx_meth_set_cycle_trim).
+ * A WINDOW is four CpGs with consecutive ordinals o .. o+3 of one sequence.  A valid alignment that the non-conversion filter has not dropped adds one to
+ * cell[o][pattern] of every window whose four CpGs are all CpGs of the read and none of them X; bit j of `pattern` (j = 0: the leftmost CpG) is set when
+ * CpG o+j is M.  Both strands feed the same cells; mates are two reads.  min_depth, the context filter, the C/T-SNP mode and bsx_meth_combine_cpg do not
+ * touch the cells.  Device memory: sixteen uint32 per reference CpG, 4 bytes per CpG for its position and 4 bytes per 64 reference letters for the rank
+ * directory, built by kernels at the first add, report or bsx_meth_n_cpg that needs them.  bsx_meth_set_reference after that discards the index AND the
+ * cells: set the whole reference before the first add.  The reference must be shorter than 2^33 letters (BSX_ERR_LIMIT).
+ *
+ * On or off only before the first add, otherwise BSX_ERR_STATE.  Every call below gives BSX_ERR_STATE while it is off, and BSX_ERR_ARG for a null handle
+ * or a null out pointer before any device call. */
+int bsx_meth_set_epi(bsx_meth *m, int on);
+int bsx_meth_n_cpg(bsx_meth *m, uint32_t chr, uint64_t *n);   /* the number of reference CpGs of one sequence */
+/* Epiallele rows of one sequence in ordinal order: the windows whose sixteen cells sum to at least min_reads (min_reads >= 1, else BSX_ERR_ARG).  The row
+ * buffers are its own: the rows of the last bsx_meth_report_chr and bsx_meth_pdr_report_chr stay fetchable. */
+int bsx_meth_epi_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_reads, uint32_t *n_rows);
+/* the rows of the last epi_report_chr: pos0[n_rows][4] the 0-based positions of the four Cs, counts[n_rows][16] the cells by pattern */
+int bsx_meth_epi_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *counts);
+/* The epiallele rows of every sequence in sorted name order (the table's) as a tab-separated file.  Header: "chr pos1 pos2 pos3 pos4 reads meth mean epipoly
+ * entropy" and the sixteen patterns as four letters U / M in CpG order, UUUU MUUU UMUU MMUU .. MMMM (pattern 0 .. 15).  A row: the name, the four 1-based
+ * positions of the Cs, reads = the sum of the counts, meth = the methylated calls (sum of popcount(k) * n_k), mean = meth / (4 * reads) as "%.3f",
+ * epipolymorphism 1 - sum p_k^2 and entropy -1/4 sum p_k log2 p_k as "%.4f" with p_k = n_k / reads in double precision, then the sixteen counts.  A file
+ * without rows is the header alone.  Needs a handle that knows its names, else BSX_ERR_ARG; n_rows may be NULL. */
+int bsx_meth_write_epi(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,8 +7,10 @@ reference letter, reverse calls in the pile-up, the SNP tests in the report).  `
 `--repeat` times each, in the order given (the order of their launches in a kernel trace).  `--nonconv-filter N`, `--read-stats` and `--pdr` (with
 `--pdr-min-cpg K`) turn the per-read pass on (k_meth_reads ahead of the pile-up: DESIGN §3.10); the JSON line then carries the dropped reads, the histogram's
 totals and the PDR rows.  (The reads here keep 30 % of ALL their cytosines, whatever the context: nearly every read has three methylated non-CpG calls, so
-`--nonconv-filter 3` drops nearly all of them and the pile-up behind it has little left to do; a threshold such as 40 drops nearly none.)
-usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
+`--nonconv-filter 3` drops nearly all of them and the pile-up behind it has little left to do; a threshold such as 40 drops nearly none.)  `--epi` turns the
+epiallele tally on (k_meth_epi behind the per-read pass: DESIGN §3.11) and times the build of the CpG index (bsx_meth_n_cpg on the whole reference, ahead of
+the first add) and bsx_meth_epi_report_chr over all chromosomes; the JSON line then carries the CpGs and the epiallele rows.
+usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--epi] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--read-stats", dest="read_stats", action="store_true")
     ap.add_argument("--pdr", dest="pdr", action="store_true")
     ap.add_argument("--pdr-min-cpg", dest="pdr_min_cpg", type=int, default=4)
+    ap.add_argument("--epi", dest="epi", action="store_true")
     a = ap.parse_args()
     L = MR._bind()
     rng = np.random.default_rng(1)
@@ -52,6 +55,15 @@ def main():
         B._check(L.bsx_meth_set_reference(h, c, s.tobytes()))
         if c < 2:
             chunks.append(s)
+    extra = {}
+    if a.epi:  # after the reference is whole: the first call that needs the index builds it
+        B._check(L.bsx_meth_set_epi(h, 1))
+        t5, n_cpg = time.perf_counter(), 0
+        for c in range(len(lens)):
+            nc = C.c_uint64()
+            B._check(L.bsx_meth_n_cpg(h, c, C.byref(nc)))
+            n_cpg += nc.value
+        extra.update(cpg_index_build_s=round(time.perf_counter() - t5, 3), n_cpg=n_cpg)
     n, ln = a.aln, a.len
     # alignments on the first two chromosomes only need their letters on the host; positions are uniform there
     chr_ = rng.integers(0, 2, n).astype(np.uint32)
@@ -79,7 +91,6 @@ def main():
         B._check(L.bsx_meth_report_chr(h, c, 1, 1, C.byref(nr), C.byref(cv), C.byref(sd)))
         rows += nr.value; cov += cv.value
     dt_rep = time.perf_counter() - t1
-    extra = {}
     if a.nonconv_filter:
         nd = C.c_uint64()
         B._check(L.bsx_meth_nonconv_dropped(h, C.byref(nd)))
@@ -93,6 +104,13 @@ def main():
             B._check(L.bsx_meth_pdr_report_chr(h, c, 1, C.byref(nr)))
             pdr_rows += nr.value
         extra.update(pdr_min_cpg=a.pdr_min_cpg, pdr_rows=pdr_rows, pdr_report_s_all_chromosomes=round(time.perf_counter() - t4, 3))
+    if a.epi:
+        t6, epi_rows = time.perf_counter(), 0
+        for c in range(len(lens)):
+            nr = C.c_uint32()
+            B._check(L.bsx_meth_epi_report_chr(h, c, 1, C.byref(nr)))
+            epi_rows += nr.value
+        extra.update(epi_rows=epi_rows, epi_report_s_all_chromosomes=round(time.perf_counter() - t6, 3))
     for width in [int(x) for x in a.wig_bin.split(",") if x]:
         out = np.zeros((int(lens.max()) // width + 1, 5), np.uint64)
         nb, took = C.c_uint64(), []
