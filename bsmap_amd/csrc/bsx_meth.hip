@@ -10,12 +10,17 @@
 //   k_meth_cpg     fold the G of every CG into its C
 //   k_meth_reads   per-read call counts ahead of the pile-up: non-conversion filter, read histogram, PDR cells; off by default
 //   k_meth_epi     per read, the methylation pattern of every four neighbouring CpGs it covers, tallied per window (epialleles); off by default;
-//                  k_cpg_count / k_cpg_emit build the CpG index it needs, k_epi_count / k_epi_emit list its rows
+//                  k_cpg_count / k_cpg_emit build the CpG index it needs
 // With the C/T-SNP mode on (bsx_meth_set_ct_snp, an extension: -i of later BSMAP releases) the same pile-up pass also counts, per reference position, what the reads
 // of the OTHER reference strand show there (G over an intact C, A over a C->T SNP), and the row selection and the table use those two counters.
-//   k_meth_count / k_meth_emit   ordered compaction of the positions the table will list
 //   k_meth_bins / k_meth_regions   pooled sums per fixed bin (wiggle track, -w / -b) and per interval (BED, --regions) under the table's row rule
-// The host side (bsmap_amd/methratio.py) parses the option surface, the FASTA and the BSP / SAM lines, and prints the
+// The reports that list rows in order share one ordered compaction, compact_count / compact_emit, over a rule struct (what a row is, what it stores):
+//   k_meth_count / k_meth_emit (TableRule: the positions the table lists), k_pdr_count / k_pdr_emit (PdrRule), k_epi_count / k_epi_emit (EpiRule)
+// and one host path, meth_compact (count, scan, size, emit).  A new per-position or per-window report is a rule struct and two wrappers.
+// One place per idea elsewhere too: meth_forward_call (what a forward call is), meth_chr_of / meth_is_cpg (which chromosome, which CpG), meth_covered (the row
+// rule), meth_site (a site's five values); on the host DevBuf (device memory that owns itself), OutFile, guarded (no exception across the C ABI), format_rows,
+// sorted_chromosomes, and the row formatters of bsx_meth_text.h and bsx_meth_epi.h.
+// The host side (bsmap_amd/methratio.py) parses the option surface; the library reads the FASTA and the BSP / SAM / BAM files (bsx_meth_parse.h) and prints the
 // table with the reference's arithmetic.  All counters are integers: results are exact.
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -43,11 +48,44 @@
 #include "bsx_internal.h"
 #include "bsx_meth_epi.h"
 #include "bsx_meth_parse.h"
+#include "bsx_meth_text.h"
 #include "bsx_meth_tiles.h"
 
 namespace {
 
 typedef unsigned long long u64;
+
+// Device memory that owns itself: freed when it goes out of scope or with the handle it is a member of (bsx_meth_destroy makes the handle's device current
+// first).  A failed allocation leaves it empty and returns HIP's error, for HIP_TRY or a message of the caller's own.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;  // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // at least `bytes` of it; a buffer that is large enough stays (with its contents), a smaller one is replaced (without them)
+    hipError_t reserve(size_t bytes)
+    {
+        if (p && bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipMalloc((void **)&p, bytes ? bytes : 1);
+        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e; }
+        cap = bytes;
+        return hipSuccess;
+    }
+    // `bytes` of zeroes, ready when it returns; on `stream`, so that it does not wait for the null stream
+    hipError_t zeroed(size_t bytes, hipStream_t stream)
+    {
+        hipError_t e = reserve(bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(p, 0, bytes, stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e != hipSuccess) release();
+        return e;
+    }
+};
 
 struct MethDev {
     const uint8_t *ref;      // all chromosomes, upper-case letters, concatenated
@@ -153,7 +191,7 @@ __device__ __forceinline__ bool meth_window(const MethDev &M, const AlnBatch &B,
 
 // Context class of the cytosine at global letter g of the chromosome [c0, c1): 0 CG, 1 CHG, 2 CHH, 3 "CN".  '+' strands look at the next two letters; '-'
 // strands (the call is a G) at the previous two, with C in the role of G.  A neighbour outside the chromosome counts as no letter: the concatenated text
-// goes on with the next chromosome there (the trap of k_meth_cpg), so both indices are tested against [c0, c1) before they are read.
+// goes on with the next chromosome there (the trap of meth_is_cpg), so both indices are tested against [c0, c1) before they are read.
 __device__ __forceinline__ uint32_t meth_context(const uint8_t *ref, u64 g, u64 c0, u64 c1, bool plus)
 {
     uint8_t n1 = 0, n2 = 0;
@@ -164,6 +202,22 @@ __device__ __forceinline__ uint32_t meth_context(const uint8_t *ref, u64 g, u64 
     if (n1 != 'A' && n1 != 'T' && n1 != other) return 3;
     if (n2 == gl) return 1;
     return (n2 == 'A' || n2 == 'T' || n2 == other) ? 2 : 3;
+}
+
+// Whether letter k of the window, over the reference letter rl, is a forward call: the one place that holds its three tests, in this order: own cytosine
+// (C under a '+' read, G under a '-' read), one of the two letters, cycle mask.  Returns the call's cycle and in `m` whether it shows the unconverted
+// letter, or -1 where there is no forward call.
+__device__ __forceinline__ int64_t meth_forward_call(const AlnBatch &B, const MethWindow &W, const uint8_t *s, uint8_t rl, int64_t k, bool &m)
+{
+    const bool plus = !(W.st & 1), backward = W.st == 1 || W.st == 2;
+    const uint8_t match = plus ? 'C' : 'G', convert = plus ? 'T' : 'A';  // strand[0]: '+' -> C/T, '-' -> G/A
+    if (rl != match) return -1;
+    const uint8_t ch = s[k];
+    if (ch != convert && ch != match) return -1;
+    const int64_t j = W.lo + k, cyc = backward ? W.n0 - 1 - j : j;  // 0 <= cyc < n0
+    if (cyc < (int64_t)B.trim5 || cyc >= W.n0 - (int64_t)B.trim3) return -1;
+    m = ch == match;
+    return cyc;
 }
 
 // The calls of one valid alignment, a lane per letter: depth / methylated counters, and with MBIAS the tally cell of every call.
@@ -179,14 +233,15 @@ __device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, 
     if (W.pos < 0) return;         // (a negative position would make the reference slice from the chromosome's end: never produced by bsmap)
     const uint32_t st = W.st;
     const bool plus = !(st & 1), backward = st == 1 || st == 2;
-    const uint8_t match = plus ? 'C' : 'G', convert = plus ? 'T' : 'A';  // strand[0]: '+' -> C/T, '-' -> G/A
     const uint8_t *s = B.seq + B.seq_off[i] + W.lo;
     const u64 c0 = M.chr_off[W.c], c1 = M.chr_off[W.c + 1], g0 = c0 + (u64)W.pos;
     const int64_t len = W.hi - W.lo, cyc_lo = (int64_t)B.trim5, cyc_hi = W.n0 - (int64_t)B.trim3;
     for (int64_t k = lane; k < len; k += 64) {
         const uint8_t rl = M.ref[g0 + k];
-        if (rl != match) {
-            if (SNP) {
+        bool mb = false;
+        const int64_t cyc = meth_forward_call(B, W, s, rl, k, mb);
+        if (cyc < 0) {
+            if (SNP) {  // (the other strand's letter is not the read strand's own: a letter that failed a later forward test ends at the first test here)
                 const uint8_t rc_match = plus ? 'G' : 'C', rc_convert = plus ? 'A' : 'T';
                 if (rl != rc_match) continue;
                 const uint8_t rch = s[k];
@@ -197,11 +252,7 @@ __device__ __forceinline__ void meth_calls(const MethDev &M, const AlnBatch &B, 
             }
             continue;
         }
-        const uint8_t ch = s[k];
-        if (ch != convert && ch != match) continue;
-        const int64_t j = W.lo + k, cyc = backward ? W.n0 - 1 - j : j;  // 0 <= cyc < n0
-        if (cyc < cyc_lo || cyc >= cyc_hi) continue;
-        const uint32_t m = ch == match;
+        const uint32_t m = mb;
         if (m) atomicAdd(&M.meth[g0 + k], 1u);
         atomicAdd(&M.depth[g0 + k], 1u);
         if (MBIAS) {
@@ -280,18 +331,10 @@ constexpr size_t RS_CELLS = (size_t)RS_LDS_CELLS + 4;
 constexpr int RS_BLOCK = 512, RS_BLOCKS_PER_CU = 3;  // 78 VGPRs: 6 waves per SIMD, 24 per CU
 
 // Letter k of the window as a call: its context class 0..3 and in `m` whether it shows the unconverted letter; -1 where meth_calls makes no forward call
-// (the same tests in the same order: own cytosine, one of the two letters, cycle mask).
 __device__ __forceinline__ int meth_call_class(const MethDev &M, const AlnBatch &B, const MethWindow &W, const uint8_t *s, u64 c0, u64 c1, u64 g0, int64_t k, bool &m)
 {
-    const bool plus = !(W.st & 1), backward = W.st == 1 || W.st == 2;
-    const uint8_t match = plus ? 'C' : 'G', convert = plus ? 'T' : 'A';
-    if (M.ref[g0 + k] != match) return -1;
-    const uint8_t ch = s[k];
-    if (ch != convert && ch != match) return -1;
-    const int64_t j = W.lo + k, cyc = backward ? W.n0 - 1 - j : j;
-    if (cyc < (int64_t)B.trim5 || cyc >= W.n0 - (int64_t)B.trim3) return -1;
-    m = ch == match;
-    return (int)meth_context(M.ref, g0 + k, c0, c1, plus);
+    if (meth_forward_call(B, W, s, M.ref[g0 + k], k, m) < 0) return -1;
+    return (int)meth_context(M.ref, g0 + k, c0, c1, !(W.st & 1));
 }
 
 // One wave per alignment in a persistent grid (the shape of k_meth_pile_mbias), ahead of the pile-up.  The wave walks the window 64 letters at a time; a lane
@@ -353,47 +396,6 @@ __global__ __launch_bounds__(RS_BLOCK) void k_meth_reads(MethDev M, AlnBatch B, 
     if (threadIdx.x == 0 && s_tot[4]) atomicAdd(R.dropped, s_tot[4]);
 }
 
-// PDR rows of one chromosome in position order (bsx_meth_pdr_report_chr): the count / scan / emit scheme of k_meth_count / k_meth_emit below with the rule
-// reads >= min_reads (min_reads >= 1) on the cell's low word
-__global__ __launch_bounds__(256) void k_pdr_count(const u64 *pdr, u64 g0, u64 n, uint32_t min_reads, uint32_t *blk_rows)
-{
-    __shared__ uint32_t s_rows;
-    if (threadIdx.x == 0) s_rows = 0;
-    __syncthreads();
-    uint32_t rows = 0;
-    for (int r = 0; r < 4; r++) {
-        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        if (k < n) rows += (uint32_t)pdr[g0 + k] >= min_reads;
-    }
-    if (rows) atomicAdd(&s_rows, rows);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_rows[blockIdx.x] = s_rows;
-}
-
-__global__ __launch_bounds__(256) void k_pdr_emit(const uint8_t *ref, const u64 *pdr, u64 g0, u64 n, uint32_t min_reads, const uint32_t *blk_start, uint32_t *out_pos,
-                                                  uint32_t *out_reads, uint32_t *out_disc, uint8_t *out_letter)
-{
-    __shared__ uint32_t s_wave[4];
-    uint32_t base = blk_start[blockIdx.x];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int r = 0; r < 4; r++) {  // positions blockIdx*1024 + r*256 + thread: ascending with (r, thread)
-        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        const u64 cell = k < n ? pdr[g0 + k] : 0ull;
-        const bool row = k < n && (uint32_t)cell >= min_reads;
-        const u64 bal = __ballot(row);
-        if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (int w = 0; w < wv; w++) off += s_wave[w];
-        if (row) {
-            const uint32_t o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
-            out_pos[o] = (uint32_t)k; out_reads[o] = (uint32_t)cell; out_disc[o] = (uint32_t)(cell >> 32); out_letter[o] = ref[g0 + k];
-        }
-        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-    }
-}
-
 // ---- epiallele patterns per window of four CpGs ----
 // The CpG index of the handle (meth_epi_index): the chromosome-relative positions of the C of every reference CpG, all chromosomes in order (a CpG's index in
 // that list is its GLOBAL ordinal; the host keeps the ordinal of every chromosome's first CpG), and the rank directory `dir`: the number of CpGs ahead of
@@ -405,14 +407,21 @@ struct EpiDev {
     u64 n_cpg;
 };
 
+// the chromosome that holds letter x < M.total of the concatenated text
+__device__ __forceinline__ uint32_t meth_chr_of(const MethDev &M, u64 x)
+{
+    uint32_t lo = 0, hi = M.n_chr;
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (M.chr_off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+
 // Whether letter x of the concatenated text is the C of a reference CpG.  The G must lie in x's own chromosome: a C at the end of one sequence and a G at
-// the start of the next are no CpG (the trap of k_meth_cpg; the search runs only behind a "CG").  The text is zero-padded behind M.total.
+// the start of the next are no CpG (the search runs only behind a "CG").  The text is zero-padded behind M.total.  The one place that knows this trap: the
+// CpG index and the fold of k_meth_cpg both ask here.
 __device__ __forceinline__ bool meth_is_cpg(const MethDev &M, u64 x)
 {
     if (x + 1 >= M.total || M.ref[x] != 'C' || M.ref[x + 1] != 'G') return false;
-    uint32_t lo = 0, hi = M.n_chr;
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (M.chr_off[mid] <= x) lo = mid; else hi = mid; }
-    return x + 1 < M.chr_off[lo + 1];
+    return x + 1 < M.chr_off[meth_chr_of(M, x) + 1];
 }
 
 // The number of reference CpGs whose C lies ahead of letter g (g <= M.total): the directory's count for g's block, and for the rest of the way one 64-letter
@@ -443,9 +452,7 @@ __global__ __launch_bounds__(256) void k_cpg_emit(MethDev M, u64 n_blocks, const
     const bool cpg = meth_is_cpg(M, x);
     const u64 bal = __ballot(cpg);
     if (!cpg) return;
-    uint32_t lo = 0, hi = M.n_chr;
-    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (M.chr_off[mid] <= x) lo = mid; else hi = mid; }
-    pos[dir[b] + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))] = (uint32_t)(x - M.chr_off[lo]);
+    pos[dir[b] + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))] = (uint32_t)(x - M.chr_off[meth_chr_of(M, x)]);
 }
 
 // one wave per chromosome border: the global ordinal of the first CpG at or behind it
@@ -522,67 +529,11 @@ __global__ __launch_bounds__(256) void k_meth_epi(MethDev M, AlnBatch B, EpiDev 
     }
 }
 
-// Epiallele rows of one chromosome in ordinal order (bsx_meth_epi_report_chr): the count / scan / emit scheme of k_pdr_count / k_pdr_emit over the chromosome's
-// n windows, the first of them at the global ordinal o0, with the rule reads >= min_reads (min_reads >= 1) on the sum of a window's sixteen cells
-__device__ __forceinline__ uint32_t epi_reads(const uint32_t *cells, u64 o, uint4 v[4])
-{
-    const uint4 *c = (const uint4 *)(cells + o * 16);
-    uint32_t sum = 0;
-    for (int q = 0; q < 4; q++) { v[q] = c[q]; sum += v[q].x + v[q].y + v[q].z + v[q].w; }  // (< 2^32 alignments per handle: no carry)
-    return sum;
-}
-
-__global__ __launch_bounds__(256) void k_epi_count(const uint32_t *cells, u64 o0, u64 n, uint32_t min_reads, uint32_t *blk_rows)
-{
-    __shared__ uint32_t s_rows;
-    if (threadIdx.x == 0) s_rows = 0;
-    __syncthreads();
-    uint32_t rows = 0;
-    for (int r = 0; r < 4; r++) {
-        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        uint4 v[4];
-        if (k < n) rows += epi_reads(cells, o0 + k, v) >= min_reads;
-    }
-    if (rows) atomicAdd(&s_rows, rows);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_rows[blockIdx.x] = s_rows;
-}
-
-__global__ __launch_bounds__(256) void k_epi_emit(const uint32_t *cells, const uint32_t *cpg_pos, u64 o0, u64 n, uint32_t min_reads, const uint32_t *blk_start,
-                                                  uint32_t *out_pos, uint32_t *out_counts)
-{
-    __shared__ uint32_t s_wave[4];
-    uint32_t base = blk_start[blockIdx.x];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int r = 0; r < 4; r++) {  // windows blockIdx*1024 + r*256 + thread: ascending with (r, thread)
-        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        uint4 v[4] = {};
-        const bool row = k < n && epi_reads(cells, o0 + k, v) >= min_reads;
-        const u64 bal = __ballot(row);
-        if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (int w = 0; w < wv; w++) off += s_wave[w];
-        if (row) {
-            const u64 o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
-            for (int j = 0; j < 4; j++) out_pos[o * 4 + j] = cpg_pos[o0 + k + j];  // a window has its four CpGs in one chromosome
-            uint4 *oc = (uint4 *)(out_counts + o * 16);
-            for (int q = 0; q < 4; q++) oc[q] = v[q];
-        }
-        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
-    }
-}
-
 __global__ void k_meth_cpg(MethDev M, u64 *rev, u64 *pdr)
 {
     // every "CG" of every chromosome (occurrences cannot overlap): the G's counters move onto the C  (methratio.py:118-128)
     for (u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x; g + 1 < M.total; g += (u64)gridDim.x * blockDim.x) {
-        if (M.ref[g] != 'C' || M.ref[g + 1] != 'G') continue;
-        // (a C that is the last letter of a chromosome must not pair with the first letter of the next one)
-        uint32_t lo = 0, hi = M.n_chr;
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (M.chr_off[mid] <= g) lo = mid; else hi = mid; }
-        if (g + 1 >= M.chr_off[lo + 1]) continue;
+        if (!meth_is_cpg(M, g)) continue;  // (a C that is the last letter of a chromosome does not pair with the first letter of the next one)
         M.depth[g] += M.depth[g + 1]; M.meth[g] += M.meth[g + 1];
         M.depth[g + 1] = 0; M.meth[g + 1] = 0;
         if (rev) { rev[g] += rev[g + 1]; rev[g + 1] = 0; }  // both halves at once: each sum stays below 2^32
@@ -617,60 +568,171 @@ __device__ __forceinline__ bool meth_covered(const MethDev &M, const u64 *rev, u
     return ok;
 }
 
-// table rows of one chromosome, in position order: blocks of 1024 positions are counted, scanned, and emitted
-__global__ __launch_bounds__(256) void k_meth_count(MethDev M, u64 g0, u64 n, RowRule R, uint32_t *blk_rows, u64 *nc_nd, const u64 *rev)
+// ---- ordered compaction: the rows of a report in ascending item order ----
+// Every per-position or per-window report is the same two passes over the items [0, n) of one chromosome, in blocks of 1 024 items taken in 4 rounds of
+// 256 (item = block * 1024 + round * 256 + thread: ascending with (round, thread)): compact_count leaves the number of rows of every block, the host scans
+// them (meth_compact), and compact_emit gives every row its place: the block's start, the rows of the rounds and waves before (one ballot per wave, a
+// prefix over s_wave[4]), the rows of the lower lanes.  What a row is and what it stores comes from a rule struct:
+//   Row                          the payload row() reads and store() writes
+//   bool row(k, Row &)           whether item k < n is a row; the same answer in both passes
+//   void store(o, k, const Row &)   row number o of the chromosome (64 bits: a rule may scale it) is item k
+// A new report is a rule struct and two one-line kernels.
+template <class Rule>
+__device__ __forceinline__ void compact_count(Rule &rule, u64 n, uint32_t *blk_rows)
 {
     __shared__ uint32_t s_rows;
-    __shared__ u64 s_nc, s_nd;
-    if (threadIdx.x == 0) { s_rows = 0; s_nc = 0; s_nd = 0; }
+    if (threadIdx.x == 0) s_rows = 0;
     __syncthreads();
-    uint32_t rows = 0; u64 nc = 0, nd = 0;
+    uint32_t rows = 0;
     for (int r = 0; r < 4; r++) {
         const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        if (k >= n) continue;
-        uint32_t d, m, g, ga;
-        const bool ok = meth_covered(M, rev, g0, n, k, R, d, m, g, ga);
-        nc += ok; nd += ok ? d : 0u;  // the raw depth in every mode
-        rows += ok && (m != 0 || R.meth0);
+        typename Rule::Row w;
+        if (k < n) rows += rule.row(k, w);
     }
-    atomicAdd(&s_rows, rows); atomicAdd(&s_nc, nc); atomicAdd(&s_nd, nd);
+    if (rows) atomicAdd(&s_rows, rows);
     __syncthreads();
-    if (threadIdx.x == 0) { blk_rows[blockIdx.x] = s_rows; if (s_nc) { atomicAdd(&nc_nd[0], s_nc); atomicAdd(&nc_nd[1], s_nd); } }
+    if (threadIdx.x == 0) blk_rows[blockIdx.x] = s_rows;
+}
+
+template <class Rule>
+__device__ __forceinline__ void compact_emit(Rule &rule, u64 n, const uint32_t *blk_start)
+{
+    __shared__ uint32_t s_wave[4];
+    uint32_t base = blk_start[blockIdx.x];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int r = 0; r < 4; r++) {
+        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
+        typename Rule::Row w{};
+        bool row = false;
+        if (k < n) row = rule.row(k, w);
+        const u64 bal = __ballot(row);
+        if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int q = 0; q < wv; q++) off += s_wave[q];
+        if (row) rule.store((u64)(off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1))), k, w);
+        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+}
+
+// The table (bsx_meth_report_chr): the covered positions of the chromosome [g0, g0 + n) that are methylated or listed under -z.  nc, nd: the covered
+// positions this thread has seen and their raw depth (in every mode), kept with SUMS for k_meth_count to flush (without it they stay 0: k_meth_emit has no
+// use for them and is a tenth slower when it keeps them)
+template <bool SUMS>
+struct TableRule {
+    struct Row { uint32_t d, m, g, ga; };
+    MethDev M;
+    u64 g0, n;
+    RowRule R;
+    const u64 *rev;
+    uint32_t *out_pos, *out_depth, *out_meth;
+    u64 *out_ctx;
+    uint32_t *out_rev_g, *out_rev_ga;
+    u64 nc, nd;
+    __device__ __forceinline__ bool row(u64 k, Row &w)
+    {
+        const bool ok = meth_covered(M, rev, g0, n, k, R, w.d, w.m, w.g, w.ga);
+        if (SUMS) { nc += ok; nd += ok ? w.d : 0u; }
+        return ok && (w.m != 0 || R.meth0);
+    }
+    __device__ __forceinline__ void store(u64 o, u64 k, const Row &w) const
+    {
+        out_pos[o] = (uint32_t)k; out_depth[o] = w.d; out_meth[o] = w.m;
+        if (R.snp) { out_rev_g[o] = w.g; out_rev_ga[o] = w.ga; }
+        if (out_ctx) {  // refcr[i-2:i+3] with Python's slice rules, byte 7 = the letter at i.  For i < 2 the start i-2 is negative and counts from the
+                        // chromosome's end: empty on a chromosome of at least five letters, but not below that ("CCGG": position 1 -> "G", "C": -> "C")
+            u64 ctx = 0;
+            int nb = 0;
+            int64_t lo, hi;
+            py_slice((int64_t)n, true, (int64_t)k - 2, true, (int64_t)k + 3, lo, hi);
+            for (int64_t q = lo; q < hi; q++) ctx |= (u64)M.ref[g0 + (u64)q] << (8 * nb++);
+            out_ctx[o] = ctx | ((u64)M.ref[g0 + k] << 56);
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void k_meth_count(MethDev M, u64 g0, u64 n, RowRule R, uint32_t *blk_rows, u64 *nc_nd, const u64 *rev)
+{
+    __shared__ u64 s_nc, s_nd;
+    if (threadIdx.x == 0) { s_nc = 0; s_nd = 0; }  // (compact_count's first barrier stands between this and the adds)
+    TableRule<true> rule{M, g0, n, R, rev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    compact_count(rule, n, blk_rows);
+    atomicAdd(&s_nc, rule.nc); atomicAdd(&s_nd, rule.nd);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_nc) { atomicAdd(&nc_nd[0], s_nc); atomicAdd(&nc_nd[1], s_nd); }
 }
 
 __global__ __launch_bounds__(256) void k_meth_emit(MethDev M, u64 g0, u64 n, RowRule R, const uint32_t *blk_start, uint32_t *out_pos, uint32_t *out_depth,
                                                    uint32_t *out_meth, u64 *out_ctx, uint32_t *out_rev_g, uint32_t *out_rev_ga, const u64 *rev)
 {
-    __shared__ uint32_t s_wave[4];
-    uint32_t base = blk_start[blockIdx.x];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int r = 0; r < 4; r++) {  // positions blockIdx*1024 + r*256 + thread: ascending with (r, thread)
-        const u64 k = (u64)blockIdx.x * 1024 + (u64)r * 256 + threadIdx.x;
-        uint32_t d = 0, m = 0, g = 0, ga = 0;
-        bool row = false;
-        if (k < n) row = meth_covered(M, rev, g0, n, k, R, d, m, g, ga) && (m != 0 || R.meth0);
-        const u64 bal = __ballot(row);
-        if (lane == 0) s_wave[wv] = (uint32_t)__builtin_popcountll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (int w = 0; w < wv; w++) off += s_wave[w];
-        if (row) {
-            const uint32_t o = off + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1));
-            out_pos[o] = (uint32_t)k; out_depth[o] = d; out_meth[o] = m;
-            if (R.snp) { out_rev_g[o] = g; out_rev_ga[o] = ga; }
-            if (out_ctx) {  // refcr[i-2:i+3] with Python's slice rules, byte 7 = the letter at i.  For i < 2 the start i-2 is negative and counts from the
-                            // chromosome's end: empty on a chromosome of at least five letters, but not below that ("CCGG": position 1 -> "G", "C": -> "C")
-                u64 ctx = 0;
-                int nb = 0;
-                int64_t lo, hi;
-                py_slice((int64_t)n, true, (int64_t)k - 2, true, (int64_t)k + 3, lo, hi);
-                for (int64_t q = lo; q < hi; q++) ctx |= (u64)M.ref[g0 + (u64)q] << (8 * nb++);
-                out_ctx[o] = ctx | ((u64)M.ref[g0 + k] << 56);
-            }
-        }
-        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        __syncthreads();
+    TableRule<false> rule{M, g0, n, R, rev, out_pos, out_depth, out_meth, out_ctx, out_rev_g, out_rev_ga, 0, 0};
+    compact_emit(rule, n, blk_start);
+}
+
+// PDR (bsx_meth_pdr_report_chr): the positions of the chromosome at g0 with reads >= min_reads (min_reads >= 1) on the cell's low word
+struct PdrRule {
+    struct Row { u64 cell; };
+    const uint8_t *ref;
+    const u64 *pdr;
+    u64 g0;
+    uint32_t min_reads;
+    uint32_t *out_pos, *out_reads, *out_disc;
+    uint8_t *out_letter;
+    __device__ __forceinline__ bool row(u64 k, Row &w) const { w.cell = pdr[g0 + k]; return (uint32_t)w.cell >= min_reads; }
+    __device__ __forceinline__ void store(u64 o, u64 k, const Row &w) const
+    {
+        out_pos[o] = (uint32_t)k; out_reads[o] = (uint32_t)w.cell; out_disc[o] = (uint32_t)(w.cell >> 32); out_letter[o] = ref[g0 + k];
     }
+};
+
+__global__ __launch_bounds__(256) void k_pdr_count(const u64 *pdr, u64 g0, u64 n, uint32_t min_reads, uint32_t *blk_rows)
+{
+    PdrRule rule{nullptr, pdr, g0, min_reads, nullptr, nullptr, nullptr, nullptr};
+    compact_count(rule, n, blk_rows);
+}
+
+__global__ __launch_bounds__(256) void k_pdr_emit(const uint8_t *ref, const u64 *pdr, u64 g0, u64 n, uint32_t min_reads, const uint32_t *blk_start, uint32_t *out_pos,
+                                                  uint32_t *out_reads, uint32_t *out_disc, uint8_t *out_letter)
+{
+    PdrRule rule{ref, pdr, g0, min_reads, out_pos, out_reads, out_disc, out_letter};
+    compact_emit(rule, n, blk_start);
+}
+
+// Epialleles (bsx_meth_epi_report_chr): the chromosome's n windows in ordinal order, the first of them at the global ordinal o0, with reads >= min_reads
+// (min_reads >= 1) on the sum of a window's sixteen cells.  A row is four positions and sixteen counts: the row number times 4 and times 16, in 64 bits
+struct EpiRule {
+    struct Row { uint4 v[4]; };
+    const uint32_t *cells, *cpg_pos;
+    u64 o0;
+    uint32_t min_reads;
+    uint32_t *out_pos, *out_counts;
+    __device__ __forceinline__ bool row(u64 k, Row &w) const
+    {
+        const uint4 *c = (const uint4 *)(cells + (o0 + k) * 16);
+        uint32_t sum = 0;
+        for (int q = 0; q < 4; q++) { w.v[q] = c[q]; sum += w.v[q].x + w.v[q].y + w.v[q].z + w.v[q].w; }  // (< 2^32 alignments per handle: no carry)
+        return sum >= min_reads;
+    }
+    __device__ __forceinline__ void store(u64 o, u64 k, const Row &w) const
+    {
+        for (int j = 0; j < 4; j++) out_pos[o * 4 + j] = cpg_pos[o0 + k + j];  // a window has its four CpGs in one chromosome
+        uint4 *oc = (uint4 *)(out_counts + o * 16);
+        for (int q = 0; q < 4; q++) oc[q] = w.v[q];
+    }
+};
+
+__global__ __launch_bounds__(256) void k_epi_count(const uint32_t *cells, u64 o0, u64 n, uint32_t min_reads, uint32_t *blk_rows)
+{
+    EpiRule rule{cells, nullptr, o0, min_reads, nullptr, nullptr};
+    compact_count(rule, n, blk_rows);
+}
+
+__global__ __launch_bounds__(256) void k_epi_emit(const uint32_t *cells, const uint32_t *cpg_pos, u64 o0, u64 n, uint32_t min_reads, const uint32_t *blk_start,
+                                                  uint32_t *out_pos, uint32_t *out_counts)
+{
+    EpiRule rule{cells, cpg_pos, o0, min_reads, out_pos, out_counts};
+    compact_emit(rule, n, blk_start);
 }
 
 // ---- pooled methylation per bin and per interval (bsx_meth_bins, bsx_meth_regions) ----
@@ -810,52 +872,62 @@ __global__ __launch_bounds__(REGION_WAVES * 64) void k_meth_regions(MethDev M, R
 
 }  // namespace
 
+enum Count { CNT_VALID, CNT_NC, CNT_ND, CNT_DROPPED, CNT_CELLS = 8 };  // d_counts: valid alignments, the nc and nd of the last table report, alignments the non-conversion filter dropped
+
 struct bsx_meth {
     int device = 0;
     uint32_t n_chr = 0;
     std::vector<u64> chr_off;
-    uint8_t *d_ref = nullptr;
-    u64 *d_chr_off = nullptr, *d_counts = nullptr;  // d_counts: [0] valid alignments, [1] nc, [2] nd, [3] dropped by the non-conversion filter
-    uint32_t *d_depth = nullptr, *d_meth = nullptr, *d_first = nullptr;
+    DevBuf<uint8_t> d_ref;
+    DevBuf<u64> d_chr_off, d_counts;
+    DevBuf<uint32_t> d_depth, d_meth, d_first;  // d_first: empty without the duplicate filter
     uint32_t index_base = 0;
     uint32_t trim5 = 0, trim3 = 0;  // bsx_meth_set_cycle_trim
     int snp = 0;                    // bsx_meth_set_ct_snp: 0 off, 1 correct, 2 skip
     uint32_t ctx_mask = 0;          // bsx_meth_set_contexts
-    u64 *d_rev = nullptr;           // the packed opposite-strand counters, (total + 16) cells, or null when snp == 0
-    uint32_t *d_out_rev[2] = {nullptr, nullptr};  // rev_G / rev_GA of the rows of the last report, allocated with d_out when snp != 0
-    u64 *d_mbias = nullptr;         // bsx_meth_set_mbias: MB_CELLS cells and the overflow counter, or null
+    DevBuf<u64> d_rev;              // the packed opposite-strand counters, (total + 16) cells, or empty when snp == 0
+    DevBuf<u64> d_mbias;            // bsx_meth_set_mbias: MB_CELLS cells and the overflow counter, or empty
     uint32_t nonconv = 0, min_cpg = 0;  // bsx_meth_set_nonconv, bsx_meth_set_pdr
-    u64 *d_hist = nullptr;          // bsx_meth_set_read_stats: RS_CELLS cells, or null
-    u64 *d_pdr = nullptr;           // the packed PDR cells, (total + 16) of them, or null when min_cpg == 0
-    uint32_t *d_pdr_out[3] = {nullptr, nullptr, nullptr};  // pos, reads, discordant of the rows of the last bsx_meth_pdr_report_chr
-    uint8_t *d_pdr_letter = nullptr;                       // and their reference letters
-    size_t pdr_out_cap = 0;
-    uint32_t pdr_last_rows = 0;
+    DevBuf<u64> d_hist;             // bsx_meth_set_read_stats: RS_CELLS cells, or empty
+    DevBuf<u64> d_pdr;              // the packed PDR cells, (total + 16) of them, or empty when min_cpg == 0
     int epi = 0;                    // bsx_meth_set_epi
     bool cpg_built = false;         // the CpG index and the cells below exist (meth_epi_index builds them at the first add or report that needs them)
-    uint32_t *d_cpg_dir = nullptr, *d_cpg_pos = nullptr, *d_epi = nullptr;  // rank directory, positions by ordinal, 16 cells per CpG (EpiDev)
+    DevBuf<uint32_t> d_cpg_dir, d_cpg_pos, d_epi;  // rank directory, positions by ordinal, 16 cells per CpG (EpiDev)
     std::vector<uint32_t> cpg_first;  // [n_chr + 1] the global ordinal of every chromosome's first CpG, then the number of CpGs
-    uint32_t *d_epi_out[2] = {nullptr, nullptr};  // pos[rows][4], counts[rows][16] of the last bsx_meth_epi_report_chr
-    size_t epi_out_cap = 0;
-    uint32_t epi_last_rows = 0;
     int n_cu = 0;
     hipStream_t stream = nullptr;
-    // report buffers of the last bsx_meth_report_chr
-    uint32_t *d_blk = nullptr, *d_blk_start = nullptr, *d_out[3] = {nullptr, nullptr, nullptr};
-    u64 *d_ctx = nullptr;
-    size_t blk_cap = 0, out_cap = 0;
-    void *d_temp = nullptr; size_t temp_cap = 0;
+    // what the reports share (meth_compact): per-block row counts, their scan, the scan's scratch
+    DevBuf<uint32_t> d_blk, d_blk_start;
+    DevBuf<char> d_temp;
+    // the rows of the last bsx_meth_report_chr: pos, depth, meth, packed context, and with snp != 0 rev_G / rev_GA
+    DevBuf<uint32_t> d_out[3], d_out_rev[2];
+    DevBuf<u64> d_ctx;
     uint32_t last_rows = 0;
+    // of the last bsx_meth_pdr_report_chr: pos, reads, discordant, reference letter
+    DevBuf<uint32_t> d_pdr_out[3];
+    DevBuf<uint8_t> d_pdr_letter;
+    uint32_t pdr_last_rows = 0;
+    // of the last bsx_meth_epi_report_chr: pos[rows][4], counts[rows][16]
+    DevBuf<uint32_t> d_epi_out[2];
+    uint32_t epi_last_rows = 0;
     std::vector<std::string> names;  // filled by bsx_meth_create_from_fasta
-    MethDev dev() const { MethDev M; M.ref = d_ref; M.chr_off = d_chr_off; M.depth = d_depth; M.meth = d_meth; M.first = d_first; M.total = chr_off.back(); M.n_chr = n_chr; return M; }
+    MethDev dev() const { MethDev M; M.ref = d_ref.p; M.chr_off = d_chr_off.p; M.depth = d_depth.p; M.meth = d_meth.p; M.first = d_first.p; M.total = chr_off.back(); M.n_chr = n_chr; return M; }
 };
 
-// ---- the CpG index of the epiallele tally (DESIGN §3.11) ----
-static int meth_scan_u32(bsx_meth *m, uint32_t *in, uint32_t *out, size_t n);
+// out[k] = in[0] + .. + in[k - 1] for k < n, on the handle's stream and with its scratch buffer
+static int meth_scan_u32(bsx_meth *m, uint32_t *in, uint32_t *out, size_t n)
+{
+    size_t need = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0u, n, rocprim::plus<uint32_t>(), m->stream));
+    HIP_TRY(m->d_temp.reserve(need));
+    HIP_TRY(rocprim::exclusive_scan(m->d_temp.p, need, in, out, 0u, n, rocprim::plus<uint32_t>(), m->stream));
+    return BSX_OK;
+}
 
+// ---- the CpG index of the epiallele tally (DESIGN §3.11) ----
 static void meth_epi_drop_index(bsx_meth *m)
 {
-    for (uint32_t **q : {&m->d_cpg_dir, &m->d_cpg_pos, &m->d_epi}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    m->d_cpg_dir.release(); m->d_cpg_pos.release(); m->d_epi.release();
     m->cpg_first.clear();
     m->cpg_built = false; m->epi_last_rows = 0;
 }
@@ -867,30 +939,31 @@ static int meth_epi_index(bsx_meth *m)
     if (m->cpg_built) return BSX_OK;
     const u64 total = m->chr_off.back(), n_blocks = (total + 63) / 64;
     if (total >= (1ull << 33)) { g_bsx_err = "the epiallele tally takes a reference of fewer than 2^33 letters"; return BSX_ERR_LIMIT; }
-    uint32_t *d_cnt = nullptr, *d_first = nullptr;
-    int rc = BSX_OK;
-    auto chk = [&](hipError_t e) { if (e != hipSuccess && rc == BSX_OK) rc = e == hipErrorOutOfMemory ? ((void)hipGetLastError(), BSX_ERR_NOMEM) : bsx_hip_fail(e, "meth_epi_index", __FILE__, __LINE__); };
+    DevBuf<uint32_t> d_cnt, d_first;
     const MethDev M = m->dev();
-    chk(hipMalloc((void **)&d_cnt, (n_blocks + 1) * 4)); chk(hipMalloc((void **)&m->d_cpg_dir, (n_blocks + 1) * 4)); chk(hipMalloc((void **)&d_first, ((size_t)m->n_chr + 1) * 4));
-    if (rc == BSX_OK) chk(hipMemsetAsync(d_cnt + n_blocks, 0, 4, m->stream));
-    if (rc == BSX_OK && n_blocks) { hipLaunchKernelGGL(k_cpg_count, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, m->stream, M, n_blocks, d_cnt); chk(hipGetLastError()); }
-    if (rc == BSX_OK) rc = meth_scan_u32(m, d_cnt, m->d_cpg_dir, (size_t)n_blocks + 1);
-    if (rc == BSX_OK) {
-        hipLaunchKernelGGL(k_cpg_chr_first, dim3(m->n_chr + 1), dim3(64), 0, m->stream, M, (const uint32_t *)m->d_cpg_dir, d_first);
-        chk(hipGetLastError());
-        m->cpg_first.assign((size_t)m->n_chr + 1, 0);
-        chk(hipMemcpyAsync(m->cpg_first.data(), d_first, ((size_t)m->n_chr + 1) * 4, hipMemcpyDeviceToHost, m->stream));
-        chk(hipStreamSynchronize(m->stream));
-    }
-    if (rc == BSX_OK) {
+    const size_t n_first = (size_t)m->n_chr + 1;
+    auto build = [&]() -> int {
+        HIP_TRY(d_cnt.reserve((n_blocks + 1) * 4)); HIP_TRY(m->d_cpg_dir.reserve((n_blocks + 1) * 4)); HIP_TRY(d_first.reserve(n_first * 4));
+        HIP_TRY(hipMemsetAsync(d_cnt.p + n_blocks, 0, 4, m->stream));
+        if (n_blocks) { hipLaunchKernelGGL(k_cpg_count, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, m->stream, M, n_blocks, d_cnt.p); HIP_TRY(hipGetLastError()); }
+        const int rc = meth_scan_u32(m, d_cnt.p, m->d_cpg_dir.p, (size_t)n_blocks + 1);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_cpg_chr_first, dim3(m->n_chr + 1), dim3(64), 0, m->stream, M, (const uint32_t *)m->d_cpg_dir.p, d_first.p);
+        HIP_TRY(hipGetLastError());
+        m->cpg_first.assign(n_first, 0);
+        HIP_TRY(hipMemcpyAsync(m->cpg_first.data(), d_first.p, n_first * 4, hipMemcpyDeviceToHost, m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream));
         const size_t n_cpg = m->cpg_first.back();
-        chk(hipMalloc((void **)&m->d_cpg_pos, (n_cpg + 4) * 4)); chk(hipMalloc((void **)&m->d_epi, (n_cpg + 1) * 64));
-        if (rc == BSX_OK) chk(hipMemsetAsync(m->d_epi, 0, (n_cpg + 1) * 64, m->stream));
-        if (rc == BSX_OK && n_blocks) { hipLaunchKernelGGL(k_cpg_emit, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, m->stream, M, n_blocks, (const uint32_t *)m->d_cpg_dir, m->d_cpg_pos); chk(hipGetLastError()); }
-        if (rc == BSX_OK) chk(hipStreamSynchronize(m->stream));
-    }
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_first) (void)hipFree(d_first);
+        HIP_TRY(m->d_cpg_pos.reserve((n_cpg + 4) * 4));
+        HIP_TRY(m->d_epi.zeroed((n_cpg + 1) * 64, m->stream));
+        if (n_blocks) {
+            hipLaunchKernelGGL(k_cpg_emit, dim3((unsigned)((n_blocks + 3) / 4)), dim3(256), 0, m->stream, M, n_blocks, (const uint32_t *)m->d_cpg_dir.p, m->d_cpg_pos.p);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(m->stream));
+        }
+        return BSX_OK;
+    };
+    const int rc = build();
     if (rc != BSX_OK) { meth_epi_drop_index(m); return rc; }
     m->cpg_built = true;
     return BSX_OK;
@@ -899,12 +972,7 @@ static int meth_epi_index(bsx_meth *m)
 extern "C" void bsx_meth_destroy(bsx_meth *m)
 {
     if (!m) return;
-    (void)hipSetDevice(m->device);
-    for (void *q : {(void *)m->d_ref, (void *)m->d_chr_off, (void *)m->d_counts, (void *)m->d_depth, (void *)m->d_meth, (void *)m->d_first, (void *)m->d_blk,
-                    (void *)m->d_blk_start, (void *)m->d_out[0], (void *)m->d_out[1], (void *)m->d_out[2], (void *)m->d_ctx, m->d_temp, (void *)m->d_mbias, (void *)m->d_rev, (void *)m->d_out_rev[0], (void *)m->d_out_rev[1],
-                    (void *)m->d_hist, (void *)m->d_pdr, (void *)m->d_pdr_out[0], (void *)m->d_pdr_out[1], (void *)m->d_pdr_out[2], (void *)m->d_pdr_letter,
-                    (void *)m->d_cpg_dir, (void *)m->d_cpg_pos, (void *)m->d_epi, (void *)m->d_epi_out[0], (void *)m->d_epi_out[1]})
-        if (q) (void)hipFree(q);
+    (void)hipSetDevice(m->device);  // ahead of the buffers' release
     if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
 }
@@ -924,16 +992,15 @@ extern "C" int bsx_meth_create(uint32_t n_chr, const uint64_t *chr_len, int rm_d
     const u64 total = m->chr_off.back();
     auto fail = [&](int rc) { bsx_meth_destroy(m); return rc; };
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    if (hipMalloc((void **)&m->d_ref, total + 16) != hipSuccess || hipMalloc((void **)&m->d_depth, (total + 16) * 4) != hipSuccess ||
-        hipMalloc((void **)&m->d_meth, (total + 16) * 4) != hipSuccess || hipMalloc((void **)&m->d_chr_off, (n_chr + 1) * 8) != hipSuccess ||
-        hipMalloc((void **)&m->d_counts, 64) != hipSuccess)
+    if (m->d_ref.reserve(total + 16) != hipSuccess || m->d_depth.reserve((total + 16) * 4) != hipSuccess || m->d_meth.reserve((total + 16) * 4) != hipSuccess ||
+        m->d_chr_off.reserve((n_chr + 1) * 8) != hipSuccess || m->d_counts.reserve(CNT_CELLS * 8) != hipSuccess)
         return fail(BSX_ERR_NOMEM);
-    if (rm_dup && hipMalloc((void **)&m->d_first, 2 * (total + 16) * 4) != hipSuccess) return fail(BSX_ERR_NOMEM);
-    if (hipMemsetAsync(m->d_ref, 0, total + 16, m->stream) != hipSuccess || hipMemsetAsync(m->d_depth, 0, (total + 16) * 4, m->stream) != hipSuccess ||
-        hipMemsetAsync(m->d_meth, 0, (total + 16) * 4, m->stream) != hipSuccess || hipMemsetAsync(m->d_counts, 0, 64, m->stream) != hipSuccess)
+    if (rm_dup && m->d_first.reserve(2 * (total + 16) * 4) != hipSuccess) return fail(BSX_ERR_NOMEM);
+    if (hipMemsetAsync(m->d_ref.p, 0, total + 16, m->stream) != hipSuccess || hipMemsetAsync(m->d_depth.p, 0, (total + 16) * 4, m->stream) != hipSuccess ||
+        hipMemsetAsync(m->d_meth.p, 0, (total + 16) * 4, m->stream) != hipSuccess || hipMemsetAsync(m->d_counts.p, 0, CNT_CELLS * 8, m->stream) != hipSuccess)
         return fail(BSX_ERR_DEVICE);
-    if (rm_dup && hipMemsetAsync(m->d_first, 0xff, 2 * (total + 16) * 4, m->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    if (hipMemcpyAsync(m->d_chr_off, m->chr_off.data(), (n_chr + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
+    if (rm_dup && hipMemsetAsync(m->d_first.p, 0xff, 2 * (total + 16) * 4, m->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
+    if (hipMemcpyAsync(m->d_chr_off.p, m->chr_off.data(), (n_chr + 1) * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
     if (hipStreamSynchronize(m->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
     *out = m;
     return BSX_OK;
@@ -944,7 +1011,7 @@ extern "C" int bsx_meth_set_reference(bsx_meth *m, uint32_t chr, const char *upp
     if (!m || chr >= m->n_chr || !upper_seq) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
     if (m->cpg_built) meth_epi_drop_index(m);  // other letters, other CpGs: the index and the cells are built again when they are next needed
-    HIP_TRY(hipMemcpy(m->d_ref + m->chr_off[chr], upper_seq, m->chr_off[chr + 1] - m->chr_off[chr], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_ref.p + m->chr_off[chr], upper_seq, m->chr_off[chr + 1] - m->chr_off[chr], hipMemcpyHostToDevice));
     return BSX_OK;
 }
 
@@ -974,24 +1041,25 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
         AlnBatch B; B.chr = d_chr; B.pos = d_pos; B.strand = d_strand; B.insert = d_ins; B.cut_at = d_cut; B.seq = d_seq; B.seq_off = d_off;
         B.n = n; B.index_base = m->index_base; B.trim_fillin = trim_fillin; B.trim5 = m->trim5; B.trim3 = m->trim3; B.drop = nullptr;
         const MethDev M = m->dev();
-        if (m->d_first) hipLaunchKernelGGL(k_meth_first, dim3((n + 255) / 256), dim3(256), 0, m->stream, M, B);
-        if (m->nonconv || m->d_hist || m->d_pdr) {  // the per-read pass: it sees the unfiltered window (B.drop is still null) and writes every flag of d_drop
+        u64 *const n_valid = m->d_counts.p + CNT_VALID, *const rev = m->d_rev.p;
+        if (M.first) hipLaunchKernelGGL(k_meth_first, dim3((n + 255) / 256), dim3(256), 0, m->stream, M, B);
+        if (m->nonconv || m->d_hist.p || m->d_pdr.p) {  // the per-read pass: it sees the unfiltered window (B.drop is still null) and writes every flag of d_drop
             const unsigned waves = RS_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * RS_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
-            const ReadsDev R{m->d_hist, m->d_pdr, m->d_counts + 3, d_drop, m->nonconv, m->min_cpg};
+            const ReadsDev R{m->d_hist.p, m->d_pdr.p, m->d_counts.p + CNT_DROPPED, d_drop, m->nonconv, m->min_cpg};
             hipLaunchKernelGGL(k_meth_reads, dim3(grid), dim3(RS_BLOCK), 0, m->stream, M, B, R);
             B.drop = d_drop;
         }
         if (m->epi)  // behind the verdicts of the non-conversion filter, ahead of the pile-up
-            hipLaunchKernelGGL(k_meth_epi, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, EpiDev{m->d_cpg_dir, m->d_epi, (u64)m->cpg_first.back()});
-        if (m->d_mbias) {  // the grid comes from the CU count; a batch too small to give every wave an alignment gets fewer blocks (fewer flushes)
+            hipLaunchKernelGGL(k_meth_epi, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, EpiDev{m->d_cpg_dir.p, m->d_epi.p, (u64)m->cpg_first.back()});
+        if (m->d_mbias.p) {  // the grid comes from the CU count; a batch too small to give every wave an alignment gets fewer blocks (fewer flushes)
             const unsigned waves = MB_BLOCK / 64, grid = (unsigned)std::min<u64>((u64)m->n_cu * MB_BLOCKS_PER_CU, ((u64)n + waves - 1) / waves);
-            const MbiasDev D{m->d_mbias, m->d_mbias + MB_CELLS};
-            if (m->d_rev) hipLaunchKernelGGL(k_meth_pile_mbias<true>, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, m->d_counts, D, m->d_rev);
-            else hipLaunchKernelGGL(k_meth_pile_mbias<false>, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, m->d_counts, D, m->d_rev);
-        } else if (m->d_rev)
-            hipLaunchKernelGGL(k_meth_pile<true>, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts, m->d_rev);
+            const MbiasDev D{m->d_mbias.p, m->d_mbias.p + MB_CELLS};
+            if (rev) hipLaunchKernelGGL(k_meth_pile_mbias<true>, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, n_valid, D, rev);
+            else hipLaunchKernelGGL(k_meth_pile_mbias<false>, dim3(grid), dim3(MB_BLOCK), 0, m->stream, M, B, n_valid, D, rev);
+        } else if (rev)
+            hipLaunchKernelGGL(k_meth_pile<true>, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, n_valid, rev);
         else
-            hipLaunchKernelGGL(k_meth_pile<false>, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, m->d_counts, m->d_rev);
+            hipLaunchKernelGGL(k_meth_pile<false>, dim3((n + 3) / 4), dim3(256), 0, m->stream, M, B, n_valid, rev);
         chk(hipGetLastError());
         chk(hipStreamSynchronize(m->stream));
         m->index_base += n;
@@ -1012,16 +1080,8 @@ extern "C" int bsx_meth_set_mbias(bsx_meth *m, int on)
     if (!m) return BSX_ERR_ARG;
     if (m->index_base) { g_bsx_err = "bsx_meth_set_mbias after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!on) {
-        if (m->d_mbias) (void)hipFree(m->d_mbias);
-        m->d_mbias = nullptr;
-        return BSX_OK;
-    }
-    if (m->d_mbias) return BSX_OK;
-    if (hipMalloc((void **)&m->d_mbias, (MB_CELLS + 1) * 8) != hipSuccess) { m->d_mbias = nullptr; return BSX_ERR_NOMEM; }
-    hipError_t e = hipMemsetAsync(m->d_mbias, 0, (MB_CELLS + 1) * 8, m->stream);  // on the handle's stream: it does not wait for the null stream
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) { (void)hipFree(m->d_mbias); m->d_mbias = nullptr; HIP_TRY(e); }
+    if (!on) m->d_mbias.release();
+    else if (!m->d_mbias.p) HIP_TRY(m->d_mbias.zeroed((MB_CELLS + 1) * 8, m->stream));
     return BSX_OK;
 }
 
@@ -1031,16 +1091,8 @@ extern "C" int bsx_meth_set_ct_snp(bsx_meth *m, int mode)
     if ((mode != 0) == (m->snp != 0)) { m->snp = mode; return BSX_OK; }  // 1 <-> 2 at any time: the counters are the same
     if (m->index_base) { g_bsx_err = "bsx_meth_set_ct_snp on or off after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!mode) {
-        if (m->d_rev) (void)hipFree(m->d_rev);
-        m->d_rev = nullptr; m->snp = 0;
-        return BSX_OK;
-    }
-    const size_t bytes = (size_t)(m->chr_off.back() + 16) * 8;
-    if (hipMalloc((void **)&m->d_rev, bytes) != hipSuccess) { (void)hipGetLastError(); m->d_rev = nullptr; return BSX_ERR_NOMEM; }
-    hipError_t e = hipMemsetAsync(m->d_rev, 0, bytes, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) { (void)hipFree(m->d_rev); m->d_rev = nullptr; HIP_TRY(e); }
+    if (!mode) m->d_rev.release();
+    else HIP_TRY(m->d_rev.zeroed((size_t)(m->chr_off.back() + 16) * 8, m->stream));
     m->snp = mode;
     return BSX_OK;
 }
@@ -1055,17 +1107,108 @@ extern "C" int bsx_meth_set_contexts(bsx_meth *m, uint32_t mask)
 extern "C" int bsx_meth_mbias_fetch(bsx_meth *m, uint64_t *cells, uint64_t *overflow_calls)
 {
     if (!m || !cells) return BSX_ERR_ARG;
-    if (!m->d_mbias) { g_bsx_err = "the M-bias tally is off (bsx_meth_set_mbias)"; return BSX_ERR_STATE; }
+    if (!m->d_mbias.p) { g_bsx_err = "the M-bias tally is off (bsx_meth_set_mbias)"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy(cells, m->d_mbias, MB_CELLS * 8, hipMemcpyDeviceToHost));
-    if (overflow_calls) HIP_TRY(hipMemcpy(overflow_calls, m->d_mbias + MB_CELLS, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cells, m->d_mbias.p, MB_CELLS * 8, hipMemcpyDeviceToHost));
+    if (overflow_calls) HIP_TRY(hipMemcpy(overflow_calls, m->d_mbias.p + MB_CELLS, 8, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
+
+// ---- what the file writers and readers share ----
+namespace {
+
+// no C++ exception may cross the C ABI: fn() with a failed host allocation as BSX_ERR_NOMEM and any other exception as BSX_ERR_IO; `doing`: "writing" or "reading"
+template <class Fn>
+int guarded(const char *path, const char *doing, Fn fn)
+{
+    try {
+        return fn();
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = std::string("out of host memory while ") + doing + " " + path; return BSX_ERR_NOMEM;
+    } catch (const std::exception &x) {
+        g_bsx_err = std::string(doing) + " " + path + ": " + x.what(); return BSX_ERR_IO;
+    }
+}
+
+struct OutFile {  // an output file that is closed on every way out; finish() closes it and says whether all of it was written
+    FILE *f;
+    const char *path;
+    explicit OutFile(const char *p) : f(fopen(p, "w")), path(p) {}
+    OutFile(const OutFile &) = delete;
+    OutFile &operator=(const OutFile &) = delete;
+    ~OutFile() { if (f) fclose(f); }
+    int cannot_write() const { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }  // (also the answer to f == nullptr)
+    int finish(bool bad = false)
+    {
+        FILE *const g = f;
+        f = nullptr;
+        return ((fclose(g) != 0) | bad) ? cannot_write() : BSX_OK;
+    }
+};
+
+// the whole text to `path`; BSX_ERR_IO when it cannot be written
+int meth_write_text(const char *path, const std::string &o)
+{
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    return out.finish(fwrite(o.data(), 1, o.size(), out.f) != o.size());
+}
+
+struct Mapping {  // a read-only memory map of a whole file, unmapped on every way out
+    const char *base = nullptr; size_t len = 0;
+    ~Mapping() { if (base) munmap((void *)base, len); }
+    int open(const char *path)  // BSX_OK (len == 0 for an empty file) or BSX_ERR_IO
+    {
+        const int fd = ::open(path, O_RDONLY);
+        if (fd < 0) { g_bsx_err = std::string("cannot open ") + path; return BSX_ERR_IO; }
+        struct stat st;
+        if (fstat(fd, &st) != 0) { ::close(fd); g_bsx_err = std::string("cannot stat ") + path; return BSX_ERR_IO; }
+        len = (size_t)st.st_size;
+        if (!len) { ::close(fd); return BSX_OK; }
+        void *q = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
+        ::close(fd);
+        if (q == MAP_FAILED) { len = 0; g_bsx_err = std::string("cannot map ") + path; return BSX_ERR_IO; }
+        base = (const char *)q;
+        return BSX_OK;
+    }
+};
+
+// the chromosomes in sorted name order, the order the reference's table has; chr_names: the caller's names in place of the handle's own
+std::vector<uint32_t> sorted_chromosomes(const bsx_meth *m, const char *const *chr_names = nullptr)
+{
+    std::vector<std::string> names;
+    for (uint32_t c = 0; c < m->n_chr; c++) names.push_back(chr_names ? std::string(chr_names[c]) : m->names[c]);
+    std::vector<uint32_t> o;
+    for (uint32_t c = 0; c < m->n_chr; c++) o.push_back(c);
+    std::sort(o.begin(), o.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+    return o;
+}
+
+// `rows` lines formatted by a pool of host threads, each a contiguous range, appended to `f` in order
+template <class Fmt>
+void format_rows(FILE *f, size_t rows, size_t reserve_per_row, Fmt fmt_row)
+{
+    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(32u, std::max(1u, bsx_usable_cpus())), rows / 65536 + 1));
+    std::vector<std::string> parts(nt);
+    auto fmt = [&](unsigned t) {
+        std::string &o = parts[t];
+        const size_t lo = rows * t / nt, hi = rows * (t + 1) / nt;
+        o.reserve((hi - lo) * reserve_per_row);
+        for (size_t i = lo; i < hi; i++) fmt_row(i, o);
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(fmt, t);
+    fmt(0);
+    for (std::thread &x : th) x.join();
+    for (const std::string &o : parts) fwrite(o.data(), 1, o.size(), f);
+}
+
+}  // namespace
 
 extern "C" int bsx_meth_write_mbias(bsx_meth *m, const char *path)
 {
     if (!m || !path) return BSX_ERR_ARG;
-    try {
+    return guarded(path, "writing", [&]() -> int {
         std::vector<uint64_t> cells(MB_CELLS);
         uint64_t over = 0;
         const int rc = bsx_meth_mbias_fetch(m, cells.data(), &over);
@@ -1094,21 +1237,15 @@ extern "C" int bsx_meth_write_mbias(bsx_meth *m, const char *path)
             o.append(line, (size_t)snprintf(line, sizeof(line), "# total\t%s\t%llu\t%llu\t%s\n", contexts[x], (u64)tot[x][0], (u64)tot[x][1], r));
         }
         o.append(line, (size_t)snprintf(line, sizeof(line), "# calls beyond cycle %d: %llu\n", BSX_MBIAS_CYCLES, (u64)over));
-        FILE *f = fopen(path, "w");
-        if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-        const bool bad = fwrite(o.data(), 1, o.size(), f) != o.size();
-        if ((fclose(f) != 0) | bad) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-        return BSX_OK;
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
-    }
+        return meth_write_text(path, o);
+    });
 }
 
 extern "C" int bsx_meth_combine_cpg(bsx_meth *m)
 {
     if (!m) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
-    hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev(), m->d_rev, m->d_pdr);
+    hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev(), m->d_rev.p, m->d_pdr.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m->stream));
     return BSX_OK;
@@ -1118,78 +1255,68 @@ extern "C" int bsx_meth_valid_mappings(bsx_meth *m, uint64_t *n)
 {
     if (!m || !n) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy(n, m->d_counts, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(n, m->d_counts.p + CNT_VALID, 8, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
-// the per-block row counts of a report over nblk blocks of 1 024 positions: d_blk[nblk + 1] (the last one zeroed here) and their exclusive scan d_blk_start
-static int meth_block_buffers(bsx_meth *m, size_t nblk)
+// ---- the reports: count, scan, size, emit (the host side of the ordered compaction) ----
+// The rows of one report over n_items items, in blocks of 1 024: `count` launches the rule's count kernel over nblk blocks into d_blk[nblk + 1] (the last
+// one zeroed here), their exclusive scan d_blk_start ends in the number of rows, `reserve` makes room for that many (not called for none) and `emit`
+// launches the rule's emit kernel.  *n_rows and last_rows are 0 on every early way out and the number of rows when the rows are in place.
+template <class CountFn, class ReserveFn, class EmitFn>
+static int meth_compact(bsx_meth *m, u64 n_items, uint32_t *n_rows, uint32_t &last_rows, CountFn count, ReserveFn reserve, EmitFn emit)
 {
-    if (nblk + 1 > m->blk_cap) {
-        if (m->d_blk) (void)hipFree(m->d_blk);
-        if (m->d_blk_start) (void)hipFree(m->d_blk_start);
-        m->d_blk = m->d_blk_start = nullptr; m->blk_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->d_blk, (nblk + 1) * 4)); HIP_TRY(hipMalloc((void **)&m->d_blk_start, (nblk + 1) * 4));
-        m->blk_cap = nblk + 1;
+    *n_rows = 0; last_rows = 0;
+    const size_t nblk = (size_t)((n_items + 1023) / 1024);
+    if (!nblk) return BSX_OK;
+    HIP_TRY(m->d_blk.reserve((nblk + 1) * 4)); HIP_TRY(m->d_blk_start.reserve((nblk + 1) * 4));
+    HIP_TRY(hipMemsetAsync(m->d_blk.p + nblk, 0, 4, m->stream));
+    count((unsigned)nblk);
+    HIP_TRY(hipGetLastError());
+    int rc = meth_scan_u32(m, m->d_blk.p, m->d_blk_start.p, nblk + 1);
+    if (rc) return rc;
+    uint32_t rows = 0;
+    HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start.p + nblk, 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (rows) {
+        rc = reserve((size_t)rows);
+        if (rc) return rc;
+        emit((unsigned)nblk);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m->stream));
     }
-    HIP_TRY(hipMemsetAsync(m->d_blk + nblk, 0, 4, m->stream));
+    *n_rows = rows; last_rows = rows;
     return BSX_OK;
 }
-
-// out[k] = in[0] + .. + in[k - 1] for k < n, on the handle's stream and with its scratch buffer
-static int meth_scan_u32(bsx_meth *m, uint32_t *in, uint32_t *out, size_t n)
-{
-    size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, in, out, 0u, n, rocprim::plus<uint32_t>(), m->stream));
-    if (need > m->temp_cap) { if (m->d_temp) (void)hipFree(m->d_temp); m->d_temp = nullptr; m->temp_cap = 0; HIP_TRY(hipMalloc(&m->d_temp, need)); m->temp_cap = need; }
-    HIP_TRY(rocprim::exclusive_scan(m->d_temp, need, in, out, 0u, n, rocprim::plus<uint32_t>(), m->stream));
-    return BSX_OK;
-}
-
-static int meth_scan_blocks(bsx_meth *m, size_t nblk) { return meth_scan_u32(m, m->d_blk, m->d_blk_start, nblk + 1); }
 
 extern "C" int bsx_meth_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_depth, int meth0, uint32_t *n_rows, uint64_t *n_covered, uint64_t *sum_depth)
 {
     if (!m || chr >= m->n_chr || !n_rows) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
     const u64 g0 = m->chr_off[chr], n = m->chr_off[chr + 1] - g0;
-    const size_t nblk = (size_t)((n + 1023) / 1024);
-    *n_rows = 0; m->last_rows = 0;
     if (n_covered) *n_covered = 0;
     if (sum_depth) *sum_depth = 0;
-    if (!nblk) return BSX_OK;
-    int rc = meth_block_buffers(m, nblk);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_counts + 1, 0, 16, m->stream));
     const MethDev M = m->dev();
     const RowRule R{min_depth, m->ctx_mask, meth0, m->snp};
-    hipLaunchKernelGGL(k_meth_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk, m->d_counts + 1, m->d_rev);
-    HIP_TRY(hipGetLastError());
-    rc = meth_scan_blocks(m, nblk);
-    if (rc) return rc;
-    uint32_t rows = 0; u64 cnt[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipMemcpyAsync(cnt, m->d_counts + 1, 16, hipMemcpyDeviceToHost, m->stream));
+    u64 *const nc_nd = m->d_counts.p + CNT_NC;  // CNT_NC and CNT_ND: k_meth_count adds to them
+    *n_rows = 0; m->last_rows = 0;
+    HIP_TRY(hipMemsetAsync(nc_nd, 0, 16, m->stream));
+    const int rc = meth_compact(m, n, n_rows, m->last_rows,
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_meth_count, dim3(nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk.p, nc_nd, m->d_rev.p); },
+        [&](size_t rows) -> int {
+            for (DevBuf<uint32_t> &b : m->d_out) HIP_TRY(b.reserve(rows * 4));
+            if (m->snp) for (DevBuf<uint32_t> &b : m->d_out_rev) HIP_TRY(b.reserve(rows * 4));
+            HIP_TRY(m->d_ctx.reserve(rows * 8));
+            return BSX_OK;
+        },
+        [&](unsigned nblk) {
+            hipLaunchKernelGGL(k_meth_emit, dim3(nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk_start.p, m->d_out[0].p, m->d_out[1].p, m->d_out[2].p, m->d_ctx.p,
+                               m->d_out_rev[0].p, m->d_out_rev[1].p, m->d_rev.p);
+        });
+    if (rc || !n) return rc;
+    u64 cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, nc_nd, 16, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
-    if (rows > m->out_cap || (m->snp && rows && !m->d_out_rev[0])) {
-        for (int k = 0; k < 3; k++) { if (m->d_out[k]) (void)hipFree(m->d_out[k]); m->d_out[k] = nullptr; }
-        for (int k = 0; k < 2; k++) { if (m->d_out_rev[k]) (void)hipFree(m->d_out_rev[k]); m->d_out_rev[k] = nullptr; }
-        if (m->d_ctx) (void)hipFree(m->d_ctx);
-        m->d_ctx = nullptr;
-        const size_t cap = std::max<size_t>(rows, m->out_cap);
-        m->out_cap = 0;
-        for (int k = 0; k < 3; k++) HIP_TRY(hipMalloc((void **)&m->d_out[k], cap * 4));
-        if (m->snp) for (int k = 0; k < 2; k++) HIP_TRY(hipMalloc((void **)&m->d_out_rev[k], cap * 4));
-        HIP_TRY(hipMalloc((void **)&m->d_ctx, cap * 8));
-        m->out_cap = cap;
-    }
-    if (rows) {
-        hipLaunchKernelGGL(k_meth_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, M, g0, n, R, m->d_blk_start, m->d_out[0], m->d_out[1], m->d_out[2], m->d_ctx,
-                           m->d_out_rev[0], m->d_out_rev[1], m->d_rev);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(m->stream));
-    }
-    *n_rows = rows; m->last_rows = rows;
     if (n_covered) *n_covered = cnt[0];
     if (sum_depth) *sum_depth = cnt[1];
     return BSX_OK;
@@ -1200,9 +1327,8 @@ extern "C" int bsx_meth_fetch_rows(bsx_meth *m, uint32_t *pos, uint32_t *depth, 
     if (!m || !pos || !depth || !meth) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
     if (!m->last_rows) return BSX_OK;
-    HIP_TRY(hipMemcpy(pos, m->d_out[0], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(depth, m->d_out[1], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(meth, m->d_out[2], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
+    uint32_t *const out[3] = {pos, depth, meth};
+    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpy(out[k], m->d_out[k].p, (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -1212,8 +1338,8 @@ extern "C" int bsx_meth_fetch_rows_snp(bsx_meth *m, uint32_t *rev_g, uint32_t *r
     if (!m->snp) { g_bsx_err = "the C/T-SNP mode is off (bsx_meth_set_ct_snp)"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
     if (!m->last_rows) return BSX_OK;
-    HIP_TRY(hipMemcpy(rev_g, m->d_out_rev[0], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rev_ga, m->d_out_rev[1], (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rev_g, m->d_out_rev[0].p, (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rev_ga, m->d_out_rev[1].p, (size_t)m->last_rows * 4, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -1229,19 +1355,7 @@ extern "C" int bsx_meth_nonconv_dropped(bsx_meth *m, uint64_t *n)
 {
     if (!m || !n) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy(n, m->d_counts + 3, 8, hipMemcpyDeviceToHost));
-    return BSX_OK;
-}
-
-// a zeroed array of u64 cells on the handle's stream (it does not wait for the null stream); BSX_ERR_NOMEM when it cannot be had
-static int meth_zeroed_cells(bsx_meth *m, u64 **out, size_t cells)
-{
-    u64 *p = nullptr;
-    if (hipMalloc((void **)&p, cells * 8) != hipSuccess) { (void)hipGetLastError(); return BSX_ERR_NOMEM; }
-    hipError_t e = hipMemsetAsync(p, 0, cells * 8, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) { (void)hipFree(p); HIP_TRY(e); }
-    *out = p;
+    HIP_TRY(hipMemcpy(n, m->d_counts.p + CNT_DROPPED, 8, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -1250,39 +1364,26 @@ extern "C" int bsx_meth_set_read_stats(bsx_meth *m, int on)
     if (!m) return BSX_ERR_ARG;
     if (m->index_base) { g_bsx_err = "bsx_meth_set_read_stats after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!on) {
-        if (m->d_hist) (void)hipFree(m->d_hist);
-        m->d_hist = nullptr;
-        return BSX_OK;
-    }
-    return m->d_hist ? BSX_OK : meth_zeroed_cells(m, &m->d_hist, RS_CELLS);
+    if (!on) m->d_hist.release();
+    else if (!m->d_hist.p) HIP_TRY(m->d_hist.zeroed(RS_CELLS * 8, m->stream));
+    return BSX_OK;
 }
 
 extern "C" int bsx_meth_read_stats_fetch(bsx_meth *m, uint64_t *cg, uint64_t *ch, uint64_t *totals)
 {
     if (!m || !cg || !ch || !totals) return BSX_ERR_ARG;
-    if (!m->d_hist) { g_bsx_err = "the read histogram is off (bsx_meth_set_read_stats)"; return BSX_ERR_STATE; }
+    if (!m->d_hist.p) { g_bsx_err = "the read histogram is off (bsx_meth_set_read_stats)"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipMemcpy(cg, m->d_hist, (size_t)RS_CG * RS_CG * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ch, m->d_hist + RS_CG * RS_CG, (size_t)RS_CH * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(totals, m->d_hist + RS_LDS_CELLS, 4 * 8, hipMemcpyDeviceToHost));
-    return BSX_OK;
-}
-
-// the whole text to `path`; BSX_ERR_IO when it cannot be written
-static int meth_write_text(const char *path, const std::string &o)
-{
-    FILE *f = fopen(path, "w");
-    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-    const bool bad = fwrite(o.data(), 1, o.size(), f) != o.size();
-    if ((fclose(f) != 0) | bad) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    HIP_TRY(hipMemcpy(cg, m->d_hist.p, (size_t)RS_CG * RS_CG * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ch, m->d_hist.p + RS_CG * RS_CG, (size_t)RS_CH * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(totals, m->d_hist.p + RS_LDS_CELLS, 4 * 8, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
 extern "C" int bsx_meth_write_read_stats(bsx_meth *m, const char *path)
 {
     if (!m || !path) return BSX_ERR_ARG;
-    try {
+    return guarded(path, "writing", [&]() -> int {
         std::vector<uint64_t> cg((size_t)RS_CG * RS_CG), ch(RS_CH);
         uint64_t tot[4] = {0, 0, 0, 0};
         const int rc = bsx_meth_read_stats_fetch(m, cg.data(), ch.data(), tot);
@@ -1299,71 +1400,50 @@ extern "C" int bsx_meth_write_read_stats(bsx_meth *m, const char *path)
         if (tot[2]) o.append(line, (size_t)snprintf(line, sizeof(line), "# CH ratio\t%.5f\n", (double)tot[3] / (double)tot[2]));
         else o += "# CH ratio\tNA\n";
         return meth_write_text(path, o);
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
-    }
+    });
 }
+
+static const char *const PDR_OFF = "PDR is off (bsx_meth_set_pdr)";
 
 extern "C" int bsx_meth_set_pdr(bsx_meth *m, uint32_t min_cpg)
 {
     if (!m) return BSX_ERR_ARG;
-    if ((min_cpg != 0) == (m->d_pdr != nullptr)) { m->min_cpg = min_cpg; return BSX_OK;}  // another threshold at any time: the cells are the same
+    if ((min_cpg != 0) == (m->d_pdr.p != nullptr)) { m->min_cpg = min_cpg; return BSX_OK;}  // another threshold at any time: the cells are the same
     if (m->index_base) { g_bsx_err = "bsx_meth_set_pdr on or off after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!min_cpg) {
-        (void)hipFree(m->d_pdr);
-        m->d_pdr = nullptr; m->min_cpg = 0;
-        return BSX_OK;
-    }
-    const int rc = meth_zeroed_cells(m, &m->d_pdr, (size_t)(m->chr_off.back() + 16));
-    if (rc == BSX_OK) m->min_cpg = min_cpg;
-    return rc;
+    if (!min_cpg) m->d_pdr.release();
+    else HIP_TRY(m->d_pdr.zeroed((size_t)(m->chr_off.back() + 16) * 8, m->stream));
+    m->min_cpg = min_cpg;
+    return BSX_OK;
 }
 
 extern "C" int bsx_meth_pdr_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_reads, uint32_t *n_rows)
 {
     if (!m || chr >= m->n_chr || !n_rows || !min_reads) return BSX_ERR_ARG;
-    if (!m->d_pdr) { g_bsx_err = "PDR is off (bsx_meth_set_pdr)"; return BSX_ERR_STATE; }
+    if (!m->d_pdr.p) { g_bsx_err = PDR_OFF; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
     const u64 g0 = m->chr_off[chr], n = m->chr_off[chr + 1] - g0;
-    const size_t nblk = (size_t)((n + 1023) / 1024);
-    *n_rows = 0; m->pdr_last_rows = 0;
-    if (!nblk) return BSX_OK;
-    int rc = meth_block_buffers(m, nblk);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_pdr_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const u64 *)m->d_pdr, g0, n, min_reads, m->d_blk);
-    HIP_TRY(hipGetLastError());
-    rc = meth_scan_blocks(m, nblk);
-    if (rc) return rc;
-    uint32_t rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (rows > m->pdr_out_cap) {
-        for (int k = 0; k < 3; k++) { if (m->d_pdr_out[k]) (void)hipFree(m->d_pdr_out[k]); m->d_pdr_out[k] = nullptr; }
-        if (m->d_pdr_letter) (void)hipFree(m->d_pdr_letter);
-        m->d_pdr_letter = nullptr; m->pdr_out_cap = 0;
-        for (int k = 0; k < 3; k++) HIP_TRY(hipMalloc((void **)&m->d_pdr_out[k], (size_t)rows * 4));
-        HIP_TRY(hipMalloc((void **)&m->d_pdr_letter, rows));
-        m->pdr_out_cap = rows;
-    }
-    if (rows) {
-        hipLaunchKernelGGL(k_pdr_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const uint8_t *)m->d_ref, (const u64 *)m->d_pdr, g0, n, min_reads,
-                           (const uint32_t *)m->d_blk_start, m->d_pdr_out[0], m->d_pdr_out[1], m->d_pdr_out[2], m->d_pdr_letter);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(m->stream));
-    }
-    *n_rows = rows; m->pdr_last_rows = rows;
-    return BSX_OK;
+    return meth_compact(m, n, n_rows, m->pdr_last_rows,
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_pdr_count, dim3(nblk), dim3(256), 0, m->stream, (const u64 *)m->d_pdr.p, g0, n, min_reads, m->d_blk.p); },
+        [&](size_t rows) -> int {
+            for (DevBuf<uint32_t> &b : m->d_pdr_out) HIP_TRY(b.reserve(rows * 4));
+            HIP_TRY(m->d_pdr_letter.reserve(rows));
+            return BSX_OK;
+        },
+        [&](unsigned nblk) {
+            hipLaunchKernelGGL(k_pdr_emit, dim3(nblk), dim3(256), 0, m->stream, (const uint8_t *)m->d_ref.p, (const u64 *)m->d_pdr.p, g0, n, min_reads,
+                               (const uint32_t *)m->d_blk_start.p, m->d_pdr_out[0].p, m->d_pdr_out[1].p, m->d_pdr_out[2].p, m->d_pdr_letter.p);
+        });
 }
 
 extern "C" int bsx_meth_pdr_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *reads, uint32_t *discordant)
 {
     if (!m || !pos0 || !reads || !discordant) return BSX_ERR_ARG;
-    if (!m->d_pdr) { g_bsx_err = "PDR is off (bsx_meth_set_pdr)"; return BSX_ERR_STATE; }
+    if (!m->d_pdr.p) { g_bsx_err = PDR_OFF; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
     if (!m->pdr_last_rows) return BSX_OK;
     uint32_t *const out[3] = {pos0, reads, discordant};
-    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpy(out[k], m->d_pdr_out[k], (size_t)m->pdr_last_rows * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 3; k++) HIP_TRY(hipMemcpy(out[k], m->d_pdr_out[k].p, (size_t)m->pdr_last_rows * 4, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -1397,35 +1477,19 @@ extern "C" int bsx_meth_epi_report_chr(bsx_meth *m, uint32_t chr, uint32_t min_r
     if (!m || chr >= m->n_chr || !n_rows || !min_reads) return BSX_ERR_ARG;
     if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    int rc = meth_epi_index(m);
+    const int rc = meth_epi_index(m);
     if (rc) return rc;
     const u64 o0 = m->cpg_first[chr], n_cpg = m->cpg_first[chr + 1] - o0, n = n_cpg >= 4 ? n_cpg - 3 : 0;  // the chromosome's windows
-    const size_t nblk = (size_t)((n + 1023) / 1024);
-    *n_rows = 0; m->epi_last_rows = 0;
-    if (!nblk) return BSX_OK;
-    rc = meth_block_buffers(m, nblk);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_epi_count, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const uint32_t *)m->d_epi, o0, n, min_reads, m->d_blk);
-    HIP_TRY(hipGetLastError());
-    rc = meth_scan_blocks(m, nblk);
-    if (rc) return rc;
-    uint32_t rows = 0;
-    HIP_TRY(hipMemcpyAsync(&rows, m->d_blk_start + nblk, 4, hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    if (rows > m->epi_out_cap) {
-        for (int k = 0; k < 2; k++) { if (m->d_epi_out[k]) (void)hipFree(m->d_epi_out[k]); m->d_epi_out[k] = nullptr; }
-        m->epi_out_cap = 0;
-        HIP_TRY(hipMalloc((void **)&m->d_epi_out[0], (size_t)rows * 16)); HIP_TRY(hipMalloc((void **)&m->d_epi_out[1], (size_t)rows * 64));
-        m->epi_out_cap = rows;
-    }
-    if (rows) {
-        hipLaunchKernelGGL(k_epi_emit, dim3((unsigned)nblk), dim3(256), 0, m->stream, (const uint32_t *)m->d_epi, (const uint32_t *)m->d_cpg_pos, o0, n, min_reads,
-                           (const uint32_t *)m->d_blk_start, m->d_epi_out[0], m->d_epi_out[1]);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(m->stream));
-    }
-    *n_rows = rows; m->epi_last_rows = rows;
-    return BSX_OK;
+    return meth_compact(m, n, n_rows, m->epi_last_rows,
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_epi_count, dim3(nblk), dim3(256), 0, m->stream, (const uint32_t *)m->d_epi.p, o0, n, min_reads, m->d_blk.p); },
+        [&](size_t rows) -> int {
+            HIP_TRY(m->d_epi_out[0].reserve(rows * 16)); HIP_TRY(m->d_epi_out[1].reserve(rows * 64));
+            return BSX_OK;
+        },
+        [&](unsigned nblk) {
+            hipLaunchKernelGGL(k_epi_emit, dim3(nblk), dim3(256), 0, m->stream, (const uint32_t *)m->d_epi.p, (const uint32_t *)m->d_cpg_pos.p, o0, n, min_reads,
+                               (const uint32_t *)m->d_blk_start.p, m->d_epi_out[0].p, m->d_epi_out[1].p);
+        });
 }
 
 extern "C" int bsx_meth_epi_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *counts)
@@ -1434,42 +1498,20 @@ extern "C" int bsx_meth_epi_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *co
     if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
     if (!m->epi_last_rows) return BSX_OK;
-    HIP_TRY(hipMemcpy(pos0, m->d_epi_out[0], (size_t)m->epi_last_rows * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(counts, m->d_epi_out[1], (size_t)m->epi_last_rows * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos0, m->d_epi_out[0].p, (size_t)m->epi_last_rows * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, m->d_epi_out[1].p, (size_t)m->epi_last_rows * 64, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
 // ---- host side for whole files: the reference's per-line Python is the slow part of the tool once the pile-up is on the GPU ----
-// The parsers (BSP / SAM lines, BAM records, FASTA) are plain C++ in bsx_meth_parse.h, where the host sanitizers reach them.
+// The parsers (BSP / SAM lines, BAM records, FASTA, BED) are plain C++ in bsx_meth_parse.h and the row formatters in bsx_meth_text.h and bsx_meth_epi.h,
+// where the host sanitizers reach them.
 using bsx_meth_parse::ParsedChunk;
-
-namespace {
-
-struct Mapping {  // a read-only memory map of a whole file, unmapped on every way out
-    const char *base = nullptr; size_t len = 0;
-    ~Mapping() { if (base) munmap((void *)base, len); }
-    int open(const char *path)  // BSX_OK (len == 0 for an empty file) or BSX_ERR_IO
-    {
-        const int fd = ::open(path, O_RDONLY);
-        if (fd < 0) { g_bsx_err = std::string("cannot open ") + path; return BSX_ERR_IO; }
-        struct stat st;
-        if (fstat(fd, &st) != 0) { ::close(fd); g_bsx_err = std::string("cannot stat ") + path; return BSX_ERR_IO; }
-        len = (size_t)st.st_size;
-        if (!len) { ::close(fd); return BSX_OK; }
-        void *q = mmap(nullptr, len, PROT_READ, MAP_PRIVATE, fd, 0);
-        ::close(fd);
-        if (q == MAP_FAILED) { len = 0; g_bsx_err = std::string("cannot map ") + path; return BSX_ERR_IO; }
-        base = (const char *)q;
-        return BSX_OK;
-    }
-};
-
-}  // namespace
 
 extern "C" int bsx_meth_add_file(bsx_meth *m, const char *path, int sam, const char *const *chr_names, int unique, int pair, uint32_t trim_fillin, uint64_t *n_lines)
 {
     if (!m || !path || (!chr_names && m->names.size() != m->n_chr)) return BSX_ERR_ARG;
-    try {  // (no C++ exception may cross the C ABI: a failed host allocation is BSX_ERR_NOMEM)
+    return guarded(path, "reading", [&]() -> int {
         Mapping map;
         if (n_lines) *n_lines = 0;
         const int rc_open = map.open(path);
@@ -1501,11 +1543,7 @@ extern "C" int bsx_meth_add_file(bsx_meth *m, const char *path, int sam, const c
         if (rc_add != BSX_OK) return rc_add;
         if (rcs == 2) { g_bsx_err = "alignment line without strand information"; return BSX_ERR_ARG; }
         return rcs ? BSX_ERR_IO : BSX_OK;
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while reading ") + path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("reading ") + path + ": " + x.what(); return BSX_ERR_IO;
-    }
+    });
 }
 
 // the table of methratio.py:130-151 for the chromosomes in `order` (the reference sorts the names), same arithmetic and formats
@@ -1513,23 +1551,15 @@ static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const ui
                        uint64_t *n_covered, uint64_t *sum_depth)
 {
     std::vector<uint32_t> sorted_order;
-    if (!order) {  // the reference writes the chromosomes in sorted name order
-        for (uint32_t c = 0; c < m->n_chr; c++) sorted_order.push_back(c);
-        std::sort(sorted_order.begin(), sorted_order.end(), [&](uint32_t a, uint32_t b) {
-            return (chr_names ? std::string(chr_names[a]) : m->names[a]) < (chr_names ? std::string(chr_names[b]) : m->names[b]); });
-        order = sorted_order.data(); n_order = m->n_chr;
-    }
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
-    FILE *f = closer.f;
-    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    if (!order) { sorted_order = sorted_chromosomes(m, chr_names); order = sorted_order.data(); n_order = m->n_chr; }
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
     const bool snp = m->snp != 0;  // C/T-SNP mode: the 12-column table of later BSMAP releases
     fputs(snp ? "chr\tpos\tstrand\tcontext\tratio\teff_CT_count\tC_count\tCT_count\trev_G_count\trev_GA_count\tCI_lower\tCI_upper\n"
-              : "chr\tpos\tstrand\tcontext\tratio\ttotal_C\tmethy_C\tCI_lower\tCI_upper\n", f);
+              : "chr\tpos\tstrand\tcontext\tratio\ttotal_C\tmethy_C\tCI_lower\tCI_upper\n", out.f);
     u64 nc = 0, nd = 0;
     int rc = BSX_OK;
-    const double z95 = 1.96, z95sq = 1.96 * 1.96;
     std::vector<uint32_t> pos, dep, met, rvg, rvga; std::vector<u64> ctx;
-    std::string buf;
     for (uint32_t k = 0; k < n_order && rc == BSX_OK; k++) {
         const uint32_t c = order[k];
         if (c >= m->n_chr) { rc = BSX_ERR_ARG; break; }
@@ -1546,42 +1576,11 @@ static int write_table(bsx_meth *m, const char *path, uint32_t n_order, const ui
             rc = bsx_meth_fetch_rows_snp(m, rvg.data(), rvga.data());
             if (rc) break;
         }
-        if (hipMemcpy(ctx.data(), m->d_ctx, (size_t)rows * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = BSX_ERR_DEVICE; break; }
+        if (hipMemcpy(ctx.data(), m->d_ctx.p, (size_t)rows * 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = BSX_ERR_DEVICE; break; }
         const char *name = chr_names ? chr_names[c] : m->names[c].c_str();
-        // rows are formatted by a pool of threads, each a contiguous range, and written in order
-        const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(32u, std::max(1u, bsx_usable_cpus())), rows / 65536 + 1));
-        std::vector<std::string> parts(nt);
-        auto fmt = [&](unsigned t) {
-            std::string &o = parts[t];
-            const size_t lo = (size_t)rows * t / nt, hi = (size_t)rows * (t + 1) / nt;
-            o.reserve((hi - lo) * (snp ? 72 : 56));
-            char line[256];
-            for (size_t i = lo; i < hi; i++) {
-                // with the mode on, d is the effective depth: the share of the raw depth that the opposite strand shows to be a real C
-                const double d = (snp && rvg[i] != rvga[i]) ? ((double)dep[i] * rvg[i]) / rvga[i] : (double)dep[i], mm = met[i];
-                const double ratio = snp ? (mm < d ? mm : d) / d : mm / d;
-                const double pmid = ratio + z95sq / (2 * d);
-                const double sd = z95 * pow(ratio * (1 - ratio) / d + z95sq / (4 * d * d), 0.5);
-                const double norminator = 1 + z95sq / d;
-                char cx[8]; int nb = 0;
-                for (; nb < 5; nb++) { const char ch = (char)((ctx[i] >> (8 * nb)) & 0xff); if (!ch) break; cx[nb] = ch; }
-                cx[nb] = 0;
-                const char letter = (char)(ctx[i] >> 56);
-                const int w = snp ? snprintf(line, sizeof(line), "%s\t%u\t%c\t%s\t%.3f\t%.2f\t%u\t%u\t%u\t%u\t%.3f\t%.3f\n", name, pos[i] + 1, letter == 'C' ? '+' : '-', cx, ratio,
-                                         d, met[i], dep[i], rvg[i], rvga[i], (pmid - sd) / norminator, (pmid + sd) / norminator)
-                                  : snprintf(line, sizeof(line), "%s\t%u\t%c\t%s\t%.3f\t%u\t%u\t%.3f\t%.3f\n", name, pos[i] + 1, letter == 'C' ? '+' : '-', cx, ratio, dep[i], met[i],
-                                             (pmid - sd) / norminator, (pmid + sd) / norminator);
-                o.append(line, (size_t)w);
-            }
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) th.emplace_back(fmt, t);
-        fmt(0);
-        for (std::thread &x : th) x.join();
-        for (const std::string &o : parts) fwrite(o.data(), 1, o.size(), f);
+        format_rows(out.f, rows, snp ? 72 : 56, [&](size_t i, std::string &o) { bsx_meth_text::append_table_row(o, name, pos[i], dep[i], met[i], ctx[i], snp, snp ? rvg[i] : 0u, snp ? rvga[i] : 0u); });
     }
-    closer.f = nullptr;
-    if (fclose(f) != 0 && rc == BSX_OK) { g_bsx_err = std::string("cannot write ") + path; rc = BSX_ERR_IO; }
+    if (rc == BSX_OK) rc = out.finish();
     if (n_covered) *n_covered = nc;
     if (sum_depth) *sum_depth = nd;
     return rc;
@@ -1591,13 +1590,7 @@ extern "C" int bsx_meth_write_table(bsx_meth *m, const char *path, uint32_t n_or
                                     uint64_t *n_covered, uint64_t *sum_depth)
 {
     if (!m || !path || (!chr_names && m->names.size() != m->n_chr)) return BSX_ERR_ARG;
-    try {
-        return write_table(m, path, n_order, order, chr_names, min_depth, meth0, n_covered, sum_depth);
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
-    }
+    return guarded(path, "writing", [&] { return write_table(m, path, n_order, order, chr_names, min_depth, meth0, n_covered, sum_depth); });
 }
 
 // the reference FASTA through bsx_meth_parse::parse_fasta (methratio.py:67-77); `chroms_csv` is the -c filter
@@ -1606,17 +1599,15 @@ extern "C" int bsx_meth_create_from_fasta(const char *path, const char *chroms_c
     if (!path || !out) return BSX_ERR_ARG;
     std::vector<std::string> names;
     std::vector<std::vector<char>> seqs;
-    try {
+    const int rc_parse = guarded(path, "reading", [&]() -> int {
         Mapping map;
         const int rc_open = map.open(path);
         if (rc_open != BSX_OK) return rc_open;
         if (!map.len) return BSX_ERR_IO;
         if (bsx_meth_parse::parse_fasta(map.base, map.len, chroms_csv, names, seqs)) { g_bsx_err = "no sequence selected from the reference file"; return BSX_ERR_ARG; }
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while reading ") + path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("reading ") + path + ": " + x.what(); return BSX_ERR_IO;
-    }
+        return BSX_OK;
+    });
+    if (rc_parse) return rc_parse;
     std::vector<uint64_t> lens;
     for (const std::vector<char> &q : seqs) lens.push_back(q.size());
     bsx_meth *m = nullptr;
@@ -1624,7 +1615,7 @@ extern "C" int bsx_meth_create_from_fasta(const char *path, const char *chroms_c
     if (rc) return rc;
     for (size_t i = 0; i < names.size() && rc == BSX_OK; i++) {
         m->names.push_back(names[i]);
-        if (!seqs[i].empty() && hipMemcpy(m->d_ref + m->chr_off[i], seqs[i].data(), seqs[i].size(), hipMemcpyHostToDevice) != hipSuccess) rc = BSX_ERR_DEVICE;
+        if (!seqs[i].empty() && hipMemcpy(m->d_ref.p + m->chr_off[i], seqs[i].data(), seqs[i].size(), hipMemcpyHostToDevice) != hipSuccess) rc = BSX_ERR_DEVICE;
         std::vector<char>().swap(seqs[i]);
     }
     if (rc) { bsx_meth_destroy(m); return rc; }
@@ -1636,17 +1627,7 @@ extern "C" uint32_t bsx_meth_n_chr(const bsx_meth *m) { return m ? m->n_chr : 0;
 extern "C" const char *bsx_meth_chr_name(const bsx_meth *m, uint32_t c) { return (m && c < m->names.size()) ? m->names[c].c_str() : ""; }
 
 // ---- pooled methylation per interval and per bin ----
-namespace {
-
-struct DevBuf {  // device memory that is freed on every way out
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t bytes) { if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; } return true; }
-};
-
-constexpr size_t REGION_CHUNK = (size_t)1 << 22;  // a launch takes intervals until it holds this many of them or of their tiles
-
-}  // namespace
+static constexpr size_t REGION_CHUNK = (size_t)1 << 22;  // a launch takes intervals until it holds this many of them or of their tiles
 
 extern "C" uint32_t bsx_meth_region_tile(void) { return bsx_meth_tiles::TILE; }
 
@@ -1671,8 +1652,11 @@ static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint
         cut_at.push_back(b);
         a = b;
     }
-    DevBuf d_tiles, d_chr, d_start, d_sums;
-    if (!d_tiles.alloc(max_tiles * sizeof(bsx_meth_tiles::Tile)) || !d_chr.alloc(max_iv * 4) || !d_start.alloc(max_iv * 4) || !d_sums.alloc(max_iv * 40)) {
+    DevBuf<bsx_meth_tiles::Tile> d_tiles;
+    DevBuf<uint32_t> d_chr, d_start;
+    DevBuf<u64> d_sums;
+    if (d_tiles.reserve(max_tiles * sizeof(bsx_meth_tiles::Tile)) != hipSuccess || d_chr.reserve(max_iv * 4) != hipSuccess || d_start.reserve(max_iv * 4) != hipSuccess ||
+        d_sums.reserve(max_iv * 40) != hipSuccess) {
         g_bsx_err = "bsx_meth_regions: no device memory for the intervals"; return BSX_ERR_NOMEM;
     }
     const MethDev M = m->dev();
@@ -1693,8 +1677,8 @@ static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint
             const bool wide = 2 * in_long > nt;
             const unsigned waves = wide ? 16 : 4;
             auto kernel = m->snp ? (wide ? k_meth_regions<true, 16> : k_meth_regions<true, 4>) : (wide ? k_meth_regions<false, 16> : k_meth_regions<false, 4>);
-            hipLaunchKernelGGL(kernel, dim3((nt + waves - 1) / waves), dim3(waves * 64), 0, m->stream, M, R, (const u64 *)m->d_rev, (const bsx_meth_tiles::Tile *)d_tiles.p, nt,
-                               (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, (u64 *)d_sums.p);
+            hipLaunchKernelGGL(kernel, dim3((nt + waves - 1) / waves), dim3(waves * 64), 0, m->stream, M, R, (const u64 *)m->d_rev.p, (const bsx_meth_tiles::Tile *)d_tiles.p, nt,
+                               (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, d_sums.p);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(sums + (size_t)a * 5, d_sums.p, (size_t)(b - a) * 40, hipMemcpyDeviceToHost, m->stream));
@@ -1721,8 +1705,8 @@ extern "C" int bsx_meth_bins(bsx_meth *m, uint32_t chr, uint32_t bin, uint32_t m
     *n_bins = need;
     if (!sums || n_bins_cap < need) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
-    DevBuf d_bins;
-    if (!d_bins.alloc((size_t)need * 40)) { g_bsx_err = "bsx_meth_bins: no device memory for the bins"; return BSX_ERR_NOMEM; }
+    DevBuf<u64> d_bins;
+    if (d_bins.reserve((size_t)need * 40) != hipSuccess) { g_bsx_err = "bsx_meth_bins: no device memory for the bins"; return BSX_ERR_NOMEM; }
     HIP_TRY(hipMemsetAsync(d_bins.p, 0, (size_t)need * 40, m->stream));
     if (n) {
         // positions per block: 1 024 below B = 16 (the block's bin table is LDS), 4 096 from there on (fewer adds on the cells that wide bins share)
@@ -1731,8 +1715,8 @@ extern "C" int bsx_meth_bins(bsx_meth *m, uint32_t chr, uint32_t bin, uint32_t m
         const size_t lds = (size_t)std::min<u64>(P, (P - 1) / bin + 2) * 40;
         const MethDev M = m->dev();
         const RowRule R{min_depth, m->ctx_mask, 1, m->snp};
-        if (m->snp) hipLaunchKernelGGL(k_meth_bins<true>, dim3((unsigned)((n + P - 1) / P)), dim3(256), lds, m->stream, M, g0, n, R, m->d_rev, bin, rounds, (u64 *)d_bins.p);
-        else hipLaunchKernelGGL(k_meth_bins<false>, dim3((unsigned)((n + P - 1) / P)), dim3(256), lds, m->stream, M, g0, n, R, m->d_rev, bin, rounds, (u64 *)d_bins.p);
+        if (m->snp) hipLaunchKernelGGL(k_meth_bins<true>, dim3((unsigned)((n + P - 1) / P)), dim3(256), lds, m->stream, M, g0, n, R, m->d_rev.p, bin, rounds, d_bins.p);
+        else hipLaunchKernelGGL(k_meth_bins<false>, dim3((unsigned)((n + P - 1) / P)), dim3(256), lds, m->stream, M, g0, n, R, m->d_rev.p, bin, rounds, d_bins.p);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(sums, d_bins.p, (size_t)need * 40, hipMemcpyDeviceToHost, m->stream));
@@ -1742,58 +1726,22 @@ extern "C" int bsx_meth_bins(bsx_meth *m, uint32_t chr, uint32_t bin, uint32_t m
 
 namespace {
 
-// the chromosomes in sorted name order: the table's
-std::vector<uint32_t> sorted_chromosomes(const bsx_meth *m)
-{
-    std::vector<uint32_t> o;
-    for (uint32_t c = 0; c < m->n_chr; c++) o.push_back(c);
-    std::sort(o.begin(), o.end(), [&](uint32_t a, uint32_t b) { return m->names[a] < m->names[b]; });
-    return o;
-}
-
-// `rows` lines formatted by a pool of host threads, each a contiguous range, appended to `f` in order (as write_table does)
-template <class Fmt>
-void format_rows(FILE *f, size_t rows, size_t reserve_per_row, Fmt fmt_row)
-{
-    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>(std::min(32u, std::max(1u, bsx_usable_cpus())), rows / 65536 + 1));
-    std::vector<std::string> parts(nt);
-    auto fmt = [&](unsigned t) {
-        std::string &o = parts[t];
-        const size_t lo = rows * t / nt, hi = rows * (t + 1) / nt;
-        o.reserve((hi - lo) * reserve_per_row);
-        for (size_t i = lo; i < hi; i++) fmt_row(i, o);
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(fmt, t);
-    fmt(0);
-    for (std::thread &x : th) x.join();
-    for (const std::string &o : parts) fwrite(o.data(), 1, o.size(), f);
-}
-
 int write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth)
 {
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
-    FILE *f = closer.f;
-    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-    fputs("track type=wiggle_0\n", f);
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs("track type=wiggle_0\n", out.f);
     std::vector<uint64_t> sums;
     for (const uint32_t c : sorted_chromosomes(m)) {
-        fprintf(f, "variableStep chrom=%s span=%u\n", m->names[c].c_str(), bin);
+        fprintf(out.f, "variableStep chrom=%s span=%u\n", m->names[c].c_str(), bin);
         const u64 need = (m->chr_off[c + 1] - m->chr_off[c]) / bin + 1;
         sums.resize((size_t)need * 5);
         uint64_t nb = 0;
         const int rc = bsx_meth_bins(m, c, bin, min_depth, need, sums.data(), &nb);
         if (rc) return rc;
-        format_rows(f, (size_t)nb, 8, [&](size_t j, std::string &o) {
-            const uint64_t *s = &sums[j * 5];
-            if (!s[0] || !s[3]) return;  // (E == 0 with a site: d * g / ga below 2^-17, no real pile-up; no ratio to print)
-            char line[64];
-            o.append(line, (size_t)snprintf(line, sizeof(line), "%llu\t%.3f\n", (u64)j * bin + 1, (double)s[4] / (double)s[3]));
-        });
+        format_rows(out.f, (size_t)nb, 8, [&](size_t j, std::string &o) { bsx_meth_text::append_wig_line(o, j, bin, &sums[j * 5]); });
     }
-    closer.f = nullptr;
-    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-    return BSX_OK;
+    return out.finish();
 }
 
 int write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
@@ -1814,28 +1762,14 @@ int write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint3
     std::vector<uint64_t> sums(n * 5 + 1);
     const int rc = bsx_meth_regions(m, (uint32_t)n, bed.chr.data(), bed.start.data(), bed.end.data(), min_depth, sums.data());
     if (rc) return rc;
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(out_path, "w")};
-    FILE *f = closer.f;
-    if (!f) { g_bsx_err = std::string("cannot write ") + out_path; return BSX_ERR_IO; }
-    fputs("chr\tstart\tend\tname\tn_C\tmethy_C\ttotal_C\teff_CT\tratio\tCI_lower\tCI_upper\n", f);
-    const double z95 = 1.96, z95sq = 1.96 * 1.96;
-    format_rows(f, n, 64, [&](size_t i, std::string &o) {
-        const uint64_t *s = &sums[i * 5];
-        char num[256];
-        o += m->names[bed.chr[i]];
-        o.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%u\t", bed.start[i], bed.end[i]));
-        o += bed.label[i];
-        const double d = (double)s[3] / 65536.0;
-        if (!s[0] || !s[3]) { o.append(num, (size_t)snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%.2f\tNA\tNA\tNA\n", (u64)s[0], (u64)s[1], (u64)s[2], d)); return; }
-        const double ratio = (double)s[4] / (double)s[3];  // the table's interval (write_table) over the pooled effective depth
-        const double pmid = ratio + z95sq / (2 * d);
-        const double sd = z95 * pow(ratio * (1 - ratio) / d + z95sq / (4 * d * d), 0.5);
-        const double norminator = 1 + z95sq / d;
-        o.append(num, (size_t)snprintf(num, sizeof(num), "\t%llu\t%llu\t%llu\t%.2f\t%.3f\t%.3f\t%.3f\n", (u64)s[0], (u64)s[1], (u64)s[2], d, ratio, (pmid - sd) / norminator,
-                                       (pmid + sd) / norminator));
+    OutFile out(out_path);
+    if (!out.f) return out.cannot_write();
+    fputs("chr\tstart\tend\tname\tn_C\tmethy_C\ttotal_C\teff_CT\tratio\tCI_lower\tCI_upper\n", out.f);
+    format_rows(out.f, n, 64, [&](size_t i, std::string &o) {
+        bsx_meth_text::append_region_row(o, m->names[bed.chr[i]].c_str(), bed.start[i], bed.end[i], bed.label[i], &sums[i * 5]);
     });
-    closer.f = nullptr;
-    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + out_path; return BSX_ERR_IO; }
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
     if (n_written) *n_written = n;
     if (n_dropped) *n_dropped = bed.dropped;
     return BSX_OK;
@@ -1843,10 +1777,9 @@ int write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint3
 
 int write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
 {
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
-    FILE *f = closer.f;
-    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-    fputs("chr\tpos\tstrand\treads\tdiscordant\tPDR\n", f);
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs("chr\tpos\tstrand\treads\tdiscordant\tPDR\n", out.f);
     std::vector<uint32_t> pos, reads, disc;
     std::vector<uint8_t> letter;
     uint64_t total = 0;
@@ -1858,27 +1791,22 @@ int write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_row
         pos.resize(rows); reads.resize(rows); disc.resize(rows); letter.resize(rows);
         rc = bsx_meth_pdr_fetch_rows(m, pos.data(), reads.data(), disc.data());
         if (rc) return rc;
-        if (hipMemcpy(letter.data(), m->d_pdr_letter, rows, hipMemcpyDeviceToHost) != hipSuccess) return BSX_ERR_DEVICE;
+        if (hipMemcpy(letter.data(), m->d_pdr_letter.p, rows, hipMemcpyDeviceToHost) != hipSuccess) return BSX_ERR_DEVICE;
         const char *name = m->names[c].c_str();
-        format_rows(f, rows, 40, [&](size_t i, std::string &o) {
-            char num[96];
-            o += name;
-            o.append(num, (size_t)snprintf(num, sizeof(num), "\t%u\t%c\t%u\t%u\t%.3f\n", pos[i] + 1, letter[i] == 'C' ? '+' : '-', reads[i], disc[i], (double)disc[i] / (double)reads[i]));
-        });
+        format_rows(out.f, rows, 40, [&](size_t i, std::string &o) { bsx_meth_text::append_pdr_row(o, name, pos[i], letter[i], reads[i], disc[i]); });
         total += rows;
     }
-    closer.f = nullptr;
-    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
     if (n_rows) *n_rows = total;
     return BSX_OK;
 }
 
 int write_epi(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
 {
-    struct Closer { FILE *f; ~Closer() { if (f) fclose(f); } } closer{fopen(path, "w")};
-    FILE *f = closer.f;
-    if (!f) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
-    fputs(bsx_meth_epi::header().c_str(), f);
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs(bsx_meth_epi::header().c_str(), out.f);
     std::vector<uint32_t> pos, counts;
     uint64_t total = 0;
     for (const uint32_t c : sorted_chromosomes(m)) {
@@ -1890,11 +1818,11 @@ int write_epi(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_row
         rc = bsx_meth_epi_fetch_rows(m, pos.data(), counts.data());
         if (rc) return rc;
         const char *name = m->names[c].c_str();
-        format_rows(f, rows, 128, [&](size_t i, std::string &o) { bsx_meth_epi::append_row(o, name, &pos[i * 4], &counts[i * 16]); });
+        format_rows(out.f, rows, 128, [&](size_t i, std::string &o) { bsx_meth_epi::append_row(o, name, &pos[i * 4], &counts[i * 16]); });
         total += rows;
     }
-    closer.f = nullptr;
-    if (fclose(f) != 0) { g_bsx_err = std::string("cannot write ") + path; return BSX_ERR_IO; }
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
     if (n_rows) *n_rows = total;
     return BSX_OK;
 }
@@ -1906,39 +1834,21 @@ extern "C" int bsx_meth_write_epi(bsx_meth *m, const char *path, uint32_t min_re
     if (!m || !path || !min_reads || m->names.size() != m->n_chr) return BSX_ERR_ARG;
     if (n_rows) *n_rows = 0;
     if (!m->epi) { g_bsx_err = EPI_OFF; return BSX_ERR_STATE; }
-    try {
-        return write_epi(m, path, min_reads, n_rows);
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
-    }
+    return guarded(path, "writing", [&] { return write_epi(m, path, min_reads, n_rows); });
 }
 
 extern "C" int bsx_meth_write_pdr(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows)
 {
     if (!m || !path || !min_reads || m->names.size() != m->n_chr) return BSX_ERR_ARG;
     if (n_rows) *n_rows = 0;
-    if (!m->d_pdr) { g_bsx_err = "PDR is off (bsx_meth_set_pdr)"; return BSX_ERR_STATE; }
-    try {
-        return write_pdr(m, path, min_reads, n_rows);
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
-    }
+    if (!m->d_pdr.p) { g_bsx_err = PDR_OFF; return BSX_ERR_STATE; }
+    return guarded(path, "writing", [&] { return write_pdr(m, path, min_reads, n_rows); });
 }
 
 extern "C" int bsx_meth_write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth)
 {
     if (!m || !path || !bin || m->names.size() != m->n_chr) return BSX_ERR_ARG;
-    try {
-        return write_wig(m, path, bin, min_depth);
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("writing ") + path + ": " + x.what(); return BSX_ERR_IO;
-    }
+    return guarded(path, "writing", [&] { return write_wig(m, path, bin, min_depth); });
 }
 
 extern "C" int bsx_meth_write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
@@ -1946,11 +1856,5 @@ extern "C" int bsx_meth_write_regions(bsx_meth *m, const char *bed_path, const c
     if (!m || !bed_path || !out_path || m->names.size() != m->n_chr) return BSX_ERR_ARG;
     if (n_written) *n_written = 0;
     if (n_dropped) *n_dropped = 0;
-    try {
-        return write_regions(m, bed_path, out_path, min_depth, n_written, n_dropped);
-    } catch (const std::bad_alloc &) {
-        g_bsx_err = std::string("out of host memory while writing ") + out_path; return BSX_ERR_NOMEM;
-    } catch (const std::exception &x) {
-        g_bsx_err = std::string("writing ") + out_path + ": " + x.what(); return BSX_ERR_IO;
-    }
+    return guarded(out_path, "writing", [&] { return write_regions(m, bed_path, out_path, min_depth, n_written, n_dropped); });
 }
