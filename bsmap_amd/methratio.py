@@ -30,6 +30,7 @@ window when it makes a CpG call at all four, and the `--nonconv-filter`, the cyc
 and `-m` do not touch it; each row carries the epipolymorphism (Landan et al. 2012) and the methylation entropy (Xie et al. 2011) of its sixteen counts,
 for windows with at least `--epi-min-reads R` (default 1) reads."""
 import ctypes as C
+import os
 import sys
 import time
 
@@ -44,58 +45,68 @@ MBIAS_CONTEXTS = ("CG", "CHG", "CHH", "CN")
 CT_SNP_MODES = ("no-action", "correct", "skip")  # bsx_meth_set_ct_snp modes 0, 1, 2
 CONTEXT_BITS = {"CG": 1, "CHG": 2, "CHH": 4}      # bsx_meth_set_contexts
 
+_VP, _U32, _I32, _U64, _STR = C.c_void_p, C.c_uint32, C.c_int32, C.c_uint64, C.c_char_p
+# every bsx_meth_* prototype of include/bsx.h as name -> (restype, argtypes); tests/test_methratio_bind_cpu.py holds it against the header
+PROTOTYPES = {
+    "bsx_meth_create": (_I32, [_U32, _VP, _I32, _I32, C.POINTER(_VP)]),
+    "bsx_meth_create_from_fasta": (_I32, [_STR, _STR, _I32, _I32, C.POINTER(_VP)]),
+    "bsx_meth_n_chr": (_U32, [_VP]),
+    "bsx_meth_chr_name": (_STR, [_VP, _U32]),
+    "bsx_meth_destroy": (None, [_VP]),
+    "bsx_meth_set_reference": (_I32, [_VP, _U32, _VP]),
+    "bsx_meth_add": (_I32, [_VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32]),
+    "bsx_meth_add_file": (_I32, [_VP, _STR, _I32, _VP, _I32, _I32, _U32, _VP]),
+    "bsx_meth_set_cycle_trim": (_I32, [_VP, _U32, _U32]),
+    "bsx_meth_set_mbias": (_I32, [_VP, _I32]),
+    "bsx_meth_mbias_fetch": (_I32, [_VP, _VP, _VP]),
+    "bsx_meth_write_mbias": (_I32, [_VP, _STR]),
+    "bsx_meth_set_ct_snp": (_I32, [_VP, _I32]),
+    "bsx_meth_set_contexts": (_I32, [_VP, _U32]),
+    "bsx_meth_combine_cpg": (_I32, [_VP]),
+    "bsx_meth_valid_mappings": (_I32, [_VP, _VP]),
+    "bsx_meth_report_chr": (_I32, [_VP, _U32, _U32, _I32, _VP, _VP, _VP]),
+    "bsx_meth_fetch_rows": (_I32, [_VP, _VP, _VP, _VP]),
+    "bsx_meth_fetch_rows_snp": (_I32, [_VP, _VP, _VP]),
+    "bsx_meth_write_table": (_I32, [_VP, _STR, _U32, _VP, _VP, _U32, _I32, _VP, _VP]),
+    "bsx_meth_region_tile": (_U32, []),
+    "bsx_meth_regions": (_I32, [_VP, _U32, _VP, _VP, _VP, _U32, _VP]),
+    "bsx_meth_bins": (_I32, [_VP, _U32, _U32, _U32, _U64, _VP, _VP]),
+    "bsx_meth_write_regions": (_I32, [_VP, _STR, _STR, _U32, _VP, _VP]),
+    "bsx_meth_write_wig": (_I32, [_VP, _STR, _U32, _U32]),
+    "bsx_meth_set_nonconv": (_I32, [_VP, _U32]),
+    "bsx_meth_nonconv_dropped": (_I32, [_VP, _VP]),
+    "bsx_meth_set_read_stats": (_I32, [_VP, _I32]),
+    "bsx_meth_read_stats_fetch": (_I32, [_VP, _VP, _VP, _VP]),
+    "bsx_meth_write_read_stats": (_I32, [_VP, _STR]),
+    "bsx_meth_set_pdr": (_I32, [_VP, _U32]),
+    "bsx_meth_pdr_report_chr": (_I32, [_VP, _U32, _U32, _VP]),
+    "bsx_meth_pdr_fetch_rows": (_I32, [_VP, _VP, _VP, _VP]),
+    "bsx_meth_write_pdr": (_I32, [_VP, _STR, _U32, _VP]),
+    "bsx_meth_set_epi": (_I32, [_VP, _I32]),
+    "bsx_meth_n_cpg": (_I32, [_VP, _U32, _VP]),
+    "bsx_meth_epi_report_chr": (_I32, [_VP, _U32, _U32, _VP]),
+    "bsx_meth_epi_fetch_rows": (_I32, [_VP, _VP, _VP]),
+    "bsx_meth_write_epi": (_I32, [_VP, _STR, _U32, _VP]),
+}
+_path = os.fsencode  # str or os.PathLike -> the bytes of a const char *path
+
+
 def _bind():
+    """the library with PROTOTYPES applied (once)"""
     L = lib()
-    if getattr(L, "_meth_bound", False):
-        return L
-    vp, u32, i32, u64 = C.c_void_p, C.c_uint32, C.c_int32, C.c_uint64
-    L.bsx_meth_create.argtypes = [u32, vp, i32, i32, C.POINTER(vp)]
-    L.bsx_meth_destroy.argtypes = [vp]; L.bsx_meth_destroy.restype = None
-    L.bsx_meth_set_reference.argtypes = [vp, u32, C.c_char_p]
-    L.bsx_meth_add.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32]
-    L.bsx_meth_combine_cpg.argtypes = [vp]
-    L.bsx_meth_valid_mappings.argtypes = [vp, vp]
-    L.bsx_meth_report_chr.argtypes = [vp, u32, u32, i32, vp, vp, vp]
-    L.bsx_meth_fetch_rows.argtypes = [vp, vp, vp, vp]
-    L.bsx_meth_create_from_fasta.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
-    L.bsx_meth_add_file.argtypes = [vp, C.c_char_p, i32, vp, i32, i32, u32, vp]
-    L.bsx_meth_write_table.argtypes = [vp, C.c_char_p, u32, vp, vp, u32, i32, vp, vp]
-    L.bsx_meth_set_cycle_trim.argtypes = [vp, u32, u32]
-    L.bsx_meth_set_mbias.argtypes = [vp, i32]
-    L.bsx_meth_mbias_fetch.argtypes = [vp, vp, vp]
-    L.bsx_meth_write_mbias.argtypes = [vp, C.c_char_p]
-    L.bsx_meth_set_ct_snp.argtypes = [vp, i32]
-    L.bsx_meth_set_contexts.argtypes = [vp, u32]
-    L.bsx_meth_fetch_rows_snp.argtypes = [vp, vp, vp]
-    L.bsx_meth_region_tile.argtypes = []; L.bsx_meth_region_tile.restype = u32
-    L.bsx_meth_regions.argtypes = [vp, u32, vp, vp, vp, u32, vp]
-    L.bsx_meth_bins.argtypes = [vp, u32, u32, u32, u64, vp, vp]
-    L.bsx_meth_write_regions.argtypes = [vp, C.c_char_p, C.c_char_p, u32, vp, vp]
-    L.bsx_meth_write_wig.argtypes = [vp, C.c_char_p, u32, u32]
-    L.bsx_meth_set_nonconv.argtypes = [vp, u32]
-    L.bsx_meth_nonconv_dropped.argtypes = [vp, vp]
-    L.bsx_meth_set_read_stats.argtypes = [vp, i32]
-    L.bsx_meth_read_stats_fetch.argtypes = [vp, vp, vp, vp]
-    L.bsx_meth_write_read_stats.argtypes = [vp, C.c_char_p]
-    L.bsx_meth_set_pdr.argtypes = [vp, u32]
-    L.bsx_meth_pdr_report_chr.argtypes = [vp, u32, u32, vp]
-    L.bsx_meth_pdr_fetch_rows.argtypes = [vp, vp, vp, vp]
-    L.bsx_meth_write_pdr.argtypes = [vp, C.c_char_p, u32, vp]
-    L.bsx_meth_set_epi.argtypes = [vp, i32]
-    L.bsx_meth_n_cpg.argtypes = [vp, u32, vp]
-    L.bsx_meth_epi_report_chr.argtypes = [vp, u32, u32, vp]
-    L.bsx_meth_epi_fetch_rows.argtypes = [vp, vp, vp]
-    L.bsx_meth_write_epi.argtypes = [vp, C.c_char_p, u32, vp]
-    L._meth_bound = True
+    if not getattr(L, "_meth_bound", False):
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+        L._meth_bound = True
     return L
 
 
 def mbias_fetch(L, h):
     """the M-bias cells of a handle as uint64 [strand][context][cycle][unmethylated, methylated] and the count of calls beyond the last cycle"""
-    cells = np.zeros((4, 4, MBIAS_CYCLES, 2), np.uint64)
-    over = C.c_uint64()
-    _check(L.bsx_meth_mbias_fetch(h, cells.ctypes.data, C.byref(over)))
-    return cells, over.value
+    cells, over = np.zeros((4, 4, MBIAS_CYCLES, 2), np.uint64), np.zeros(1, np.uint64)
+    _check(L.bsx_meth_mbias_fetch(h, cells.ctypes.data, over.ctypes.data))
+    return cells, int(over[0])
 
 
 def read_stats_fetch(L, h):
@@ -108,11 +119,186 @@ def read_stats_fetch(L, h):
 def epi_fetch(L, h, chr, min_reads=1):
     """the epiallele rows of one sequence with at least min_reads reads: pos0 as uint32 [rows][4] (the 0-based positions of the four Cs) and counts as
     uint32 [rows][16] (by pattern: bit j set = CpG j of the window methylated)"""
-    nr = C.c_uint32()
-    _check(L.bsx_meth_epi_report_chr(h, chr, min_reads, C.byref(nr)))
-    pos0, counts = np.zeros((nr.value, 4), np.uint32), np.zeros((nr.value, 16), np.uint32)
+    nr = np.zeros(1, np.uint32)
+    _check(L.bsx_meth_epi_report_chr(h, chr, min_reads, nr.ctypes.data))
+    pos0, counts = np.zeros((nr[0], 4), np.uint32), np.zeros((nr[0], 16), np.uint32)
     _check(L.bsx_meth_epi_fetch_rows(h, pos0.ctypes.data, counts.ctypes.data))
     return pos0, counts
+
+
+class Meth:
+    """one bsx_meth handle of include/bsx.h: the pile-up counters of a reference in HBM and every call on them (the methylation side's RefSeq / Batch).
+    Methods check the return code and give numpy arrays.  `L` (the bound library) and `h` (the handle) are public: a test of the ABI's own error codes
+    calls L.bsx_meth_*(h, ..) directly.  close() destroys the handle and sets h to None; it may be called again, and every other method of a closed object
+    raises ValueError before any call into the library.  There is no __del__ (destruction sets the device and must not run at interpreter shutdown): use
+    `with` or try / finally."""
+    L = None
+    h = None
+
+    @classmethod
+    def from_fasta(cls, path, chroms=None, rm_dup=False, device=0):
+        """the sequences of a FASTA file (chroms: names to keep, default all) with their letters and names; rm_dup: with the fragment-end table of -r"""
+        m = cls()
+        m.L, h = _bind(), C.c_void_p()
+        _check(m.L.bsx_meth_create_from_fasta(_path(path), ",".join(chroms).encode() if chroms else None, 1 if rm_dup else 0, device, C.byref(h)))
+        m.h = h
+        return m
+
+    @classmethod
+    def from_lengths(cls, lens, rm_dup=False, device=0):
+        """sequences of the given lengths without names; set_reference gives each its letters"""
+        m = cls()
+        m.L, h, lens = _bind(), C.c_void_p(), np.array(lens, np.uint64)
+        _check(m.L.bsx_meth_create(len(lens), lens.ctypes.data, 1 if rm_dup else 0, device, C.byref(h)))
+        m.h = h
+        return m
+
+    def _live(self):
+        if self.h is None:
+            raise ValueError("this Meth is closed")
+        return self.h
+
+    def _call(self, name, *args):
+        """L.<name>(h, *args) with the return code checked; a closed object raises before L is touched"""
+        h = self._live()
+        return _check(getattr(self.L, name)(h, *args))
+
+    def _count(self, name, *args):
+        """the same for a call whose last argument is a uint64 to fill, which is returned"""
+        n = C.c_uint64()
+        self._call(name, *args, C.byref(n))
+        return n.value
+
+    def close(self):
+        if self.h is not None:
+            self.L.bsx_meth_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        self._live()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_reference(self, chr, seq):
+        """the upper-case letters of one sequence, as many as its length: str, bytes or a uint8 array (passed as it is, without a copy)"""
+        h = self._live()
+        seq = seq.encode() if isinstance(seq, str) else seq if isinstance(seq, bytes) else np.ascontiguousarray(seq, np.uint8)
+        _check(self.L.bsx_meth_set_reference(h, chr, seq if isinstance(seq, bytes) else seq.ctypes.data))
+
+    @property
+    def n_chr(self):
+        h = self._live()
+        return self.L.bsx_meth_n_chr(h)
+
+    def chr_name(self, c):
+        """the name a FASTA gave sequence c ("" without one)"""
+        h = self._live()
+        return self.L.bsx_meth_chr_name(h, c).decode()
+
+    # ---- settings (include/bsx.h says when each may change) ----
+    def set_mbias(self, on=True): self._call("bsx_meth_set_mbias", 1 if on else 0)
+    def set_cycle_trim(self, trim5, trim3): self._call("bsx_meth_set_cycle_trim", trim5, trim3)
+    def set_contexts(self, mask): self._call("bsx_meth_set_contexts", mask)
+    def set_nonconv(self, n): self._call("bsx_meth_set_nonconv", n)
+    def set_read_stats(self, on=True): self._call("bsx_meth_set_read_stats", 1 if on else 0)
+    def set_pdr(self, min_cpg): self._call("bsx_meth_set_pdr", min_cpg)
+    def set_epi(self, on=True): self._call("bsx_meth_set_epi", 1 if on else 0)
+
+    def set_ct_snp(self, mode):
+        """mode: 0, 1, 2 or its name in CT_SNP_MODES"""
+        self._call("bsx_meth_set_ct_snp", CT_SNP_MODES.index(mode) if isinstance(mode, str) else mode)
+
+    # ---- input ----
+    def add(self, alns, trim_fillin):
+        """alns: [(chr id, 0-based pos, strand code, insert, cut_at or -1, letters)] in input order; an empty list is no call"""
+        self._live()
+        if not alns:
+            return
+        off = np.cumsum([0] + [len(a[5]) for a in alns]).astype(np.uint64)
+        seq = np.frombuffer("".join(a[5] for a in alns).encode() + b"\0", np.uint8)
+        col = lambda k, dtype: np.array([a[k] for a in alns], dtype)
+        self.add_arrays(len(alns), col(0, np.uint32), col(1, np.int64), col(2, np.uint8), col(3, np.int32), col(4, np.int64), seq, off, trim_fillin)
+
+    def add_arrays(self, n, chr, pos, strand, insert, cut_at, seq, off, trim_fillin):
+        """the first n alignments of the arrays of bsx_meth_add (uint32, int64, uint8, int32, int64; letters as uint8 with uint64 offsets[n + 1]).  An array of
+        that type goes to the library as it is; another one is converted"""
+        self._live()
+        a = [np.ascontiguousarray(x, t) for x, t in zip((chr, pos, strand, insert, cut_at, seq, off), (np.uint32, np.int64, np.uint8, np.int32, np.int64, np.uint8, np.uint64))]
+        self._call("bsx_meth_add", n, *[x.ctypes.data for x in a], trim_fillin)
+
+    def add_file(self, path, unique=False, pair=False, trim_fillin=2):
+        """a mapping file of bsmap, *.sam / *.bam by their format and anything else as BSP; returns its lines"""
+        self._live()
+        ext = str(path)[-4:].upper()
+        return self._count("bsx_meth_add_file", _path(path), 2 if ext == ".BAM" else 1 if ext == ".SAM" else 0, None, 1 if unique else 0, 1 if pair else 0, trim_fillin)
+
+    # ---- counters ----
+    def combine_cpg(self): self._call("bsx_meth_combine_cpg")
+    def valid_mappings(self): return self._count("bsx_meth_valid_mappings")
+    def nonconv_dropped(self): return self._count("bsx_meth_nonconv_dropped")
+    def n_cpg(self, c): return self._count("bsx_meth_n_cpg", c)
+
+    # ---- reports: one sequence's rows as uint32 arrays ----
+    def report(self, c, min_depth=1, meth0=True, snp=False):
+        """(pos0, depth, meth, n_covered, sum_depth) of sequence c, with snp=True (pos0, depth, meth, rev_g, rev_ga, n_covered, sum_depth)"""
+        h, nr, cov, sd = self._live(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _check(self.L.bsx_meth_report_chr(h, c, min_depth, 1 if meth0 else 0, C.byref(nr), C.byref(cov), C.byref(sd)))
+        rows = [np.zeros(nr.value, np.uint32) for _ in range(5 if snp else 3)]
+        _check(self.L.bsx_meth_fetch_rows(h, *[x.ctypes.data for x in rows[:3]]))
+        if snp:
+            _check(self.L.bsx_meth_fetch_rows_snp(h, rows[3].ctypes.data, rows[4].ctypes.data))
+        return (*rows, cov.value, sd.value)
+
+    def pdr_report(self, c, min_reads=1):
+        """(pos0, reads, discordant) of sequence c"""
+        h, nr = self._live(), C.c_uint32()
+        _check(self.L.bsx_meth_pdr_report_chr(h, c, min_reads, C.byref(nr)))
+        rows = [np.zeros(nr.value, np.uint32) for _ in range(3)]
+        _check(self.L.bsx_meth_pdr_fetch_rows(h, *[x.ctypes.data for x in rows]))
+        return tuple(rows)
+
+    def epi_report(self, c, min_reads=1): return epi_fetch(self.L, self._live(), c, min_reads)   # (pos0 [rows][4], counts [rows][16]) of sequence c
+    def mbias(self): return mbias_fetch(self.L, self._live())
+    def read_stats(self): return read_stats_fetch(self.L, self._live())
+
+    def bins(self, c, width, min_depth=1):
+        """the sums N, M, D, E, MC of every bin of `width` positions of sequence c as uint64 [bins][5]"""
+        h, n = self._live(), C.c_uint64()
+        self.L.bsx_meth_bins(h, c, width, min_depth, 0, None, C.byref(n))   # the size query: an error code by design, with n set
+        out = np.zeros((n.value, 5), np.uint64)
+        _check(self.L.bsx_meth_bins(h, c, width, min_depth, n.value, out.ctypes.data, C.byref(n)))
+        return out[:n.value]
+
+    def regions(self, chr, start, end, min_depth=1):
+        """the same sums over the intervals [start[i], end[i]) of sequence chr[i], as uint64 [len(chr)][5]"""
+        h = self._live()
+        a = [np.ascontiguousarray(x, np.uint32) for x in (chr, start, end)]
+        if not a[0].size == a[1].size == a[2].size:
+            raise ValueError("chr, start and end differ in length")
+        out = np.zeros((a[0].size, 5), np.uint64)
+        _check(self.L.bsx_meth_regions(h, a[0].size, *[x.ctypes.data for x in a], min_depth, out.ctypes.data))
+        return out
+
+    # ---- files ----
+    def write_table(self, path, min_depth=1, meth0=True):
+        """the table of every sequence in sorted name order; returns (n_covered, sum_depth) of the summary line"""
+        h, nc, nd = self._live(), C.c_uint64(), C.c_uint64()
+        _check(self.L.bsx_meth_write_table(h, _path(path), 0, None, None, min_depth, 1 if meth0 else 0, C.byref(nc), C.byref(nd)))
+        return nc.value, nd.value
+
+    def write_mbias(self, path): self._call("bsx_meth_write_mbias", _path(path))
+    def write_read_stats(self, path): self._call("bsx_meth_write_read_stats", _path(path))
+    def write_wig(self, path, width, min_depth=1): self._call("bsx_meth_write_wig", _path(path), width, min_depth)
+    def write_pdr(self, path, min_reads=1): return self._count("bsx_meth_write_pdr", _path(path), min_reads)   # the rows written
+    def write_epi(self, path, min_reads=1): return self._count("bsx_meth_write_epi", _path(path), min_reads)   # the rows written
+
+    def write_regions(self, bed_path, out_path, min_depth=1):
+        """one pooled ratio per interval of a BED file; returns (intervals written, intervals dropped: on sequences that are not loaded)"""
+        h, nw, nd = self._live(), C.c_uint64(), C.c_uint64()
+        _check(self.L.bsx_meth_write_regions(h, _path(bed_path), _path(out_path), min_depth, C.byref(nw), C.byref(nd)))
+        return nw.value, nd.value
 
 
 def load_reference(path, chroms):
@@ -164,70 +350,59 @@ def run(reffile, infiles, outfile, chroms=None, unique=False, pair=False, meth0=
         if not quiet:
             sys.stderr.write("@ %s: %s\n" % (time.asctime(), txt))
 
-    L = _bind()
     disp("reading reference %s ..." % reffile)
-    h = C.c_void_p()
-    _check(L.bsx_meth_create_from_fasta(reffile.encode(), ",".join(chroms).encode() if chroms else None, 1 if rm_dup else 0, device, C.byref(h)))
-    try:
+    with Meth.from_fasta(reffile, chroms, rm_dup, device) as m:
         if mbias:
-            _check(L.bsx_meth_set_mbias(h, 1))
+            m.set_mbias()
         if trim5 or trim3:
-            _check(L.bsx_meth_set_cycle_trim(h, trim5, trim3))
+            m.set_cycle_trim(trim5, trim3)
         if ct_snp != "no-action":
-            _check(L.bsx_meth_set_ct_snp(h, CT_SNP_MODES.index(ct_snp)))
+            m.set_ct_snp(ct_snp)
         if context is not None:
-            _check(L.bsx_meth_set_contexts(h, sum(CONTEXT_BITS[x] for x in set(context))))
+            m.set_contexts(sum(CONTEXT_BITS[x] for x in set(context)))
         if nonconv_filter:
-            _check(L.bsx_meth_set_nonconv(h, nonconv_filter))
+            m.set_nonconv(nonconv_filter)
         if read_stats is not None:
-            _check(L.bsx_meth_set_read_stats(h, 1))
+            m.set_read_stats()
         if pdr is not None:
-            _check(L.bsx_meth_set_pdr(h, pdr_min_cpg))
+            m.set_pdr(pdr_min_cpg)
         if epi is not None:
-            _check(L.bsx_meth_set_epi(h, 1))
+            m.set_epi()
         for infile in infiles:
             disp("reading %s ..." % infile)
-            ext = infile[-4:].upper()
-            nl = C.c_uint64()
-            _check(L.bsx_meth_add_file(h, infile.encode(), 2 if ext == ".BAM" else 1 if ext == ".SAM" else 0, None, 1 if unique else 0, 1 if pair else 0, max(0, trim_fillin), C.byref(nl)))
+            m.add_file(infile, unique, pair, max(0, trim_fillin))
         if mbias:
             disp("writing %s ..." % mbias)
-            _check(L.bsx_meth_write_mbias(h, mbias.encode()))
+            m.write_mbias(mbias)
         if nonconv_filter:
-            ndropped = C.c_uint64()
-            _check(L.bsx_meth_nonconv_dropped(h, C.byref(ndropped)))
-            disp("%d reads with %d or more methylated non-CpG calls dropped" % (ndropped.value, nonconv_filter))
+            disp("%d reads with %d or more methylated non-CpG calls dropped" % (m.nonconv_dropped(), nonconv_filter))
         if read_stats is not None:
             disp("writing %s ..." % read_stats)
-            _check(L.bsx_meth_write_read_stats(h, read_stats.encode()))
+            m.write_read_stats(read_stats)
         if combine_CpG:
             disp("combining CpG methylation from both strands ...")
-            _check(L.bsx_meth_combine_cpg(h))
+            m.combine_cpg()
         disp("writing %s ..." % outfile)
-        nc, nd, nmap = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        _check(L.bsx_meth_write_table(h, outfile.encode(), 0, None, None, min_depth, 1 if meth0 else 0, C.byref(nc), C.byref(nd)))
-        _check(L.bsx_meth_valid_mappings(h, C.byref(nmap)))
+        nc, nd = m.write_table(outfile, min_depth, meth0)
+        nmap = m.valid_mappings()
         if pdr is not None:
             disp("writing %s ..." % pdr)
-            _check(L.bsx_meth_write_pdr(h, pdr.encode(), pdr_min_reads, None))
+            m.write_pdr(pdr, pdr_min_reads)
         if epi is not None:
             disp("writing %s ..." % epi)
-            _check(L.bsx_meth_write_epi(h, epi.encode(), epi_min_reads, None))
+            m.write_epi(epi, epi_min_reads)
         if wig is not None:
             disp("writing %s ..." % wig)
-            _check(L.bsx_meth_write_wig(h, wig.encode(), wig_bin, min_depth))
+            m.write_wig(wig, wig_bin, min_depth)
         if regions is not None:
             disp("writing %s ..." % region_out)
-            nw, ndrop = C.c_uint64(), C.c_uint64()
-            _check(L.bsx_meth_write_regions(h, regions.encode(), region_out.encode(), min_depth, C.byref(nw), C.byref(ndrop)))
-            disp("%d intervals of %s written, %d on sequences that are not loaded dropped" % (nw.value, regions, ndrop.value))
+            nw, ndrop = m.write_regions(regions, region_out, min_depth)
+            disp("%d intervals of %s written, %d on sequences that are not loaded dropped" % (nw, regions, ndrop))
         disp("done.")
         # (with nothing covered the reference dies here on a division by zero; that is reported instead)
-        if nc.value == 0:
-            return "total %d valid mappings, 0 covered cytosines.\n" % nmap.value
-        return "total %d valid mappings, %d covered cytosines, average coverage: %.2f fold.\n" % (nmap.value, nc.value, float(nd.value) / nc.value)
-    finally:
-        L.bsx_meth_destroy(h)
+        if nc == 0:
+            return "total %d valid mappings, 0 covered cytosines.\n" % nmap
+        return "total %d valid mappings, %d covered cytosines, average coverage: %.2f fold.\n" % (nmap, nc, float(nd) / nc)
 
 
 def build_parser():

@@ -9,6 +9,7 @@ import os
 import pytest
 
 import golden_util as G
+import meth_util as U
 
 pytestmark = pytest.mark.gpu
 GOLD = json.load(gzip.open(os.path.join(G.GOLDEN, "methratio.json.gz"), "rt"))
@@ -68,20 +69,13 @@ def test_methratio_matches_reference_script(gold, case, i, request, capsys):
 def test_methratio_low_level_calls_agree_with_the_file_path(files):
     """bsx_meth_add with explicit arrays in many small batches (duplicate removal is defined by input order across calls)
     gives the same rows as the file-level call"""
-    import ctypes as C
     import numpy as np
-    from bsmap_amd import methratio, _check
+    from bsmap_amd import methratio
     fa, paths, d = files
     out = str(d / "file.txt")
     methratio.run(fa, paths["pe"], out, rm_dup=True, meth0=True)
-    L = methratio._bind()
     ref = methratio.load_reference(fa, [])
     names = list(ref)
-    lens = np.array([len(ref[n]) for n in names], np.uint64)
-    h = C.c_void_p()
-    _check(L.bsx_meth_create(len(names), lens.ctypes.data, 1, 0, C.byref(h)))
-    for i, n in enumerate(names):
-        _check(L.bsx_meth_set_reference(h, i, ref[n].encode()))
     st = {"++": 0, "-+": 1, "+-": 2, "--": 3}
     rows = []
     for p_ in paths["pe"]:
@@ -90,21 +84,16 @@ def test_methratio_low_level_calls_agree_with_the_file_path(files):
             if col[3][:2] in ("NM", "QC"):
                 continue
             rows.append((names.index(col[4]), int(col[5]) - 1, st[col[6]], int(col[7]), col[1]))
-    for b0 in range(0, len(rows), 53):
-        part = rows[b0:b0 + 53]
-        off = np.cumsum([0] + [len(r[4]) for r in part]).astype(np.uint64)
-        seq = np.frombuffer(("".join(r[4] for r in part)).encode() + b"\0", np.uint8)
-        arr = [np.array([r[0] for r in part], np.uint32), np.array([r[1] for r in part], np.int64), np.array([r[2] for r in part], np.uint8),
-               np.array([r[3] for r in part], np.int32), np.full(len(part), -1, np.int64), seq, off]
-        _check(L.bsx_meth_add(h, len(part), *[a.ctypes.data for a in arr], 2))
-    got = []
-    for i, n in enumerate(names):
-        nr = C.c_uint32()
-        _check(L.bsx_meth_report_chr(h, i, 1, 1, C.byref(nr), None, None))
-        pos, dep, met = (np.zeros(nr.value, np.uint32) for _ in range(3))
-        _check(L.bsx_meth_fetch_rows(h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-        got += [(n, int(a) + 1, int(b), int(c)) for a, b, c in zip(pos, dep, met)]
-    L.bsx_meth_destroy(h)
+    with methratio.Meth.from_lengths([len(ref[n]) for n in names], rm_dup=True) as m:
+        for i, n in enumerate(names):
+            m.set_reference(i, ref[n])
+        for b0 in range(0, len(rows), 53):
+            part = rows[b0:b0 + 53]
+            off = np.cumsum([0] + [len(r[4]) for r in part]).astype(np.uint64)
+            seq = np.frombuffer(("".join(r[4] for r in part)).encode() + b"\0", np.uint8)
+            m.add_arrays(len(part), np.array([r[0] for r in part], np.uint32), np.array([r[1] for r in part], np.int64), np.array([r[2] for r in part], np.uint8),
+                         np.array([r[3] for r in part], np.int32), np.full(len(part), -1, np.int64), seq, off, 2)
+        got = [(names[c], pos + 1, dep, met) for c, pos, dep, met in U.table_rows(m, len(names))[0]]
     exp = [(f[0], int(f[1]), int(f[5]), int(f[6])) for f in (l.split("\t") for l in open(out).read().split("\n")[1:] if l)]
     assert sorted(got) == sorted(exp) and len(got) > 1000
 

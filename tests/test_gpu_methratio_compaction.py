@@ -13,13 +13,14 @@ opposite-strand calls of the C/T-SNP mode."""
 import ctypes as C
 import functools
 
-import numpy as np
 import pytest
+
+from bsmap_amd import _check
 
 import ctsnp_model as M
 import epi_model as E
 import readlevel_model as RL
-from test_gpu_methratio_epi import Handle, write_fasta
+import meth_util as U
 
 NAMES = ["a", "b", "c"]
 REFS = ["ACGCGCGCGT", "CG" * 2055 + "A", "C"]
@@ -98,40 +99,36 @@ def test_expected_sets_are_the_ones_named():
 
 @pytest.fixture(scope="module")
 def fasta(tmp_path_factory):
-    return write_fasta(tmp_path_factory.mktemp("compaction") / "three.fa", NAMES, REFS)
+    return U.write_fasta(tmp_path_factory.mktemp("compaction") / "three.fa", NAMES, REFS)
+
+
+def row_counts(h, report, *args):
+    """the number of rows every sequence's report call sets, with the counts it fills preset to a value no report here gives: an empty report has to write its 0"""
+    per_chr = []
+    for c in range(len(REFS)):
+        out = [C.c_uint32(0xFFFFFFFF)] + [C.c_uint64(0xFFFFFFFFFFFFFFFF) for _ in range(2 if report == "bsx_meth_report_chr" else 0)]
+        _check(getattr(h.L, report)(h.h, c, *args, *[C.byref(x) for x in out]))
+        assert all(x.value < 0xFFFFFFFF for x in out)
+        per_chr.append(out[0].value)
+    return per_chr
 
 
 def table_rows(h, min_depth, meth0, snp):
-    """([(chr id, pos, depth, meth, rev_g, rev_ga)], n_covered, sum_depth) over all sequences; rev_g = rev_ga = 0 with the mode off"""
-    got, nc, nd, per_chr = [], 0, 0, []
-    for c in range(len(REFS)):
-        nr, cov, sd = C.c_uint32(12345), C.c_uint64(12345), C.c_uint64(12345)
-        h.check(h.L.bsx_meth_report_chr(h.h, c, min_depth, 1 if meth0 else 0, C.byref(nr), C.byref(cov), C.byref(sd)))
-        pos, dep, met, g, ga = (np.zeros(nr.value, np.uint32) for _ in range(5))
-        h.check(h.L.bsx_meth_fetch_rows(h.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-        if snp:
-            h.check(h.L.bsx_meth_fetch_rows_snp(h.h, g.ctypes.data, ga.ctypes.data))
-        got += [(c,) + t for t in zip(pos.tolist(), dep.tolist(), met.tolist(), g.tolist(), ga.tolist())]
-        nc, nd = nc + cov.value, nd + sd.value
-        per_chr.append(nr.value)
+    """([(chr id, pos, depth, meth, rev_g, rev_ga)], n_covered, sum_depth, rows per sequence) over all sequences; rev_g = rev_ga = 0 with the mode off"""
+    got, nc, nd = U.table_rows(h, len(REFS), min_depth, meth0, bool(snp), pad=True)
+    per_chr = row_counts(h, "bsx_meth_report_chr", min_depth, 1 if meth0 else 0)
+    assert per_chr == [sum(1 for r in got if r[0] == c) for c in range(len(REFS))]
     return got, nc, nd, per_chr
 
 
 def table_text(h, path, min_depth, meth0):
-    nc, nd = C.c_uint64(), C.c_uint64()
-    h.check(h.L.bsx_meth_write_table(h.h, str(path).encode(), 0, None, None, min_depth, 1 if meth0 else 0, C.byref(nc), C.byref(nd)))
-    return open(path).read(), nc.value, nd.value
+    nc, nd = h.write_table(path, min_depth, meth0)
+    return open(path).read(), nc, nd
 
 
 def pdr_rows(h, min_reads):
-    got, per_chr = [], []
-    for c in range(len(REFS)):
-        nr = C.c_uint32(12345)
-        h.check(h.L.bsx_meth_pdr_report_chr(h.h, c, min_reads, C.byref(nr)))
-        pos, reads, disc = (np.zeros(nr.value, np.uint32) for _ in range(3))
-        h.check(h.L.bsx_meth_pdr_fetch_rows(h.h, pos.ctypes.data, reads.ctypes.data, disc.ctypes.data))
-        got += [(c,) + t for t in zip(pos.tolist(), reads.tolist(), disc.tolist())]
-        per_chr.append(nr.value)
+    got, per_chr = U.pdr_rows(h, len(REFS), min_reads), row_counts(h, "bsx_meth_pdr_report_chr", min_reads)
+    assert per_chr == [sum(1 for r in got if r[0] == c) for c in range(len(REFS))]
     return got, per_chr
 
 
@@ -140,10 +137,10 @@ def pdr_rows(h, min_reads):
 def test_reports_equal_the_models(fasta, tmp_path, kind):
     X = expected(kind)
     for mode in (0, 1):   # the table without and with its two extra columns
-        with Handle(fasta, epi=False, snp=mode) as h:
+        with U.open_meth(fasta, snp=mode) as h:
             h.add(X["alns"], 0)
             if mode:
-                h.cpg()
+                h.combine_cpg()
             for min_depth in (1, 2):
                 for meth0 in (True, False):
                     want, nc, nd = X["table", mode, min_depth, meth0]
@@ -154,11 +151,11 @@ def test_reports_equal_the_models(fasta, tmp_path, kind):
             if mode == 0:
                 got, _, _, per_chr = table_rows(h, NEVER, True, 0)
                 assert got == [(c, i, dd, m, 0, 0) for c, i, dd, m, _, _ in X["table", 0, NEVER, True][0]] and per_chr[0] == 0 and per_chr[2] == 0
-    with Handle(fasta, min_cpg=4) as h:   # PDR and the epiallele tally
+    with U.open_meth(fasta, min_cpg=4, epi=True) as h:   # PDR and the epiallele tally
         h.add(X["alns"], 0)
         for min_reads in (1, 2, NEVER):
             got, per_chr = pdr_rows(h, min_reads)
             assert got == X["pdr", min_reads] and per_chr[2] == 0 and (min_reads == 1 or per_chr[0] == 0)
-            assert h.epi_rows(len(REFS), min_reads) == X["epi", min_reads]
-        assert len(pdr_rows(h, 1)[0]) > 0 and len(h.epi_rows(len(REFS), 1)) == len(X["epi", 1]) > 0
-        assert h.n_cpg(len(REFS)) == [4, 2055, 0] and h.epi_rows(len(REFS), NEVER) == []
+            assert U.epi_rows(h, len(REFS), min_reads) == X["epi", min_reads]
+        assert len(pdr_rows(h, 1)[0]) > 0 and len(U.epi_rows(h, len(REFS), 1)) == len(X["epi", 1]) > 0
+        assert [h.n_cpg(c) for c in range(len(REFS))] == [4, 2055, 0] and U.epi_rows(h, len(REFS), NEVER) == []

@@ -3,7 +3,6 @@ against the pure-Python model of ctsnp_model.py, which never looks at the librar
 
 The v2.6 script the project mirrors has neither option, so there is no reference table for them: the model is the yardstick, and test 9
 ties the corrected table back to the pinned v2.6 tables where the two must agree."""
-import ctypes as C
 import gzip
 import json
 import os
@@ -13,77 +12,17 @@ import pytest
 
 import ctsnp_model as M
 import golden_util as G
+import meth_util as U
 
 pytestmark = pytest.mark.gpu
 STRANDS = M.STRANDS
 BSX_ERR_ARG, BSX_ERR_STATE = -1, -5
 
 
-# ---- the library through its C ABI -------------------------------------------------------------------------------------
-class Handle:
-    def __init__(self, fa, rm_dup=False, mode=0, mbias=False, trim=None):
-        from bsmap_amd import methratio, _check
-        self.M, self.check, self.L = methratio, _check, methratio._bind()
-        self.h = C.c_void_p()
-        _check(self.L.bsx_meth_create_from_fasta(fa.encode(), None, 1 if rm_dup else 0, 0, C.byref(self.h)))
-        if mode:
-            _check(self.L.bsx_meth_set_ct_snp(self.h, mode))
-        if mbias:
-            _check(self.L.bsx_meth_set_mbias(self.h, 1))
-        if trim:
-            _check(self.L.bsx_meth_set_cycle_trim(self.h, *trim))
-
-    def close(self):
-        self.L.bsx_meth_destroy(self.h)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def add(self, alns, trim_fillin):
-        if not alns:
-            return
-        off = np.cumsum([0] + [len(a[5]) for a in alns]).astype(np.uint64)
-        seq = np.frombuffer("".join(a[5] for a in alns).encode() + b"\0", np.uint8)
-        arr = [np.array([a[0] for a in alns], np.uint32), np.array([a[1] for a in alns], np.int64), np.array([a[2] for a in alns], np.uint8),
-               np.array([a[3] for a in alns], np.int32), np.array([a[4] for a in alns], np.int64), seq, off]
-        self.check(self.L.bsx_meth_add(self.h, len(alns), *[a.ctypes.data for a in arr], trim_fillin))
-
-    def mode(self, mode):
-        self.check(self.L.bsx_meth_set_ct_snp(self.h, mode))
-
-    def contexts(self, mask):
-        self.check(self.L.bsx_meth_set_contexts(self.h, mask))
-
-    def cpg(self):
-        self.check(self.L.bsx_meth_combine_cpg(self.h))
-
-    def rows(self, n_chr, min_depth=1, meth0=1, snp=True):
-        """[(chr id, pos, dd, m, g, ga)] (g = ga = 0 with snp=False: the mode is off), n_covered, sum_depth"""
-        got, nc, nd = [], 0, 0
-        for c in range(n_chr):
-            nr, cov, sd = C.c_uint32(), C.c_uint64(), C.c_uint64()
-            self.check(self.L.bsx_meth_report_chr(self.h, c, min_depth, meth0, C.byref(nr), C.byref(cov), C.byref(sd)))
-            pos, dep, met, g, ga = (np.zeros(nr.value, np.uint32) for _ in range(5))
-            self.check(self.L.bsx_meth_fetch_rows(self.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-            if snp:
-                self.check(self.L.bsx_meth_fetch_rows_snp(self.h, g.ctypes.data, ga.ctypes.data))
-            got += [(c,) + t for t in zip(pos.tolist(), dep.tolist(), met.tolist(), g.tolist(), ga.tolist())]
-            nc += cov.value
-            nd += sd.value
-        return got, nc, nd
-
-    def nmap(self):
-        n = C.c_uint64()
-        self.check(self.L.bsx_meth_valid_mappings(self.h, C.byref(n)))
-        return n.value
-
-    def table(self, path, min_depth=1, meth0=1):
-        nc, nd = C.c_uint64(), C.c_uint64()
-        self.check(self.L.bsx_meth_write_table(self.h, str(path).encode(), 0, None, None, min_depth, meth0, C.byref(nc), C.byref(nd)))
-        return open(path, "rb").read().decode(), nc.value, nd.value
+# ---- the library through bsmap_amd.methratio.Meth ---------------------------------------------------------------------------
+def rows(h, n_chr, min_depth=1, meth0=1, snp=True):
+    """[(chr id, pos, dd, m, g, ga)] (g = ga = 0 with snp=False: the mode is off), n_covered, sum_depth"""
+    return U.table_rows(h, n_chr, min_depth, meth0, snp, pad=True)
 
 
 # ---- the edge set ------------------------------------------------------------------------------------------------------------
@@ -220,18 +159,18 @@ def test_edge_set_covers_what_it_claims(edges):
 @pytest.mark.parametrize("trim_fillin", [0, 2, 5])
 def test_counter_parity(edges, trim_fillin, rm_dup, mode):
     K = edges.pile(trim_fillin, bool(rm_dup))
-    with Handle(edges.fa, rm_dup, mode) as h:
+    with U.open_meth(edges.fa, rm_dup, mode) as h:
         h.add(edges.alns, trim_fillin)
-        assert h.rows(3) == M.rows(K, 1, True, mode)
-        assert h.nmap() == K.nmap
+        assert rows(h, 3) == M.rows(K, 1, True, mode)
+        assert h.valid_mappings() == K.nmap
     # with the M-bias twin: the same rows, and the tally of a handle that has the mode off
-    with Handle(edges.fa, rm_dup, mode, mbias=True) as h, Handle(edges.fa, rm_dup, 0, mbias=True) as plain:
+    with U.open_meth(edges.fa, rm_dup, mode, mbias=True) as h, U.open_meth(edges.fa, rm_dup, 0, mbias=True) as plain:
         h.add(edges.alns, trim_fillin)
         plain.add(edges.alns, trim_fillin)
-        assert h.rows(3) == M.rows(K, 1, True, mode) and h.nmap() == K.nmap
-        (cells, over), (cells0, over0) = h.M.mbias_fetch(h.L, h.h), plain.M.mbias_fetch(plain.L, plain.h)
+        assert rows(h, 3) == M.rows(K, 1, True, mode) and h.valid_mappings() == K.nmap
+        (cells, over), (cells0, over0) = h.mbias(), plain.mbias()
         assert over == over0 == 0 and cells.sum() > 0 and np.array_equal(cells, cells0)
-        assert [r[:4] for r in plain.rows(3, snp=False)[0]] == [r[:4] for r in M.rows(K, 1, True, 0)[0]]
+        assert [r[:4] for r in rows(plain, 3, snp=False)[0]] == [r[:4] for r in M.rows(K, 1, True, 0)[0]]
 
 
 # ---- 2. table bytes ------------------------------------------------------------------------------------------------------------------
@@ -241,27 +180,27 @@ def test_counter_parity(edges, trim_fillin, rm_dup, mode):
 @pytest.mark.parametrize("mode", [1, 2])
 def test_table_bytes(edges, mode, meth0, min_depth, cpg):
     K = edges.pile(2, False, cpg=bool(cpg))
-    with Handle(edges.fa, 0, mode) as h:
+    with U.open_meth(edges.fa, 0, mode) as h:
         h.add(edges.alns, 2)
         if cpg:
-            h.cpg()
-        got = h.table(edges.dir / "t.txt", min_depth, meth0)
+            h.combine_cpg()
+        got = U.written_table(h, edges.dir / "t.txt", min_depth, meth0)
     want = M.table(edges.names, K, min_depth, bool(meth0), mode)
     assert got[1:] == want[1:] and got[0] == want[0]
     assert got[0].count("\n") > (20 if meth0 else 5)
 
 
 def test_two_tables_from_one_pileup(edges):
-    with Handle(edges.fa, 0, 1) as h:
+    with U.open_meth(edges.fa, 0, 1) as h:
         h.add(edges.alns, 2)
-        t1 = h.table(edges.dir / "m1.txt")
-        h.mode(2)
-        t2 = h.table(edges.dir / "m2.txt")
-        h.mode(1)
-        assert h.table(edges.dir / "m1b.txt") == t1
-    with Handle(edges.fa, 0, 2) as h:
+        t1 = U.written_table(h, edges.dir / "m1.txt")
+        h.set_ct_snp(2)
+        t2 = U.written_table(h, edges.dir / "m2.txt")
+        h.set_ct_snp(1)
+        assert U.written_table(h, edges.dir / "m1b.txt") == t1
+    with U.open_meth(edges.fa, 0, 2) as h:
         h.add(edges.alns, 2)
-        fresh = h.table(edges.dir / "m2f.txt")
+        fresh = U.written_table(h, edges.dir / "m2f.txt")
     assert t2 == fresh == M.table(edges.names, edges.pile(2, False), 1, True, 2) and t1 != t2
     assert t1 == M.table(edges.names, edges.pile(2, False), 1, True, 1)
 
@@ -283,11 +222,11 @@ def test_cpg_fold_at_a_chromosome_boundary(tmp_path):
     assert (K.depth[1][0], K.meth[1][0], K.rev_g[1][0], K.rev_ga[1][0]) == (1, 1, 2, 3)
     F = M.combine_cpg(K)
     assert F.depth[0][3] == K.depth[0][3] + K.depth[0][4] > K.depth[0][3] and F.rev_ga[0][3] == K.rev_ga[0][3] + K.rev_ga[0][4] > K.rev_ga[0][3]
-    with Handle(fa, 0, 1) as h:
+    with U.open_meth(fa, 0, 1) as h:
         h.add(alns, 0)
-        assert h.rows(2) == M.rows(K, 1, True, 1)
-        h.cpg()
-        got = h.rows(2)
+        assert rows(h, 2) == M.rows(K, 1, True, 1)
+        h.combine_cpg()
+        got = rows(h, 2)
     assert got == M.rows(F, 1, True, 1)
     assert (0, 8, 1, 1, 1, 2) in got[0] and (1, 0, 1, 1, 2, 3) in got[0]
 
@@ -310,13 +249,13 @@ def test_contention(tmp_path):
     assert any(m == 1 for _, _, dd, m, g, ga in want) and any(m == 0 for _, _, dd, m, g, ga in want)
     n = 1 << 16
     for split in ((2 * n,), (1, 60_001, 2 * n - 60_002)):
-        with Handle(fa, 0, 1) as h:
+        with U.open_meth(fa, 0, 1) as h:
             at = 0
             for part in split:  # the two alignments alternate through the whole input
                 h.add([pair[(at + i) & 1] for i in range(part)], 2)
                 at += part
-            got, got_nc, got_nd = h.rows(1)
-            assert h.nmap() == 2 * n
+            got, got_nc, got_nd = rows(h, 1)
+            assert h.valid_mappings() == 2 * n
         assert got == [(c, i, dd * n, m * n, g * n, ga * n) for c, i, dd, m, g, ga in want] and (got_nc, got_nd) == (nc, nd * n)
         assert max(g for *_, g, ga in got) == n > 65535 and max(ga for *_, ga in got) == n
 
@@ -325,12 +264,12 @@ def test_contention(tmp_path):
 @pytest.mark.parametrize("trim5,trim3", [(3, 0), (0, 4), (5, 5), (200, 0)])
 def test_cycle_trimming(edges, trim5, trim3):
     K = edges.pile(2, True, trim5, trim3)
-    with Handle(edges.fa, 1, 1, trim=(trim5, trim3)) as h:
+    with U.open_meth(edges.fa, 1, 1, trim=(trim5, trim3)) as h:
         h.add(edges.alns, 2)
-        got = h.rows(3)
+        got = rows(h, 3)
         assert got == M.rows(K, 1, True, 1)
-        assert h.nmap() == K.nmap == edges.pile(2, True).nmap
-        table = h.table(edges.dir / "trim.txt")
+        assert h.valid_mappings() == K.nmap == edges.pile(2, True).nmap
+        table = U.written_table(h, edges.dir / "trim.txt")
     if (trim5, trim3) == (200, 0):
         assert got == ([], 0, 0) and table == (M.HEADER12, 0, 0) and sum(map(sum, K.rev_ga)) == 0
     else:
@@ -341,9 +280,9 @@ def test_cycle_trimming(edges, trim5, trim3):
 @pytest.mark.parametrize("mode", [0, 1])
 def test_context_filter(edges, mode):
     K = edges.pile(2, False)
-    with Handle(edges.fa, 0, mode) as h:
+    with U.open_meth(edges.fa, 0, mode) as h:
         h.add(edges.alns, 2)
-        free = h.table(edges.dir / "free.txt")
+        free = U.written_table(h, edges.dir / "free.txt")
         assert free == M.table(edges.names, K, 1, True, mode)
         lines = free[0].split("\n")[1:-1]
         cls = []   # the class of every unfiltered row
@@ -355,23 +294,23 @@ def test_context_filter(edges, mode):
             rr, nc, nd = M.rows(K, *a)
             return (rr if mode else [r[:4] + (0, 0) for r in rr]), nc, nd
         for mask in range(0, 16):
-            h.contexts(mask)
-            assert h.rows(3, snp=bool(mode)) == model_rows(1, True, mode, mask), mask
-            got = h.table(edges.dir / "masked.txt")
+            h.set_contexts(mask)
+            assert rows(h, 3, snp=bool(mode)) == model_rows(1, True, mode, mask), mask
+            got = U.written_table(h, edges.dir / "masked.txt")
             assert got == M.table(edges.names, K, 1, True, mode, mask), mask
             if mask in (0, 15):
                 assert got == free
             else:  # exactly the unfiltered rows of the chosen classes, in their order
                 assert got[0].split("\n")[1:-1] == [l for l, x in zip(lines, cls) if (mask >> x) & 1] and 0 < got[1] < free[1], mask
-        h.contexts(3)
-        assert h.rows(3, 3, 0, snp=bool(mode)) == model_rows(3, False, mode, 3)
+        h.set_contexts(3)
+        assert rows(h, 3, 3, 0, snp=bool(mode)) == model_rows(3, False, mode, 3)
 
 
 # ---- 7. state rules ---------------------------------------------------------------------------------------------------------------------------------
 def test_state_rules(edges):
     g, ga = np.zeros(4096, np.uint32), np.zeros(4096, np.uint32)
     K = edges.pile(2, False)
-    with Handle(edges.fa) as h:
+    with U.open_meth(edges.fa) as h:
         L = h.L
         fetch = lambda: L.bsx_meth_fetch_rows_snp(h.h, g.ctypes.data, ga.ctypes.data)
         assert fetch() == BSX_ERR_STATE
@@ -382,13 +321,13 @@ def test_state_rules(edges):
         h.add(edges.alns, 2)
         assert L.bsx_meth_set_ct_snp(h.h, 1) == BSX_ERR_STATE and L.bsx_meth_set_ct_snp(h.h, 2) == BSX_ERR_STATE   # 0 -> 1 after an add
         assert L.bsx_meth_set_ct_snp(h.h, 0) == 0
-        plain = h.table(edges.dir / "state.txt")                                  # ... then add: the plain table
+        plain = U.written_table(h, edges.dir / "state.txt")                                  # ... then add: the plain table
         assert plain == M.table(edges.names, K, 1, True, 0) and plain[0].startswith(M.HEADER9)
-    with Handle(edges.fa, 0, 1) as h:
+    with U.open_meth(edges.fa, 0, 1) as h:
         h.add(edges.alns[:50], 2)
         assert h.L.bsx_meth_set_ct_snp(h.h, 0) == BSX_ERR_STATE                   # 1 -> 0 after an add
         assert h.L.bsx_meth_set_ct_snp(h.h, 2) == 0 and h.L.bsx_meth_set_ct_snp(h.h, 3) == BSX_ERR_ARG   # 1 -> 2 after an add
-        assert h.rows(3) == M.rows(M.pileup(edges.refs, edges.alns[:50], 2), 1, True, 2)
+        assert rows(h, 3) == M.rows(M.pileup(edges.refs, edges.alns[:50], 2), 1, True, 2)
 
 
 # ---- 8. command line -------------------------------------------------------------------------------------------------------------------------------------

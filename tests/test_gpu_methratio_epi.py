@@ -7,9 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from bsmap_amd import _check
+from bsmap_amd.methratio import Meth
+
 import epi_model as E
+import meth_util as U
 import readlevel_model as RL
-from test_gpu_methratio_readlevel import Handle as ReadLevelHandle
 from test_methratio_epi_cpu import CELLS_N0, CELLS_N3, HEADER, TEXT_N0, TEXT_N3, pat
 from test_methratio_readlevel_cpu import ALNS as EX_ALNS, REF as EX_REF
 
@@ -18,41 +21,18 @@ STRANDS = RL.STRANDS
 BSX_ERR_ARG, BSX_ERR_STATE = -1, -5
 
 
-class Handle(ReadLevelHandle):
-    """the handle of test_gpu_methratio_readlevel.py with the epiallele tally on (epi=False: off), histogram and PDR off unless asked for"""
-
-    def __init__(self, fa, epi=True, stats=False, min_cpg=0, **kw):
-        super().__init__(fa, stats=stats, min_cpg=min_cpg, **kw)
-        if epi:
-            self.check(self.L.bsx_meth_set_epi(self.h, 1))
-
-    def n_cpg(self, n_chr):
-        out = []
-        for c in range(n_chr):
-            n = C.c_uint64()
-            self.check(self.L.bsx_meth_n_cpg(self.h, c, C.byref(n)))
-            out.append(n.value)
-        return out
-
-    def epi_rows(self, n_chr, min_reads=1):
-        """[(chr id, (four 0-based C positions), [16 counts])], the form of epi_model.epi_rows"""
-        got = []
-        for c in range(n_chr):
-            pos, counts = self.M.epi_fetch(self.L, self.h, c, min_reads)
-            got += [(c, tuple(p), n) for p, n in zip(pos.tolist(), counts.tolist())]
-        return got
-
-    def write_epi(self, path, min_reads=1):
-        n = C.c_uint64()
-        self.check(self.L.bsx_meth_write_epi(self.h, str(path).encode(), min_reads, C.byref(n)))
-        return open(path, "rb").read().decode(), n.value
+def handle(fa, epi=True, stats=False, min_cpg=0, **kw):
+    """the epiallele tally on (epi=False: off), histogram and PDR off unless asked for; kw: rm_dup, snp, mbias, trim, nonconv"""
+    return U.open_meth(fa, epi=epi, stats=stats, min_cpg=min_cpg, **kw)
 
 
-def write_fasta(path, names, refs):
-    with open(path, "w") as f:
-        for n, s in zip(names, refs):
-            f.write(">%s some text\n%s" % (n, "".join(s[i:i + 50] + "\n" for i in range(0, len(s), 50))))
-    return str(path)
+def n_cpg(h, n_chr):
+    return [h.n_cpg(c) for c in range(n_chr)]
+
+
+def written_epi(h, path, min_reads=1):
+    n = h.write_epi(path, min_reads)
+    return U.read_text(path), n
 
 
 def make_read(rng, ref, pos, L, st, keep=None, x_rate=0.03):
@@ -71,24 +51,24 @@ def make_read(rng, ref, pos, L, st, keep=None, x_rate=0.03):
 # ---- the worked example ------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def example_fa(tmp_path_factory):
-    return write_fasta(tmp_path_factory.mktemp("epi_example") / "one.fa", ["one"], [EX_REF])
+    return U.write_fasta(tmp_path_factory.mktemp("epi_example") / "one.fa", ["one"], [EX_REF])
 
 
 @pytest.mark.parametrize("nonconv", [3, 0])
 def test_worked_example(example_fa, tmp_path, nonconv):
     cells, text = (CELLS_N3, TEXT_N3) if nonconv else (CELLS_N0, TEXT_N0)
     rows = [(0, (2, 6, 10, 14), cells[0][0]), (0, (6, 10, 14, 18), cells[0][1])]
-    with Handle(example_fa, nonconv=nonconv) as h:
-        assert h.n_cpg(1) == [5]
+    with handle(example_fa, nonconv=nonconv) as h:
+        assert n_cpg(h, 1) == [5]
         h.add(EX_ALNS, 0)
-        assert h.epi_rows(1) == rows
-        assert h.epi_rows(1, 6) == (rows if nonconv == 0 else []) and h.epi_rows(1, 7) == []
-        got, n = h.write_epi(tmp_path / "epi.txt")
+        assert U.epi_rows(h, 1) == rows
+        assert U.epi_rows(h, 1, 6) == (rows if nonconv == 0 else []) and U.epi_rows(h, 1, 7) == []
+        got, n = written_epi(h, tmp_path / "epi.txt")
         assert E.same_text(got, text) and n == 2, got
         assert [line.split("\t")[:7] + line.split("\t")[10:] for line in got.split("\n")] == [line.split("\t")[:7] + line.split("\t")[10:] for line in text.split("\n")]
-        got, n = h.write_epi(tmp_path / "epi6.txt", 6)
+        got, n = written_epi(h, tmp_path / "epi6.txt", 6)
         assert (E.same_text(got, text) and n == 2) if nonconv == 0 else (got == HEADER and n == 0)
-        assert h.nmap() == (7 if nonconv == 0 else 6)
+        assert h.valid_mappings() == (7 if nonconv == 0 else 6)
 
 
 # ---- step borders and directory borders --------------------------------------------------------------------------------------------------
@@ -160,7 +140,7 @@ class Borders:
 @pytest.fixture(scope="module")
 def borders(tmp_path_factory):
     b = Borders()
-    b.fa = write_fasta(tmp_path_factory.mktemp("epi_borders") / "borders.fa", b.names, b.refs)
+    b.fa = U.write_fasta(tmp_path_factory.mktemp("epi_borders") / "borders.fa", b.names, b.refs)
     return b
 
 
@@ -188,13 +168,13 @@ def test_border_set_covers_what_it_claims(borders):
 
 
 def test_n_cpg_and_borders(borders, tmp_path):
-    with Handle(borders.fa) as h:
-        assert h.n_cpg(5) == [len(x) for x in E.cpgs(borders.refs)]
-        assert h.epi_rows(5) == []
+    with handle(borders.fa) as h:
+        assert n_cpg(h, 5) == [len(x) for x in E.cpgs(borders.refs)]
+        assert U.epi_rows(h, 5) == []
         h.add(borders.alns, 0)
-        assert h.epi_rows(5) == E.epi_rows(borders.cells, borders.refs)
-        assert h.epi_rows(5, 4) == E.epi_rows(borders.cells, borders.refs, 4) != []
-        got, n = h.write_epi(tmp_path / "e.txt", 2)
+        assert U.epi_rows(h, 5) == E.epi_rows(borders.cells, borders.refs)
+        assert U.epi_rows(h, 5, 4) == E.epi_rows(borders.cells, borders.refs, 4) != []
+        got, n = written_epi(h, tmp_path / "e.txt", 2)
         want = E.epi_text(borders.names, borders.refs, borders.cells, 2)
         assert E.same_text(got, want) and n == want.count("\n") - 1 > 100
 
@@ -205,9 +185,9 @@ def test_step_borders_per_strand(borders, st):
     mine = [a for a in borders.alns if a[2] == st and a[0] >= 3]
     want = E.epi_rows(E.epi_cells(borders.refs, mine, 0), borders.refs)
     assert len(want) > 150
-    with Handle(borders.fa) as h:
+    with handle(borders.fa) as h:
         h.add(mine, 0)
-        assert h.epi_rows(5) == want
+        assert U.epi_rows(h, 5) == want
 
 
 # ---- model parity ------------------------------------------------------------------------------------------------------------------------------
@@ -260,7 +240,7 @@ class Parity:
 def parity(tmp_path_factory):
     p = Parity()
     p.dir = tmp_path_factory.mktemp("epi_parity")
-    p.fa = write_fasta(p.dir / "parity.fa", p.names, p.refs)
+    p.fa = U.write_fasta(p.dir / "parity.fa", p.names, p.refs)
     return p
 
 
@@ -289,13 +269,13 @@ def test_model_parity(parity, trim_fillin, rm_dup, trim5, trim3, nonconv):
         assert sum(1 for s in E.states_of(parity.refs, parity.alns, trim_fillin, rm_dup, trim5, trim3, 0) if s is not None) > sum(1 for s in states if s is not None) + 20
     third = len(parity.alns) // 3
     for split in ((len(parity.alns),), (third, third + 1, len(parity.alns) - 2 * third - 1)):
-        with Handle(parity.fa, rm_dup=rm_dup, nonconv=nonconv, trim=(trim5, trim3)) as h:
+        with handle(parity.fa, rm_dup=rm_dup, nonconv=nonconv, trim=(trim5, trim3)) as h:
             at = 0
             for part in split:
                 h.add(parity.alns[at:at + part], trim_fillin)
                 at += part
-            assert h.epi_rows(3) == want
-            assert h.epi_rows(3, 3) == E.epi_rows(parity.cells(*key), parity.refs, 3)
+            assert U.epi_rows(h, 3) == want
+            assert U.epi_rows(h, 3, 3) == E.epi_rows(parity.cells(*key), parity.refs, 3)
 
 
 # ---- contention ------------------------------------------------------------------------------------------------------------------------------
@@ -303,9 +283,9 @@ def test_contention(example_fa):
     """5 000 identical reads on one window: one cell holds 5 000"""
     read = (0, 0, 0, 0, -1, EX_ALNS[2][5][:16])   # M U M U at 2, 6, 10, 14
     assert E.epi_cells([EX_REF], [read], 0) == [{0: pat(MUMU=1)}]
-    with Handle(example_fa) as h:
+    with handle(example_fa) as h:
         h.add([read] * 5000, 0)
-        assert h.epi_rows(1) == [(0, (2, 6, 10, 14), pat(MUMU=5000))] and h.epi_rows(1, 5000) == h.epi_rows(1) and h.epi_rows(1, 5001) == []
+        assert U.epi_rows(h, 1) == [(0, (2, 6, 10, 14), pat(MUMU=5000))] and U.epi_rows(h, 1, 5000) == U.epi_rows(h, 1) and U.epi_rows(h, 1, 5001) == []
 
 
 # ---- independence ----------------------------------------------------------------------------------------------------------------------------
@@ -316,18 +296,18 @@ def test_everything_else_is_unchanged(parity):
     R = RL.analyse(parity.refs, parity.alns, 2, True, 0, 0, 2, 4)
     assert R.nmap > 500 and R.dropped > 100
     kw = dict(rm_dup=True, nonconv=2, stats=True, min_cpg=4, snp=1, mbias=True)
-    with Handle(parity.fa, epi=True, **kw) as on, Handle(parity.fa, epi=False, **kw) as off:
+    with handle(parity.fa, epi=True, **kw) as on, handle(parity.fa, epi=False, **kw) as off:
         on.add(parity.alns, 2)
         off.add(parity.alns, 2)
-        assert on.epi_rows(3) == want
+        assert U.epi_rows(on, 3) == want
         for fold in (False, True):
             if fold:
-                on.cpg(); off.cpg()
-            rows = on.rows(3)
-            assert rows == off.rows(3) and len(rows[0]) > 1000 and len(rows[1]) == len(rows[0])
-            assert on.nmap() == off.nmap() == R.nmap and on.dropped() == off.dropped() == R.dropped
-            assert on.pdr_rows(3) == off.pdr_rows(3) != [] and on.hist() == off.hist() and on.mbias() == off.mbias() and len(on.mbias()[0]) > 100
-            assert on.epi_rows(3) == want
+                on.combine_cpg(); off.combine_cpg()
+            rows = U.rows_and_rev(on, 3, 1)
+            assert rows == U.rows_and_rev(off, 3, 1) and len(rows[0]) > 1000 and len(rows[1]) == len(rows[0])
+            assert on.valid_mappings() == off.valid_mappings() == R.nmap and on.nonconv_dropped() == off.nonconv_dropped() == R.dropped
+            assert U.pdr_rows(on, 3) == U.pdr_rows(off, 3) != [] and U.read_hist(on) == U.read_hist(off) and U.mbias_cells(on) == U.mbias_cells(off) and len(U.mbias_cells(on)[0]) > 100
+            assert U.epi_rows(on, 3) == want
 
 
 # ---- state and errors --------------------------------------------------------------------------------------------------------------------------
@@ -335,7 +315,7 @@ def test_state_and_errors(example_fa, tmp_path):
     buf = np.zeros(4096, np.uint32)
     p = buf.ctypes.data
     n64, nr = C.c_uint64(), C.c_uint32()
-    with Handle(example_fa, epi=False) as h:
+    with handle(example_fa, epi=False) as h:
         L = h.L
         assert L.bsx_meth_n_cpg(h.h, 0, C.byref(n64)) == BSX_ERR_STATE and L.bsx_meth_epi_report_chr(h.h, 0, 1, C.byref(nr)) == BSX_ERR_STATE
         assert L.bsx_meth_epi_fetch_rows(h.h, p, p) == BSX_ERR_STATE
@@ -350,50 +330,38 @@ def test_state_and_errors(example_fa, tmp_path):
         assert L.bsx_meth_set_epi(h.h, 0) == 0 and L.bsx_meth_epi_report_chr(h.h, 0, 1, C.byref(nr)) == BSX_ERR_STATE       # off again before any add
         h.add(EX_ALNS, 0)
         assert L.bsx_meth_set_epi(h.h, 1) == BSX_ERR_STATE and L.bsx_meth_set_epi(h.h, 0) == 0                                # no change is no error
-    with Handle(example_fa) as h:
+    with handle(example_fa) as h:
         h.add(EX_ALNS, 0)
         assert h.L.bsx_meth_set_epi(h.h, 0) == BSX_ERR_STATE and h.L.bsx_meth_set_epi(h.h, 1) == 0
         # an epiallele report between a table report and its fetch, and between a PDR report and its fetch, disturbs neither
-    with Handle(example_fa, min_cpg=4) as h, Handle(example_fa, epi=False, min_cpg=4) as plain:
+    with handle(example_fa, min_cpg=4) as h, handle(example_fa, epi=False, min_cpg=4) as plain:
         h.add(EX_ALNS, 0)
         plain.add(EX_ALNS, 0)
-        want_rows, want_pdr = plain.rows(1), plain.pdr_rows(1)
+        want_rows, want_pdr = U.rows_and_rev(plain, 1), U.pdr_rows(plain, 1)
         assert len(want_rows[0]) > 10 and len(want_pdr) == 10
-        h.check(h.L.bsx_meth_report_chr(h.h, 0, 1, 1, C.byref(nr), None, None))
+        _check(h.L.bsx_meth_report_chr(h.h, 0, 1, 1, C.byref(nr), None, None))
         n_table = nr.value
-        h.check(h.L.bsx_meth_pdr_report_chr(h.h, 0, 1, C.byref(nr)))
+        _check(h.L.bsx_meth_pdr_report_chr(h.h, 0, 1, C.byref(nr)))
         n_pdr = nr.value
-        assert h.epi_rows(1) == E.epi_rows(CELLS_N0, [EX_REF])
+        assert U.epi_rows(h, 1) == E.epi_rows(CELLS_N0, [EX_REF])
         pos, dep, met = (np.zeros(n_table, np.uint32) for _ in range(3))
-        h.check(h.L.bsx_meth_fetch_rows(h.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
+        _check(h.L.bsx_meth_fetch_rows(h.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
         assert [(0,) + t for t in zip(pos.tolist(), dep.tolist(), met.tolist())] == want_rows[0]
         pos, reads, disc = (np.zeros(n_pdr, np.uint32) for _ in range(3))
-        h.check(h.L.bsx_meth_pdr_fetch_rows(h.h, pos.ctypes.data, reads.ctypes.data, disc.ctypes.data))
+        _check(h.L.bsx_meth_pdr_fetch_rows(h.h, pos.ctypes.data, reads.ctypes.data, disc.ctypes.data))
         assert [(0,) + t for t in zip(pos.tolist(), reads.tolist(), disc.tolist())] == want_pdr
 
 
 def test_set_reference_rebuilds_the_index():
     """through bsx_meth_create: the index built for one text is discarded when the text changes"""
-    from bsmap_amd import methratio, _check
-    L = methratio._bind()
-    lens = np.array([70, 9], np.uint64)
-    h = C.c_void_p()
-    _check(L.bsx_meth_create(2, lens.ctypes.data, 0, 0, C.byref(h)))
-    try:
+    with Meth.from_lengths([70, 9]) as h:
         first, second = ["AT" * 31 + "ACGCGCGC", "GCGACGTCG"], ["CG" * 35, "GCGCATATA"]
-        n = C.c_uint64()
-        _check(L.bsx_meth_set_epi(h, 1))
+        h.set_epi()
         for refs in (first, second):
             for c, s in enumerate(refs):
-                _check(L.bsx_meth_set_reference(h, c, s.encode()))
-            got = []
-            for c in range(2):
-                _check(L.bsx_meth_n_cpg(h, c, C.byref(n)))
-                got.append(n.value)
-            assert got == [len(x) for x in E.cpgs(refs)]
+                h.set_reference(c, s)
+            assert n_cpg(h, 2) == [len(x) for x in E.cpgs(refs)]
         assert [len(x) for x in E.cpgs(first)] == [3, 3] and [len(x) for x in E.cpgs(second)] == [35, 1]
-    finally:
-        L.bsx_meth_destroy(h)
 
 
 # ---- command line ------------------------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import golden_util as G
+import meth_util as U
 
 pytestmark = pytest.mark.gpu
 STRANDS = ("++", "-+", "+-", "--")  # the library's strand codes 0..3
@@ -106,53 +107,17 @@ def model_rows(depth, meth):
     return [(c, g, d, meth[c][g]) for c in range(len(depth)) for g, d in enumerate(depth[c]) if d >= 1]
 
 
-# ---- the library through its C ABI -------------------------------------------------------------------------------------
-class Handle:
-    def __init__(self, fa, rm_dup=False):
-        from bsmap_amd import methratio, _check
-        self.M, self.check, self.L = methratio, _check, methratio._bind()
-        self.h = C.c_void_p()
-        _check(self.L.bsx_meth_create_from_fasta(fa.encode(), None, 1 if rm_dup else 0, 0, C.byref(self.h)))
+# ---- the library through bsmap_amd.methratio.Meth ---------------------------------------------------------------------------
+def handle(fa, rm_dup=False, mbias=True, trim=None):
+    return U.open_meth(fa, rm_dup, mbias=mbias, trim=trim)
 
-    def close(self):
-        self.L.bsx_meth_destroy(self.h)
 
-    def __enter__(self):
-        return self
+def got_rows(h, n_chr):
+    return U.table_rows(h, n_chr)[0]
 
-    def __exit__(self, *a):
-        self.close()
 
-    def add(self, alns, trim_fillin):
-        if not alns:
-            return
-        off = np.cumsum([0] + [len(a[5]) for a in alns]).astype(np.uint64)
-        seq = np.frombuffer("".join(a[5] for a in alns).encode() + b"\0", np.uint8)
-        arr = [np.array([a[0] for a in alns], np.uint32), np.array([a[1] for a in alns], np.int64), np.array([a[2] for a in alns], np.uint8),
-               np.array([a[3] for a in alns], np.int32), np.array([a[4] for a in alns], np.int64), seq, off]
-        self.check(self.L.bsx_meth_add(self.h, len(alns), *[a.ctypes.data for a in arr], trim_fillin))
-
-    def mbias(self):
-        return self.M.mbias_fetch(self.L, self.h)
-
-    def rows(self, n_chr):
-        got = []
-        for c in range(n_chr):
-            nr = C.c_uint32()
-            self.check(self.L.bsx_meth_report_chr(self.h, c, 1, 1, C.byref(nr), None, None))
-            pos, dep, met = (np.zeros(nr.value, np.uint32) for _ in range(3))
-            self.check(self.L.bsx_meth_fetch_rows(self.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-            got += [(c, int(a), int(b), int(d)) for a, b, d in zip(pos.tolist(), dep.tolist(), met.tolist())]
-        return got
-
-    def nmap(self):
-        n = C.c_uint64()
-        self.check(self.L.bsx_meth_valid_mappings(self.h, C.byref(n)))
-        return n.value
-
-    def table(self, path):
-        self.check(self.L.bsx_meth_write_table(self.h, path.encode(), 0, None, None, 1, 1, None, None))
-        return open(path, "rb").read()
+def got_table(h, path):
+    return U.written_table(h, path)[0].encode()
 
 
 # ---- the edge set of tests 1 and 5 ---------------------------------------------------------------------------------------
@@ -248,14 +213,13 @@ def test_edge_set_covers_what_it_claims(edges):
 @pytest.mark.parametrize("trim_fillin", [0, 2, 5])
 def test_model_parity_on_edge_shapes(edges, trim_fillin, rm_dup):
     depth, meth, cells, over, nmap = edges.model(trim_fillin, bool(rm_dup))
-    with Handle(edges.fa, rm_dup) as h:
-        h.check(h.L.bsx_meth_set_mbias(h.h, 1))
+    with handle(edges.fa, rm_dup) as h:
         h.add(edges.alns, trim_fillin)
         got_cells, got_over = h.mbias()
         assert got_over == over
         assert np.array_equal(got_cells, cells), np.argwhere(got_cells != cells)[:8].tolist()
-        assert h.rows(2) == model_rows(depth, meth)
-        assert h.nmap() == nmap
+        assert got_rows(h, 2) == model_rows(depth, meth)
+        assert h.valid_mappings() == nmap
 
 
 # ---- 2. sum invariant against the pinned table ------------------------------------------------------------------------------
@@ -340,11 +304,10 @@ def test_contention_and_flush(tmp_path):
     n = 1 << 16
     got = []
     for split in ((n,), (1, 30_000, n - 30_001)):
-        with Handle(fa) as h:
-            h.check(h.L.bsx_meth_set_mbias(h.h, 1))
+        with handle(fa) as h:
             for part in split:
                 h.add([aln] * part, 2)
-            got.append((h.mbias(), h.rows(1), h.nmap()))
+            got.append((h.mbias(), got_rows(h, 1), h.valid_mappings()))
     for (got_cells, got_over), rows, got_nmap in got:
         assert got_over == 0 and got_nmap == n
         assert np.array_equal(got_cells, cells * np.uint64(n))
@@ -371,13 +334,12 @@ def test_beyond_the_cap(tmp_path):
     assert nmap == 2 and over >= 2 and all(cells[st, :, a:b].sum() > 0 for st in (0, 1) for a, b in ((0, 16), (256, 1024), (1008, 1024)))
     assert sum(1 for _, pos, st, _, _, read in alns for j in range(1030) if (j if st == 0 else 1029 - j) >= 1024
                and ref[pos + j] == "CG"[st] and read[j] in ("CT", "GA")[st]) == over
-    with Handle(fa) as h:
-        h.check(h.L.bsx_meth_set_mbias(h.h, 1))
-        h.check(h.L.bsx_meth_add_file(h.h, sam.encode(), 1, None, 0, 0, 2, None))
+    with handle(fa) as h:
+        h.add_file(sam)
         got_cells, got_over = h.mbias()
         assert got_over == over
         assert np.array_equal(got_cells, cells)
-        assert h.rows(1) == model_rows(depth, meth) and h.nmap() == 2
+        assert got_rows(h, 1) == model_rows(depth, meth) and h.valid_mappings() == 2
 
 
 # ---- 5. cycle trimming ----------------------------------------------------------------------------------------------------------
@@ -385,20 +347,18 @@ def test_beyond_the_cap(tmp_path):
 def test_cycle_trimming(edges, trim5, trim3):
     for trim_fillin, rm_dup in ((2, 1), (0, 0)):
         depth, meth, cells, over, nmap = edges.model(trim_fillin, bool(rm_dup), trim5, trim3)
-        with Handle(edges.fa, rm_dup) as h:
-            h.check(h.L.bsx_meth_set_mbias(h.h, 1))
-            h.check(h.L.bsx_meth_set_cycle_trim(h.h, trim5, trim3))
+        with handle(edges.fa, rm_dup, trim=(trim5, trim3)) as h:
             h.add(edges.alns, trim_fillin)
             got_cells, got_over = h.mbias()
             assert got_over == over and np.array_equal(got_cells, cells)
-            rows = h.rows(2)
+            rows = got_rows(h, 2)
             assert rows == model_rows(depth, meth)
-            assert h.nmap() == nmap == edges.model(trim_fillin, bool(rm_dup))[4]  # masking calls never changes what counts as a valid mapping
-            table = h.table(str(edges.dir / "trim.txt"))
+            assert h.valid_mappings() == nmap == edges.model(trim_fillin, bool(rm_dup))[4]  # masking calls never changes what counts as a valid mapping
+            table = got_table(h, str(edges.dir / "trim.txt"))
         if (trim5, trim3) == (0, 0):
-            with Handle(edges.fa, rm_dup) as h:  # neither new call made
+            with handle(edges.fa, rm_dup, mbias=False) as h:  # neither new call made
                 h.add(edges.alns, trim_fillin)
-                assert h.table(str(edges.dir / "plain.txt")) == table and h.nmap() == nmap
+                assert got_table(h, str(edges.dir / "plain.txt")) == table and h.valid_mappings() == nmap
             assert len(rows) > 100
         if (trim5, trim3) == (200, 0):
             assert rows == [] and nmap > 200 and table == b"chr\tpos\tstrand\tcontext\tratio\ttotal_C\tmethy_C\tCI_lower\tCI_upper\n"
@@ -410,7 +370,7 @@ def test_cycle_trimming(edges, trim5, trim3):
 def test_state_rules(edges):
     cells = np.zeros((4, 4, CYCLES, 2), np.uint64)
     over = C.c_uint64()
-    with Handle(edges.fa) as h:
+    with handle(edges.fa, mbias=False) as h:
         fetch = lambda: h.L.bsx_meth_mbias_fetch(h.h, cells.ctypes.data, C.byref(over))
         assert fetch() == BSX_ERR_STATE                                   # M-bias off
         assert h.L.bsx_meth_write_mbias(h.h, str(edges.dir / "off.mbias").encode()) == BSX_ERR_STATE
@@ -419,7 +379,7 @@ def test_state_rules(edges):
         h.add(edges.alns[:10], 2)
         assert h.L.bsx_meth_set_mbias(h.h, 1) == BSX_ERR_STATE            # alignments have been added
         assert fetch() == BSX_ERR_STATE
-    with Handle(edges.fa) as h:
+    with handle(edges.fa, mbias=False) as h:
         assert h.L.bsx_meth_set_mbias(h.h, 1) == 0
         h.add(edges.alns[:10], 2)
         assert h.L.bsx_meth_set_mbias(h.h, 0) == BSX_ERR_STATE
@@ -447,10 +407,8 @@ def test_command_line(fmt, edges, tmp_path, capsys):
     methratio.main(["-q", "-z", "-r", "-o", out, "-d", edges.fa, "--trim-3p", "2", path])
     assert capsys.readouterr().out == stdout and open(out).read() == table and stdout.startswith("total ")
     cells, over, lmax, rows, comments = parse_mbias(open(mb).read())
-    with Handle(edges.fa, 1) as h:
-        h.check(h.L.bsx_meth_set_mbias(h.h, 1))
-        h.check(h.L.bsx_meth_set_cycle_trim(h.h, 0, 2))
-        h.check(h.L.bsx_meth_add_file(h.h, path.encode(), 1 if fmt == "sam" else 0, None, 0, 0, 2, None))
+    with handle(edges.fa, 1, trim=(0, 2)) as h:
+        h.add_file(path)
         got_cells, got_over = h.mbias()
     assert np.array_equal(cells, got_cells) and over == got_over == 0 and cells.sum() > 1000
     # the model on the same alignments (a BSP line carries no mate position: no cut)
@@ -469,7 +427,6 @@ def test_command_line(fmt, edges, tmp_path, capsys):
 
 def test_empty_tally_writes_header_and_comments_only(edges, tmp_path):
     mb = str(tmp_path / "empty.mbias")
-    with Handle(edges.fa) as h:
-        h.check(h.L.bsx_meth_set_mbias(h.h, 1))
-        h.check(h.L.bsx_meth_write_mbias(h.h, mb.encode()))
+    with handle(edges.fa) as h:
+        h.write_mbias(mb)
     assert open(mb).read() == "strand\tcontext\tcycle\tmeth\tdepth\tratio\n" + "".join("# total\t%s\t0\t0\tNA\n" % x for x in CONTEXTS) + "# calls beyond cycle 1024: 0\n"

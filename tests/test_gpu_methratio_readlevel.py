@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import golden_util as G
+import meth_util as U
 import readlevel_model as RL
 from test_methratio_readlevel_cpu import ALNS as EX_ALNS, PDR_TEXT, PDR_TEXT_FOLDED, REF as EX_REF, STATS_TEXT, CG_C, CG_G
 
@@ -18,96 +19,19 @@ STRANDS = RL.STRANDS
 BSX_ERR_ARG, BSX_ERR_STATE = -1, -5
 
 
-# ---- the library through its C ABI -------------------------------------------------------------------------------------
-class Handle:
-    def __init__(self, fa, rm_dup=False, nonconv=0, stats=True, min_cpg=4, snp=0, mbias=False, trim=None):
-        from bsmap_amd import methratio, _check
-        self.M, self.check, self.L = methratio, _check, methratio._bind()
-        self.h = C.c_void_p()
-        _check(self.L.bsx_meth_create_from_fasta(fa.encode(), None, 1 if rm_dup else 0, 0, C.byref(self.h)))
-        if snp:
-            _check(self.L.bsx_meth_set_ct_snp(self.h, snp))
-        if mbias:
-            _check(self.L.bsx_meth_set_mbias(self.h, 1))
-        if trim:
-            _check(self.L.bsx_meth_set_cycle_trim(self.h, *trim))
-        if nonconv:
-            _check(self.L.bsx_meth_set_nonconv(self.h, nonconv))
-        if stats:
-            _check(self.L.bsx_meth_set_read_stats(self.h, 1))
-        if min_cpg:
-            _check(self.L.bsx_meth_set_pdr(self.h, min_cpg))
-        self.snp = snp
+# ---- the library through bsmap_amd.methratio.Meth ---------------------------------------------------------------------------
+def handle(fa, rm_dup=False, nonconv=0, stats=True, min_cpg=4, snp=0, mbias=False, trim=None):
+    return U.open_meth(fa, rm_dup, snp, mbias, trim, nonconv, stats, min_cpg)
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *a):
-        self.L.bsx_meth_destroy(self.h)
+def written_pdr(h, path, min_reads=1):
+    n = h.write_pdr(path, min_reads)
+    return U.read_text(path), n
 
-    def add(self, alns, trim_fillin):
-        if not alns:
-            return
-        off = np.cumsum([0] + [len(a[5]) for a in alns]).astype(np.uint64)
-        seq = np.frombuffer("".join(a[5] for a in alns).encode() + b"\0", np.uint8)
-        arr = [np.array([a[0] for a in alns], np.uint32), np.array([a[1] for a in alns], np.int64), np.array([a[2] for a in alns], np.uint8),
-               np.array([a[3] for a in alns], np.int32), np.array([a[4] for a in alns], np.int64), seq, off]
-        self.check(self.L.bsx_meth_add(self.h, len(alns), *[a.ctypes.data for a in arr], trim_fillin))
 
-    def cpg(self):
-        self.check(self.L.bsx_meth_combine_cpg(self.h))
-
-    def nmap(self):
-        n = C.c_uint64()
-        self.check(self.L.bsx_meth_valid_mappings(self.h, C.byref(n)))
-        return n.value
-
-    def dropped(self):
-        n = C.c_uint64()
-        self.check(self.L.bsx_meth_nonconv_dropped(self.h, C.byref(n)))
-        return n.value
-
-    def hist(self):
-        """(cg as nested lists, ch as a list, (reads, cg_over, ch_calls, ch_meth))"""
-        cg, ch, tot = self.M.read_stats_fetch(self.L, self.h)
-        return cg.tolist(), ch.tolist(), tot
-
-    def pdr_rows(self, n_chr, min_reads=1):
-        got = []
-        for c in range(n_chr):
-            nr = C.c_uint32()
-            self.check(self.L.bsx_meth_pdr_report_chr(self.h, c, min_reads, C.byref(nr)))
-            pos, reads, disc = (np.zeros(nr.value, np.uint32) for _ in range(3))
-            self.check(self.L.bsx_meth_pdr_fetch_rows(self.h, pos.ctypes.data, reads.ctypes.data, disc.ctypes.data))
-            got += [(c,) + t for t in zip(pos.tolist(), reads.tolist(), disc.tolist())]
-        return got
-
-    def rows(self, n_chr):
-        """[(chr id, pos, depth, meth)] with min_depth 1 and meth0, and with the C/T-SNP mode on [(chr id, pos, rev_g, rev_ga)] of the same rows"""
-        got, rev = [], []
-        for c in range(n_chr):
-            nr = C.c_uint32()
-            self.check(self.L.bsx_meth_report_chr(self.h, c, 1, 1, C.byref(nr), None, None))
-            pos, dep, met, g, ga = (np.zeros(nr.value, np.uint32) for _ in range(5))
-            self.check(self.L.bsx_meth_fetch_rows(self.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-            got += [(c,) + t for t in zip(pos.tolist(), dep.tolist(), met.tolist())]
-            if self.snp:
-                self.check(self.L.bsx_meth_fetch_rows_snp(self.h, g.ctypes.data, ga.ctypes.data))
-                rev += [(c,) + t for t in zip(pos.tolist(), g.tolist(), ga.tolist())]
-        return got, rev
-
-    def mbias(self):
-        cells, over = self.M.mbias_fetch(self.L, self.h)
-        return {(int(s), int(x), int(cyc), int(m)): int(cells[s, x, cyc, m]) for s, x, cyc, m in zip(*np.nonzero(cells))}, over
-
-    def write_pdr(self, path, min_reads=1):
-        n = C.c_uint64()
-        self.check(self.L.bsx_meth_write_pdr(self.h, str(path).encode(), min_reads, C.byref(n)))
-        return open(path, "rb").read().decode(), n.value
-
-    def write_stats(self, path):
-        self.check(self.L.bsx_meth_write_read_stats(self.h, str(path).encode()))
-        return open(path, "rb").read().decode()
+def written_stats(h, path):
+    h.write_read_stats(path)
+    return U.read_text(path)
 
 
 def model_hist(R):
@@ -123,20 +47,20 @@ def model_rows_snp1(R):
 def compare(h, R, refs, snp=0, mbias=False):
     """everything a handle holds against the model's result, before and after the CpG fold"""
     n = len(refs)
-    assert h.dropped() == R.dropped and h.nmap() == R.nmap
+    assert h.nonconv_dropped() == R.dropped and h.valid_mappings() == R.nmap
     if R.has_stats:
-        assert h.hist() == model_hist(R)
+        assert U.read_hist(h) == model_hist(R)
     if R.min_cpg:
-        assert h.pdr_rows(n) == RL.pdr_rows(R.pdr) and h.pdr_rows(n, 3) == RL.pdr_rows(R.pdr, 3)
-    assert h.rows(n) == (model_rows_snp1(R) if snp else (RL.table_rows(R), []))
+        assert U.pdr_rows(h, n) == RL.pdr_rows(R.pdr) and U.pdr_rows(h, n, 3) == RL.pdr_rows(R.pdr, 3)
+    assert U.rows_and_rev(h, n, snp) == (model_rows_snp1(R) if snp else (RL.table_rows(R), []))
     if mbias:
-        assert h.mbias() == (R.mbias, 0)
-    h.cpg()
+        assert U.mbias_cells(h) == (R.mbias, 0)
+    h.combine_cpg()
     if R.min_cpg:
         folded = RL.fold(refs, R.pdr)
-        assert h.pdr_rows(n) == RL.pdr_rows(folded) and h.pdr_rows(n, 2) == RL.pdr_rows(folded, 2)
+        assert U.pdr_rows(h, n) == RL.pdr_rows(folded) and U.pdr_rows(h, n, 2) == RL.pdr_rows(folded, 2)
     if not snp:
-        assert h.rows(n)[0] == RL.table_rows(R, RL.fold(refs, R.depth), RL.fold(refs, R.meth))
+        assert U.rows_and_rev(h, n)[0] == RL.table_rows(R, RL.fold(refs, R.depth), RL.fold(refs, R.meth))
 
 
 # ---- the worked example ------------------------------------------------------------------------------------------------------------
@@ -148,23 +72,23 @@ def example_fa(tmp_path_factory):
 
 
 def test_worked_example(example_fa, tmp_path):
-    with Handle(example_fa, nonconv=3, min_cpg=4) as h:
+    with handle(example_fa, nonconv=3, min_cpg=4) as h:
         h.add(EX_ALNS, 0)
-        assert h.pdr_rows(1) == sorted([(0, i, 3, 1) for i in CG_C] + [(0, i, 2, 1) for i in CG_G])
-        assert h.dropped() == 1 and h.nmap() == 6
-        cg, ch, tot = h.hist()
+        assert U.pdr_rows(h, 1) == sorted([(0, i, 3, 1) for i in CG_C] + [(0, i, 2, 1) for i in CG_G])
+        assert h.nonconv_dropped() == 1 and h.valid_mappings() == 6
+        cg, ch, tot = U.read_hist(h)
         assert tot == (7, 0, 16, 3) and ch == [6, 0, 0, 1] + [0] * 60
         assert {(a, b): v for a, row in enumerate(cg) for b, v in enumerate(row) if v} == {(5, 5): 2, (5, 0): 2, (5, 3): 1, (5, 4): 1, (3, 2): 1}
-        assert h.write_pdr(tmp_path / "pdr.txt") == (PDR_TEXT, 10) and h.write_stats(tmp_path / "stats.txt") == STATS_TEXT
-        h.cpg()
-        assert h.pdr_rows(1) == [(0, i, 5, 2) for i in CG_C] and h.pdr_rows(1, 6) == []
-        assert h.write_pdr(tmp_path / "pdr_g.txt") == (PDR_TEXT_FOLDED, 5) and h.write_stats(tmp_path / "stats_g.txt") == STATS_TEXT
-    with Handle(example_fa, nonconv=3, min_cpg=6) as h:   # K = 6: no read is eligible
+        assert written_pdr(h, tmp_path / "pdr.txt") == (PDR_TEXT, 10) and written_stats(h, tmp_path / "stats.txt") == STATS_TEXT
+        h.combine_cpg()
+        assert U.pdr_rows(h, 1) == [(0, i, 5, 2) for i in CG_C] and U.pdr_rows(h, 1, 6) == []
+        assert written_pdr(h, tmp_path / "pdr_g.txt") == (PDR_TEXT_FOLDED, 5) and written_stats(h, tmp_path / "stats_g.txt") == STATS_TEXT
+    with handle(example_fa, nonconv=3, min_cpg=6) as h:   # K = 6: no read is eligible
         h.add(EX_ALNS, 0)
-        assert h.pdr_rows(1) == [] and h.write_pdr(tmp_path / "none.txt") == (RL.PDR_HEADER, 0) and h.dropped() == 1
-    with Handle(example_fa, nonconv=0, min_cpg=4) as h:   # N = 0: read 4 is eligible and concordant
+        assert U.pdr_rows(h, 1) == [] and written_pdr(h, tmp_path / "none.txt") == (RL.PDR_HEADER, 0) and h.nonconv_dropped() == 1
+    with handle(example_fa, nonconv=0, min_cpg=4) as h:   # N = 0: read 4 is eligible and concordant
         h.add(EX_ALNS, 0)
-        assert h.pdr_rows(1) == sorted([(0, i, 4, 1) for i in CG_C] + [(0, i, 2, 1) for i in CG_G]) and h.dropped() == 0 and h.nmap() == 7
+        assert U.pdr_rows(h, 1) == sorted([(0, i, 4, 1) for i in CG_C] + [(0, i, 2, 1) for i in CG_G]) and h.nonconv_dropped() == 0 and h.valid_mappings() == 7
 
 
 def test_dropped_owner_still_suppresses_its_duplicate(example_fa):
@@ -172,12 +96,12 @@ def test_dropped_owner_still_suppresses_its_duplicate(example_fa):
     dup = [EX_ALNS[3], EX_ALNS[0]]
     R = RL.analyse([EX_REF], dup, trim_fillin=0, rm_dup=True, nonconv=3)
     assert R.verdict == ["dropped", "invalid"] and R.reads == 1
-    with Handle(example_fa, rm_dup=True, nonconv=3) as h:
+    with handle(example_fa, rm_dup=True, nonconv=3) as h:
         h.add(dup, 0)
-        assert h.hist()[2] == (1, 0, 3, 3) and h.dropped() == 1 and h.nmap() == 0 and h.rows(1) == ([], []) and h.pdr_rows(1) == []
-    with Handle(example_fa, rm_dup=True, nonconv=0) as h:   # without the filter the owner is piled, the duplicate is not
+        assert U.read_hist(h)[2] == (1, 0, 3, 3) and h.nonconv_dropped() == 1 and h.valid_mappings() == 0 and U.rows_and_rev(h, 1) == ([], []) and U.pdr_rows(h, 1) == []
+    with handle(example_fa, rm_dup=True, nonconv=0) as h:   # without the filter the owner is piled, the duplicate is not
         h.add(dup, 0)
-        assert h.hist()[2] == (1, 0, 3, 3) and h.nmap() == 1 and h.pdr_rows(1) == [(0, i, 1, 0) for i in CG_C]
+        assert U.read_hist(h)[2] == (1, 0, 3, 3) and h.valid_mappings() == 1 and U.pdr_rows(h, 1) == [(0, i, 1, 0) for i in CG_C]
 
 
 # ---- the edge set ------------------------------------------------------------------------------------------------------------
@@ -347,7 +271,7 @@ CONFIGS = [  # trim_fillin, rm_dup, trim5, trim3, N, K, histogram, C/T-SNP mode,
 def test_model_parity(edges, trim_fillin, rm_dup, trim5, trim3, nonconv, min_cpg, stats, snp, mbias):
     R = edges.result(trim_fillin, rm_dup, trim5, trim3, nonconv, min_cpg, stats)
     assert R.reads > 500 and (not nonconv or R.dropped >= 10) and (not min_cpg or len(RL.pdr_rows(R.pdr)) > 50)
-    with Handle(edges.fa, rm_dup, nonconv, stats, min_cpg, snp, mbias, (trim5, trim3)) as h:
+    with handle(edges.fa, rm_dup, nonconv, stats, min_cpg, snp, mbias, (trim5, trim3)) as h:
         h.add(edges.alns, trim_fillin)
         compare(h, R, edges.refs, snp, mbias)
 
@@ -359,7 +283,7 @@ def test_directed_cut(edges):
         R = RL.analyse(edges.refs, [aln], 2, False, 0, 0, N0, K0)
         assert R.counts == [want] and R.verdict == ["plain" if want[0] < K0 else "concordant"]
         R.has_stats, R.min_cpg = True, K0
-        with Handle(edges.fa, nonconv=N0, min_cpg=K0) as h:
+        with handle(edges.fa, nonconv=N0, min_cpg=K0) as h:
             h.add([aln], 2)
             compare(h, R, edges.refs)
 
@@ -370,14 +294,14 @@ def test_filter_equals_feeding_the_kept_reads(edges, mbias):
     R = edges.result(2, False)
     kept = [edges.alns[i] for i in R.kept]
     assert 0 < R.dropped and len(kept) == R.nmap < R.reads
-    with Handle(edges.fa, nonconv=N0, snp=1, mbias=mbias) as h, Handle(edges.fa, nonconv=0, snp=1, mbias=mbias) as plain:
+    with handle(edges.fa, nonconv=N0, snp=1, mbias=mbias) as h, handle(edges.fa, nonconv=0, snp=1, mbias=mbias) as plain:
         h.add(edges.alns, 2)
         plain.add(kept, 2)
-        assert h.rows(4) == plain.rows(4) == model_rows_snp1(R) and h.nmap() == plain.nmap() == R.nmap
-        assert h.pdr_rows(4) == plain.pdr_rows(4) == RL.pdr_rows(R.pdr)
-        assert (h.dropped(), plain.dropped()) == (R.dropped, 0)
+        assert U.rows_and_rev(h, 4, 1) == U.rows_and_rev(plain, 4, 1) == model_rows_snp1(R) and h.valid_mappings() == plain.valid_mappings() == R.nmap
+        assert U.pdr_rows(h, 4) == U.pdr_rows(plain, 4) == RL.pdr_rows(R.pdr)
+        assert (h.nonconv_dropped(), plain.nonconv_dropped()) == (R.dropped, 0)
         if mbias:
-            assert h.mbias() == plain.mbias() == (R.mbias, 0)
+            assert U.mbias_cells(h) == U.mbias_cells(plain) == (R.mbias, 0)
 
 
 def test_histogram_does_not_depend_on_the_threshold(edges):
@@ -385,10 +309,10 @@ def test_histogram_does_not_depend_on_the_threshold(edges):
     for n in (0, 1, 3):
         R = edges.result(2, False, 0, 0, n)
         assert model_hist(R) == want and R.dropped == sum(R.ch[n:]) * (n > 0)
-        with Handle(edges.fa, nonconv=n) as h:
+        with handle(edges.fa, nonconv=n) as h:
             h.add(edges.alns, 2)
-            cg, ch, tot = h.hist()
-            assert (cg, ch, tot) == want and h.dropped() == (sum(ch[n:]) if n else 0) == R.dropped and h.nmap() == R.nmap
+            cg, ch, tot = U.read_hist(h)
+            assert (cg, ch, tot) == want and h.nonconv_dropped() == (sum(ch[n:]) if n else 0) == R.dropped and h.valid_mappings() == R.nmap
 
 
 # ---- accumulation and contention ------------------------------------------------------------------------------------------------------------
@@ -421,23 +345,23 @@ def test_accumulation_and_contention(edges):
     want_rows = RL.pdr_rows([p.tolist() for p in pdr])
     assert cg[10][9] >= n and sum(1 for c, i, r, d in want_rows if r >= n and d >= n) == 10 and dropped > 100 and tot[0] == 2 * n
     for split in ((2 * n,), (n + 1, n - 1)):
-        with Handle(edges.fa, nonconv=N0, min_cpg=K0) as h:
+        with handle(edges.fa, nonconv=N0, min_cpg=K0) as h:
             at = 0
             for part in split:
                 h.add(alns[at:at + part], 2)
                 at += part
-            assert h.hist() == (cg.tolist(), ch.tolist(), tuple(tot.tolist()))
-            assert h.pdr_rows(4) == want_rows and h.dropped() == dropped and h.nmap() == nmap
-            h.cpg()
+            assert U.read_hist(h) == (cg.tolist(), ch.tolist(), tuple(tot.tolist()))
+            assert U.pdr_rows(h, 4) == want_rows and h.nonconv_dropped() == dropped and h.valid_mappings() == nmap
+            h.combine_cpg()
             folded = RL.pdr_rows(RL.fold(edges.refs, [p.tolist() for p in pdr]))
-            assert h.pdr_rows(4) == folded and sum(1 for c, i, r, d in folded if r >= n and d >= n) == 10
+            assert U.pdr_rows(h, 4) == folded and sum(1 for c, i, r, d in folded if r >= n and d >= n) == 10
 
 
 # ---- state and errors ----------------------------------------------------------------------------------------------------------------------------
 def test_state_and_errors(edges, tmp_path):
     buf = np.zeros(4096, np.uint64)
     p = buf.ctypes.data
-    with Handle(edges.fa, stats=False, min_cpg=0) as h:
+    with handle(edges.fa, stats=False, min_cpg=0) as h:
         L = h.L
         nr = C.c_uint32()
         assert L.bsx_meth_read_stats_fetch(h.h, p, p, p) == BSX_ERR_STATE and L.bsx_meth_write_read_stats(h.h, str(tmp_path / "s").encode()) == BSX_ERR_STATE
@@ -453,7 +377,7 @@ def test_state_and_errors(edges, tmp_path):
         h.add(edges.alns[:50], 2)
         assert L.bsx_meth_set_read_stats(h.h, 1) == BSX_ERR_STATE and L.bsx_meth_set_pdr(h.h, 4) == BSX_ERR_STATE
         assert L.bsx_meth_set_pdr(h.h, 0) == 0 and L.bsx_meth_set_nonconv(h.h, 3) == 0                                      # no change; the filter at any time
-    with Handle(edges.fa) as h:
+    with handle(edges.fa) as h:
         h.add(edges.alns[:50], 2)
         assert h.L.bsx_meth_set_read_stats(h.h, 0) == BSX_ERR_STATE and h.L.bsx_meth_set_pdr(h.h, 0) == BSX_ERR_STATE
         assert h.L.bsx_meth_set_pdr(h.h, 2) == 0                                                                             # another threshold: later adds
@@ -466,15 +390,15 @@ def test_set_nonconv_between_two_adds(edges):
     A, B = RL.analyse(edges.refs, a, 2, False, 0, 0, 0, K0), RL.analyse(edges.refs, b, 2, False, 0, 0, N0, K0)
     plus = lambda x, y: [[p + q for p, q in zip(u, v)] for u, v in zip(x, y)]
     assert A.dropped == 0 < B.dropped and sum(A.ch[N0:]) > 0
-    with Handle(edges.fa) as h:
+    with handle(edges.fa) as h:
         h.add(a, 2)
         assert h.L.bsx_meth_set_nonconv(h.h, N0) == 0
         h.add(b, 2)
-        assert h.dropped() == B.dropped and h.nmap() == A.nmap + B.nmap
-        assert h.hist() == (plus(A.cg, B.cg), [p + q for p, q in zip(A.ch, B.ch)], tuple(p + q for p, q in zip(model_hist(A)[2], model_hist(B)[2])))
+        assert h.nonconv_dropped() == B.dropped and h.valid_mappings() == A.nmap + B.nmap
+        assert U.read_hist(h) == (plus(A.cg, B.cg), [p + q for p, q in zip(A.ch, B.ch)], tuple(p + q for p, q in zip(model_hist(A)[2], model_hist(B)[2])))
         both = [[[p + q for p, q in zip(u, v)] for u, v in zip(x, y)] for x, y in zip(A.pdr, B.pdr)]
-        assert h.pdr_rows(4) == RL.pdr_rows(both)
-        assert h.rows(4)[0] == RL.table_rows(A, plus(A.depth, B.depth), plus(A.meth, B.meth))
+        assert U.pdr_rows(h, 4) == RL.pdr_rows(both)
+        assert U.rows_and_rev(h, 4)[0] == RL.table_rows(A, plus(A.depth, B.depth), plus(A.meth, B.meth))
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------------------------------

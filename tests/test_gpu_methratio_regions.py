@@ -11,8 +11,11 @@ import os
 import numpy as np
 import pytest
 
+from bsmap_amd import _check
+
 import ctsnp_model as M
 import golden_util as G
+import meth_util as U
 import regions_model as R
 
 pytestmark = pytest.mark.gpu
@@ -28,67 +31,57 @@ def _lib():
     return methratio._bind()
 
 
-class Handle:
-    def __init__(self, fa, snp=False):
-        from bsmap_amd import _check
-        self.check, self.L = _check, _lib()
-        self.h = C.c_void_p()
-        _check(self.L.bsx_meth_create_from_fasta(fa.encode(), None, 0, 0, C.byref(self.h)))
-        if snp:
-            _check(self.L.bsx_meth_set_ct_snp(self.h, 1))
+POISON = 0xA5A5A5A5A5A5A5A5   # what the sums hold before the call: a cell the library leaves out shows
 
-    def close(self):
-        self.L.bsx_meth_destroy(self.h)
 
-    def add(self, alns, trim_fillin):
-        off = np.cumsum([0] + [len(a[5]) for a in alns]).astype(np.uint64)
-        seq = np.frombuffer("".join(a[5] for a in alns).encode() + b"\0", np.uint8)
-        arr = [np.array([a[0] for a in alns], np.uint32), np.array([a[1] for a in alns], np.int64), np.array([a[2] for a in alns], np.uint8),
-               np.array([a[3] for a in alns], np.int32), np.array([a[4] for a in alns], np.int64), seq, off]
-        self.check(self.L.bsx_meth_add(self.h, len(alns), *[a.ctypes.data for a in arr], trim_fillin))
+def handle(fa, snp=False):
+    return U.open_meth(fa, snp=1 if snp else 0)
 
-    def rule(self, mode, mask):
-        """mode: 0 stays off (a handle without the rev cells), 1 <-> 2 at any time"""
-        if mode:
-            self.check(self.L.bsx_meth_set_ct_snp(self.h, mode))
-        self.check(self.L.bsx_meth_set_contexts(self.h, mask))
 
-    def bins(self, c, B, min_depth):
-        n = C.c_uint64()
-        assert self.L.bsx_meth_bins(self.h, c, B, min_depth, 0, None, C.byref(n)) == BSX_ERR_ARG   # the size query
-        out = np.full((n.value, 5), 0xA5A5A5A5A5A5A5A5, np.uint64)
-        n2 = C.c_uint64()
-        self.check(self.L.bsx_meth_bins(self.h, c, B, min_depth, n.value, out.ctypes.data, C.byref(n2)))
-        assert n2.value == n.value
-        return out.tolist()
+def rule(h, mode, mask):
+    """mode: 0 stays off (a handle without the rev cells), 1 <-> 2 at any time"""
+    if mode:
+        h.set_ct_snp(mode)
+    h.set_contexts(mask)
 
-    def regions(self, ivs, min_depth):
-        """ivs: [(chr id, start, end)] -> [[N, M, D, E, MC]]"""
-        a = [np.array([iv[k] for iv in ivs], np.uint32) for k in range(3)]
-        out = np.full((len(ivs), 5), 0xA5A5A5A5A5A5A5A5, np.uint64)
-        self.check(self.L.bsx_meth_regions(self.h, len(ivs), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, min_depth, out.ctypes.data))
-        return out.tolist()
 
-    def wig(self, path, B, min_depth):
-        self.check(self.L.bsx_meth_write_wig(self.h, str(path).encode(), B, min_depth))
-        return open(path, "rb").read()
+def got_bins(h, c, B, min_depth):
+    """the raw call into a preset array, and Meth.bins, which has to give the same"""
+    n, n2 = C.c_uint64(), C.c_uint64()
+    assert h.L.bsx_meth_bins(h.h, c, B, min_depth, 0, None, C.byref(n)) == BSX_ERR_ARG   # the size query
+    out = np.full((n.value, 5), POISON, np.uint64)
+    _check(h.L.bsx_meth_bins(h.h, c, B, min_depth, n.value, out.ctypes.data, C.byref(n2)))
+    assert n2.value == n.value and np.array_equal(h.bins(c, B, min_depth), out)
+    return out.tolist()
 
-    def region_file(self, bed, path, min_depth):
-        nw, nd = C.c_uint64(), C.c_uint64()
-        self.check(self.L.bsx_meth_write_regions(self.h, str(bed).encode(), str(path).encode(), min_depth, C.byref(nw), C.byref(nd)))
-        return open(path, "rb").read(), nw.value, nd.value
 
-    def report(self, c, min_depth, meth0=1):
-        nr, cov, sd = C.c_uint32(), C.c_uint64(), C.c_uint64()
-        self.check(self.L.bsx_meth_report_chr(self.h, c, min_depth, meth0, C.byref(nr), C.byref(cov), C.byref(sd)))
-        pos, dep, met = (np.zeros(nr.value, np.uint32) for _ in range(3))
-        self.check(self.L.bsx_meth_fetch_rows(self.h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-        return list(zip(pos.tolist(), met.tolist(), dep.tolist())), cov.value, sd.value
+def got_regions(h, ivs, min_depth):
+    """ivs: [(chr id, start, end)] -> [[N, M, D, E, MC]], likewise"""
+    a = [np.array([iv[k] for iv in ivs], np.uint32) for k in range(3)]
+    out = np.full((len(ivs), 5), POISON, np.uint64)
+    _check(h.L.bsx_meth_regions(h.h, len(ivs), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, min_depth, out.ctypes.data))
+    assert np.array_equal(h.regions(*a, min_depth), out)
+    return out.tolist()
 
-    def table(self, path, min_depth=1, meth0=1):
-        nc, nd = C.c_uint64(), C.c_uint64()
-        self.check(self.L.bsx_meth_write_table(self.h, str(path).encode(), 0, None, None, min_depth, meth0, C.byref(nc), C.byref(nd)))
-        return open(path, "rb").read(), nc.value, nd.value
+
+def got_wig(h, path, B, min_depth):
+    h.write_wig(path, B, min_depth)
+    return open(path, "rb").read()
+
+
+def got_region_file(h, bed, path, min_depth):
+    nw, nd = h.write_regions(bed, path, min_depth)
+    return open(path, "rb").read(), nw, nd
+
+
+def got_report(h, c, min_depth, meth0=1):
+    pos, dep, met, cov, sd = h.report(c, min_depth, meth0)
+    return list(zip(pos.tolist(), met.tolist(), dep.tolist())), cov, sd
+
+
+def got_table(h, path, min_depth=1, meth0=1):
+    text, nc, nd = U.written_table(h, path, min_depth, meth0)
+    return text.encode(), nc, nd
 
 
 def make_read(rng, ref, snp, pos, L, st, noise=True):
@@ -165,12 +158,12 @@ class World:
         """one pile-up per (SNP cells or not, folded or not), shared by all tests: the calls under test change no counter"""
         key = (bool(mode), cpg)
         if key not in self._h:
-            h = Handle(self.fa, snp=bool(mode))
+            h = handle(self.fa, snp=bool(mode))
             h.add(self.alns, self.TRIM)
             if cpg:
-                h.check(h.L.bsx_meth_combine_cpg(h.h))
+                h.combine_cpg()
             self._h[key] = h
-        self._h[key].rule(mode, mask)
+        rule(self._h[key], mode, mask)
         return self._h[key]
 
 
@@ -234,8 +227,8 @@ def test_bins_against_the_model(world, mode, mask, md, cpg):
     h, S = world.handle(mode, mask, cpg), world.S(mode, mask, md, cpg)
     for B in (1, 2, 25, 63, 64, 65, 1000, 1024, 4096, 2 * world.T + 67, 1 << 31):
         for c in range(4):
-            assert h.bins(c, B, md) == R.bin_sums(S, c, B), (B, c)
-        assert h.wig(world.dir / "t.wig", B, md) == R.wig_text(world.names, S, B).encode(), B
+            assert got_bins(h, c, B, md) == R.bin_sums(S, c, B), (B, c)
+        assert got_wig(h, world.dir / "t.wig", B, md) == R.wig_text(world.names, S, B).encode(), B
 
 
 # ---- 2. regions against the model -----------------------------------------------------------------------------------------------------
@@ -248,13 +241,13 @@ def test_regions_against_the_model(world, mode, mask, md, cpg):
         if (c, a, b) not in memo:
             memo[(c, a, b)] = R.interval_sums(S, c, a, b)
         return memo[(c, a, b)]
-    got = h.regions([iv[:3] for iv in ivs], md)                                    # one call, the order kept
+    got = got_regions(h, [iv[:3] for iv in ivs], md)                                    # one call, the order kept
     assert got == [want_of(*iv[:3]) for iv in ivs]
     assert sum(1 for s in got if s[0]) > 60 and sum(1 for s in got if not s[0]) >= 6
     bed = str(world.dir / "r.bed")
     open(bed, "w").write(bed_text(world, ivs))
     recs, dropped = R.parse_bed(bed_text(world, ivs), world.names, world.lens)
-    text, nw, nd = h.region_file(bed, world.dir / "r.txt", md)
+    text, nw, nd = got_region_file(h, bed, world.dir / "r.txt", md)
     assert (nw, nd) == (len(ivs), 0) == (len(recs), dropped)
     assert text == R.region_text(world.names, S, recs).encode()
 
@@ -266,15 +259,15 @@ def test_ties_to_the_report(world, mode, cpg):
     for mask in MASKS:
         h = world.handle(mode, mask, cpg)
         for md in DEPTHS:
-            whole = h.regions([(c, 0, world.lens[c]) for c in range(4)], md)
+            whole = got_regions(h, [(c, 0, world.lens[c]) for c in range(4)], md)
             for c in range(4):
-                rows, cov, sd = h.report(c, md, 1)
+                rows, cov, sd = got_report(h, c, md, 1)
                 assert (whole[c][0], whole[c][2]) == (cov, sd), (mask, md, c)
-                b1 = h.bins(c, 1, md)
+                b1 = got_bins(h, c, 1, md)
                 assert [(j, s[1], s[2]) for j, s in enumerate(b1) if s[0]] == rows and all(s[0] <= 1 for s in b1)
                 for B in (25, 1000):
                     nb = world.lens[c] // B + 1
-                    assert h.bins(c, B, md) == h.regions([(c, j * B, min((j + 1) * B, world.lens[c])) for j in range(nb)], md), (B, c)
+                    assert got_bins(h, c, B, md) == got_regions(h, [(c, j * B, min((j + 1) * B, world.lens[c])) for j in range(nb)], md), (B, c)
             assert sum(s[0] for s in whole) > 50
 
 
@@ -319,10 +312,10 @@ def test_contention_and_determinism(world, mode):
     want = R.interval_sums(S, 3, 0, n)
     assert want[0] > 1000
     ivs = [(3, 0, n)] * 4096
-    first = h.regions(ivs, 1)
+    first = got_regions(h, ivs, 1)
     assert first == [want] * 4096
-    assert h.regions(ivs, 1) == first
-    a, b = h.wig(world.dir / "d1.wig", 25, 1), h.wig(world.dir / "d2.wig", 25, 1)
+    assert got_regions(h, ivs, 1) == first
+    a, b = got_wig(h, world.dir / "d1.wig", 25, 1), got_wig(h, world.dir / "d2.wig", 25, 1)
     assert a == b and len(a) > 1000
 
 
@@ -344,15 +337,15 @@ def test_intervals_of_many_tiles(tmp_path, mode):
     fa = str(tmp_path / "long.fa")
     open(fa, "w").write(">long\n" + ref + "\n")
     ivs = [(0, 0, n), (0, T // 2, n - T // 2), (0, 0, n), (0, 100, 160), (0, 0, n)]
-    h = Handle(fa, snp=bool(mode))
+    h = handle(fa, snp=bool(mode))
     try:
         h.add(alns, 2)
-        h.rule(mode, 0)
+        rule(h, mode, 0)
         want = [R.interval_sums(S, *iv) for iv in ivs]
-        got = h.regions(ivs, 1)
+        got = got_regions(h, ivs, 1)
         assert got == want and want[0][0] > 10000 and want[1] != want[0]
-        assert h.regions(ivs, 1) == got
-        rows, cov, sd = h.report(0, 1, 1)
+        assert got_regions(h, ivs, 1) == got
+        rows, cov, sd = got_report(h, 0, 1, 1)
         assert (got[0][0], got[0][2]) == (cov, sd) and got[0][1] == sum(r[1] for r in rows)
     finally:
         h.close()
@@ -370,21 +363,21 @@ def test_borders_between_chromosomes(tmp_path, mode):
             (1, 0, 1, 0, -1, "GTTACGTT"), (1, 0, 1, 0, -1, "GTTACATT"), (1, 0, 1, 0, -1, "ATT"), (1, 0, 0, 0, -1, "GTTACGTT"), (1, 0, 2, 0, -1, "GTTAC")]
     K = M.pileup(refs, alns, 0)
     assert K.depth[0][8] == 2 and K.depth[1][0] == 3 and K.meth[1][0] == 2
-    h = Handle(fa, snp=bool(mode))
+    h = handle(fa, snp=bool(mode))
     try:
         h.add(alns, 0)
         for mask in (0, 1, 6, 8):
-            h.rule(mode, mask)
+            rule(h, mode, mask)
             S = R.site_table(K, 1, mode, mask)
             for B in (1, 4, 9, 8, 16, 64):
                 for c in range(2):
-                    assert h.bins(c, B, 1) == R.bin_sums(S, c, B), (mask, B, c)
+                    assert got_bins(h, c, B, 1) == R.bin_sums(S, c, B), (mask, B, c)
             ivs = [(0, 0, 9), (0, 8, 9), (0, 5, 200), (1, 0, 8), (1, 0, 1), (0, 9, 9), (1, 0, 0)]
-            assert h.regions(ivs, 1) == [R.interval_sums(S, *iv) for iv in ivs], mask
+            assert got_regions(h, ivs, 1) == [R.interval_sums(S, *iv) for iv in ivs], mask
         S_cg, S_other = R.site_table(K, 1, mode, 1), R.site_table(K, 1, mode, 8)
         assert S_cg[0][8] is None and S_other[0][8] and S_cg[0][3] and S_cg[1][0] is None and S_other[1][0]   # the border letters are in class 3
-        h.rule(mode, 0)
-        assert h.regions([(0, 8, 9)], 1)[0][:3] == [1, 2, 2] and h.regions([(1, 0, 1)], 1)[0][:3] == [1, 2, 3]
+        rule(h, mode, 0)
+        assert got_regions(h, [(0, 8, 9)], 1)[0][:3] == [1, 2, 2] and got_regions(h, [(1, 0, 1)], 1)[0][:3] == [1, 2, 3]
     finally:
         h.close()
 
@@ -392,12 +385,12 @@ def test_borders_between_chromosomes(tmp_path, mode):
 # ---- 6. state --------------------------------------------------------------------------------------------------------------------------------
 def test_the_calls_change_nothing(world):
     h = world.handle(1, 0, 1)
-    before = h.table(world.dir / "before.txt")
-    h.bins(3, 25, 1); h.regions([(3, 0, world.lens[3]), (2, 5, 50)], 1)
-    h.wig(world.dir / "s.wig", 64, 3)
+    before = got_table(h, world.dir / "before.txt")
+    got_bins(h, 3, 25, 1); got_regions(h, [(3, 0, world.lens[3]), (2, 5, 50)], 1)
+    got_wig(h, world.dir / "s.wig", 64, 3)
     open(world.dir / "s.bed", "w").write("wa_long\t0\t100\n")
-    h.region_file(world.dir / "s.bed", world.dir / "s.txt", 1)
-    assert h.table(world.dir / "after.txt") == before and before[1] > 1000
+    got_region_file(h, world.dir / "s.bed", world.dir / "s.txt", 1)
+    assert got_table(h, world.dir / "after.txt") == before and before[1] > 1000
     assert before[0].decode() == M.table(world.names, world.K[1], 1, True, 1)[0]
 
 
@@ -428,13 +421,13 @@ def test_argument_errors(world):
 
 
 def test_before_any_alignment(world, tmp_path):
-    h = Handle(world.fa)
+    h = handle(world.fa)
     try:
-        assert h.regions([(3, 0, world.lens[3]), (0, 0, 1)], 1) == [[0] * 5] * 2
-        assert h.bins(2, 25, 1) == [[0] * 5] * (4099 // 25 + 1)
-        assert h.wig(tmp_path / "z.wig", 25, 1).decode() == "track type=wiggle_0\n" + "".join("variableStep chrom=%s span=25\n" % n for n in sorted(world.names))
+        assert got_regions(h, [(3, 0, world.lens[3]), (0, 0, 1)], 1) == [[0] * 5] * 2
+        assert got_bins(h, 2, 25, 1) == [[0] * 5] * (4099 // 25 + 1)
+        assert got_wig(h, tmp_path / "z.wig", 25, 1).decode() == "track type=wiggle_0\n" + "".join("variableStep chrom=%s span=25\n" % n for n in sorted(world.names))
         open(tmp_path / "z.bed", "w").write("wb_mid\t0\t10\tz\n")
-        assert h.region_file(tmp_path / "z.bed", tmp_path / "z.txt", 1) == ((R.REGION_HEADER + "wb_mid\t0\t10\tz\t0\t0\t0\t0.00\tNA\tNA\tNA\n").encode(), 1, 0)
+        assert got_region_file(h, tmp_path / "z.bed", tmp_path / "z.txt", 1) == ((R.REGION_HEADER + "wb_mid\t0\t10\tz\t0\t0\t0\t0.00\tNA\tNA\tNA\n").encode(), 1, 0)
     finally:
         h.close()
 

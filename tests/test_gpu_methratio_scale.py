@@ -4,13 +4,13 @@ oracle/methratio_oracle.py on the very same text (pinned to the reference script
 included), and both are compared as whole strings: every column is an integer or the same double arithmetic on the same integers.
 
 Every fragment end (the slot of the duplicate filter) lies inside its chromosome, so that -r is defined by the reference."""
-import ctypes as C
 import os
 import re
 
 import numpy as np
 import pytest
 
+import meth_util as U
 from oracle import methratio_oracle as MO
 
 pytestmark = pytest.mark.gpu
@@ -173,15 +173,11 @@ def test_three_files_in_an_order_that_matters(wide, capsys, tmp_path):
 def test_calls(wide):
     """Reaches: first-wins across bsx_meth_add calls: the wide alignments as arrays in batches of 1, 53, 4 099 and the remaining
     ~186 000, duplicate removal on; rows and the count of valid mappings are the file path's (= the oracle's -z -r)"""
-    from bsmap_amd import methratio, _check
+    from bsmap_amd.methratio import Meth
     table, summary = wide.expected(("-z", "-r"))
-    L = methratio._bind()
-    h = C.c_void_p()
-    lens = wide.lens.astype(np.uint64)
-    _check(L.bsx_meth_create(len(wide.names), lens.ctypes.data, 1, 0, C.byref(h)))
-    try:
+    with Meth.from_lengths(wide.lens, rm_dup=True) as m:
         for i in range(len(wide.names)):
-            _check(L.bsx_meth_set_reference(h, i, wide.genome[wide.off[i]:wide.off[i + 1]].tobytes()))
+            m.set_reference(i, wide.genome[wide.off[i]:wide.off[i + 1]])
         keep = np.array([f != "NM" for f in wide.flag])
         idx = np.nonzero(keep)[0]
         assert len(idx) > 180_000
@@ -191,24 +187,14 @@ def test_calls(wide):
             b0 += len(part)
             seq = b"".join(wide.seqs[wide.so[i]:wide.so[i + 1]] for i in part.tolist()) + b"\0"
             off = np.concatenate([[0], np.cumsum(wide.so[part + 1] - wide.so[part])]).astype(np.uint64)
-            arr = [wide.c[part].astype(np.uint32), wide.pos[part].astype(np.int64), wide.st[part].astype(np.uint8), wide.ins[part].astype(np.int32),
-                   np.full(len(part), -1, np.int64), np.frombuffer(seq, np.uint8), off]
-            _check(L.bsx_meth_add(h, len(part), *[a.ctypes.data for a in arr], 2))
+            m.add_arrays(len(part), wide.c[part].astype(np.uint32), wide.pos[part].astype(np.int64), wide.st[part].astype(np.uint8), wide.ins[part].astype(np.int32),
+                         np.full(len(part), -1, np.int64), np.frombuffer(seq, np.uint8), off, 2)
         assert b0 == len(idx)
-        got = []
-        for i, n in enumerate(wide.names):
-            nr = C.c_uint32()
-            _check(L.bsx_meth_report_chr(h, i, 1, 1, C.byref(nr), None, None))
-            pos, dep, met = (np.zeros(nr.value, np.uint32) for _ in range(3))
-            _check(L.bsx_meth_fetch_rows(h, pos.ctypes.data, dep.ctypes.data, met.ctypes.data))
-            got += [(n, int(a) + 1, int(b), int(c)) for a, b, c in zip(pos.tolist(), dep.tolist(), met.tolist())]
-        nmap = C.c_uint64()
-        _check(L.bsx_meth_valid_mappings(h, C.byref(nmap)))
-    finally:
-        L.bsx_meth_destroy(h)
+        got = [(wide.names[c], pos + 1, dep, met) for c, pos, dep, met in U.table_rows(m, len(wide.names))[0]]
+        nmap = m.valid_mappings()
     exp = [(f[0], int(f[1]), int(f[5]), int(f[6])) for f in _rows(table)]
     assert sorted(got) == sorted(exp) and len(got) > 200_000
-    assert nmap.value == int(re.match(r"total (\d+) valid mappings", summary).group(1))
+    assert nmap == int(re.match(r"total (\d+) valid mappings", summary).group(1))
 
 
 class Deep:

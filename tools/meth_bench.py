@@ -33,36 +33,33 @@ def main():
     ap.add_argument("--pdr-min-cpg", dest="pdr_min_cpg", type=int, default=4)
     ap.add_argument("--epi", dest="epi", action="store_true")
     a = ap.parse_args()
-    L = MR._bind()
     rng = np.random.default_rng(1)
     lens = np.array([int(x * a.genome) for x in (248956422, 242193529, 198295559, 190214555, 181538259, 170805979, 159345973, 145138636, 138394717, 133797422,
                                                 135086622, 133275309, 114364328, 107043718, 101991189, 90338345, 83257441, 80373285, 58617616, 64444167,
                                                 46709983, 50818468, 156040895, 57227415)], np.uint64)
-    h = C.c_void_p()
-    B._check(L.bsx_meth_create(len(lens), lens.ctypes.data, 1, 0, C.byref(h)))
+    m = MR.Meth.from_lengths(lens, rm_dup=True)
+    L, h = m.L, m.h   # the timed regions below that hold one library call and no fetch make that call directly
     if a.ct_snp != "no-action":
-        B._check(L.bsx_meth_set_ct_snp(h, MR.CT_SNP_MODES.index(a.ct_snp)))
+        m.set_ct_snp(a.ct_snp)
     if a.nonconv_filter:
-        B._check(L.bsx_meth_set_nonconv(h, a.nonconv_filter))
+        m.set_nonconv(a.nonconv_filter)
     if a.read_stats:
-        B._check(L.bsx_meth_set_read_stats(h, 1))
+        m.set_read_stats()
     if a.pdr:
-        B._check(L.bsx_meth_set_pdr(h, a.pdr_min_cpg))
+        m.set_pdr(a.pdr_min_cpg)
     letters = np.frombuffer(b"ACGT", np.uint8)
     chunks = []
     for c, n in enumerate(lens.tolist()):
         s = letters[rng.integers(0, 4, n, dtype=np.uint8)]
-        B._check(L.bsx_meth_set_reference(h, c, s.tobytes()))
+        m.set_reference(c, s.tobytes())   # (the array itself would do; the copy is kept as every earlier figure in profiles/ was taken with it)
         if c < 2:
             chunks.append(s)
     extra = {}
     if a.epi:  # after the reference is whole: the first call that needs the index builds it
-        B._check(L.bsx_meth_set_epi(h, 1))
+        m.set_epi()
         t5, n_cpg = time.perf_counter(), 0
         for c in range(len(lens)):
-            nc = C.c_uint64()
-            B._check(L.bsx_meth_n_cpg(h, c, C.byref(nc)))
-            n_cpg += nc.value
+            n_cpg += m.n_cpg(c)
         extra.update(cpg_index_build_s=round(time.perf_counter() - t5, 3), n_cpg=n_cpg)
     n, ln = a.aln, a.len
     # alignments on the first two chromosomes only need their letters on the host; positions are uniform there
@@ -80,9 +77,9 @@ def main():
     seq[(~plus)[:, None] & (seq == ord("G")) & conv] = ord("A")
     ins = np.zeros(n, np.int32); cut = np.full(n, -1, np.int64)
     off = (np.arange(n + 1, dtype=np.uint64) * ln)
-    B._check(L.bsx_meth_add(h, min(n, 1 << 20), chr_.ctypes.data, pos.ctypes.data, strand.ctypes.data, ins.ctypes.data, cut.ctypes.data, seq.ctypes.data, off.ctypes.data, 2))
+    m.add_arrays(min(n, 1 << 20), chr_, pos, strand, ins, cut, seq, off, 2)
     t0 = time.perf_counter()
-    B._check(L.bsx_meth_add(h, n, chr_.ctypes.data, pos.ctypes.data, strand.ctypes.data, ins.ctypes.data, cut.ctypes.data, seq.ctypes.data, off.ctypes.data, 2))
+    m.add_arrays(n, chr_, pos, strand, ins, cut, seq, off, 2)   # every array has its type already: passed as it is
     dt = time.perf_counter() - t0
     t1 = time.perf_counter()
     rows = cov = 0
@@ -92,11 +89,9 @@ def main():
         rows += nr.value; cov += cv.value
     dt_rep = time.perf_counter() - t1
     if a.nonconv_filter:
-        nd = C.c_uint64()
-        B._check(L.bsx_meth_nonconv_dropped(h, C.byref(nd)))
-        extra.update(nonconv_filter=a.nonconv_filter, dropped=nd.value)
+        extra.update(nonconv_filter=a.nonconv_filter, dropped=m.nonconv_dropped())
     if a.read_stats:
-        extra["read_stats_totals"] = dict(zip(("reads", "cg_over", "ch_calls", "ch_meth"), MR.read_stats_fetch(L, h)[2]))
+        extra["read_stats_totals"] = dict(zip(("reads", "cg_over", "ch_calls", "ch_meth"), m.read_stats()[2]))
     if a.pdr:
         t4, pdr_rows = time.perf_counter(), 0
         for c in range(len(lens)):
@@ -135,7 +130,7 @@ def main():
             B._check(L.bsx_meth_regions(h, n_iv, ic.ctypes.data, start.ctypes.data, end.ctypes.data, 1, sums.ctypes.data))
             took.append(round(time.perf_counter() - t3, 3))
         extra.setdefault("regions_s", []).append({"intervals": n_iv, "len": iv_len, "s": took, "sites": int(sums[:, 0].sum())})
-    L.bsx_meth_destroy(h)
+    m.close()
     print(json.dumps(dict({"alignments": n, "read_len": ln, "ct_snp": a.ct_snp, "add_s_incl_pcie": round(dt, 3), "alignments_per_s_incl_pcie": round(n / dt),
                            "report_s_all_chromosomes": round(dt_rep, 3), "rows": rows, "covered": cov, "genome_bp": int(lens.sum())}, **extra)))
 
