@@ -77,6 +77,7 @@ EXPORTS = [
     "bsx_meth_set_nonconv", "bsx_meth_nonconv_dropped", "bsx_meth_set_read_stats", "bsx_meth_read_stats_fetch", "bsx_meth_write_read_stats",
     "bsx_meth_set_pdr", "bsx_meth_pdr_report_chr", "bsx_meth_pdr_fetch_rows", "bsx_meth_write_pdr",
     "bsx_meth_set_epi", "bsx_meth_n_cpg", "bsx_meth_epi_report_chr", "bsx_meth_epi_fetch_rows", "bsx_meth_write_epi",
+    "bsx_meth_diff_report_chr", "bsx_meth_diff_fetch_rows", "bsx_meth_write_diff", "bsx_meth_diff_regions", "bsx_meth_write_diff_regions", "bsx_meth_write_diff_bins",
 ]
 
 

@@ -17,6 +17,8 @@
 // The reports that list rows in order share one ordered compaction, compact_count / compact_emit, over a rule struct (what a row is, what it stores):
 //   k_meth_count / k_meth_emit (TableRule: the positions the table lists), k_pdr_count / k_pdr_emit (PdrRule), k_epi_count / k_epi_emit (EpiRule)
 // and one host path, meth_compact (count, scan, size, emit).  A new per-position or per-window report is a rule struct and two wrappers.
+// Two handles at once (differential methylation): k_diff_count / k_diff_emit (DiffRule: the common sites of two samples whose ratios differ),
+//   k_meth_fisher (the two-sided Fisher exact test of every row, bsx_meth_diff.h) and k_meth_diff_regions (the joint form of k_meth_regions; bins are intervals)
 // One place per idea elsewhere too: meth_forward_call (what a forward call is), meth_chr_of / meth_is_cpg (which chromosome, which CpG), meth_covered (the row
 // rule), meth_site (a site's five values); on the host DevBuf (device memory that owns itself), OutFile, guarded (no exception across the C ABI), format_rows,
 // sorted_chromosomes, and the row formatters of bsx_meth_text.h and bsx_meth_epi.h.
@@ -46,6 +48,7 @@
 
 #include "bsx_cpus.h"
 #include "bsx_internal.h"
+#include "bsx_meth_diff.h"
 #include "bsx_meth_epi.h"
 #include "bsx_meth_parse.h"
 #include "bsx_meth_text.h"
@@ -870,6 +873,113 @@ __global__ __launch_bounds__(REGION_WAVES * 64) void k_meth_regions(MethDev M, R
     for (int q = 0; q < 5; q++) atomicAdd(&out[q], tot[q]);
 }
 
+// ---- two samples: differential methylation (bsx_meth_diff_report_chr, bsx_meth_diff_regions) ----
+// Position k is a COMMON SITE of the samples A and B when meth_covered holds for it in both (R.snp is 0: no rev cells) and both raw depths are above 0.
+// B is B's counters under A's letters and offsets (the host builds it so).  The one place that says it: the rows and the interval sums both ask here.
+__device__ __forceinline__ bool diff_site(const MethDev &A, const MethDev &B, u64 g0, u64 n, u64 k, const RowRule &R, uint32_t &dA, uint32_t &mA, uint32_t &dB, uint32_t &mB)
+{
+    uint32_t g, ga;
+    dB = mB = 0;
+    if (!meth_covered(A, nullptr, g0, n, k, R, dA, mA, g, ga) || dA == 0) return false;
+    return meth_covered(B, nullptr, g0, n, k, R, dB, mB, g, ga) && dB != 0;
+}
+
+// The rows (bsx_meth_diff_report_chr): the common sites whose ratios differ by at least permille / 1000: |mA dB - mB dA| 1000 >= permille dA dB, both
+// sides as 128-bit integers (a product of two 32-bit counts fits 64 bits).  cls: bits 0-1 the context class, bit 2 set over a G
+struct DiffRule {
+    struct Row { uint32_t mA, dA, mB, dB; };
+    MethDev A, B;
+    u64 g0, n;
+    RowRule R;
+    uint32_t permille;
+    uint32_t *out_pos;
+    uint4 *out_counts;
+    uint8_t *out_cls;
+    __device__ __forceinline__ bool row(u64 k, Row &w) const
+    {
+        if (!diff_site(A, B, g0, n, k, R, w.dA, w.mA, w.dB, w.mB)) return false;
+        const u64 x = (u64)w.mA * w.dB, y = (u64)w.mB * w.dA, diff = x > y ? x - y : y - x, dd = (u64)w.dA * w.dB;
+        const u64 lhi = __umul64hi(diff, 1000ull), llo = diff * 1000ull, rhi = __umul64hi(dd, (u64)permille), rlo = dd * (u64)permille;
+        return lhi > rhi || (lhi == rhi && llo >= rlo);
+    }
+    __device__ __forceinline__ void store(u64 o, u64 k, const Row &w) const
+    {
+        const bool plus = A.ref[g0 + k] == 'C';
+        out_pos[o] = (uint32_t)k; out_counts[o] = make_uint4(w.mA, w.dA, w.mB, w.dB);
+        out_cls[o] = (uint8_t)(meth_context(A.ref, g0 + k, g0, g0 + n, plus) | (plus ? 0u : 4u));
+    }
+};
+
+__global__ __launch_bounds__(256) void k_diff_count(MethDev A, MethDev B, u64 g0, u64 n, RowRule R, uint32_t permille, uint32_t *blk_rows)
+{
+    DiffRule rule{A, B, g0, n, R, permille, nullptr, nullptr, nullptr};
+    compact_count(rule, n, blk_rows);
+}
+
+__global__ __launch_bounds__(256) void k_diff_emit(MethDev A, MethDev B, u64 g0, u64 n, RowRule R, uint32_t permille, const uint32_t *blk_start, uint32_t *out_pos,
+                                                   uint4 *out_counts, uint8_t *out_cls)
+{
+    DiffRule rule{A, B, g0, n, R, permille, out_pos, out_counts, out_cls};
+    compact_emit(rule, n, blk_start);
+}
+
+// p of every row, a thread per row: over the compacted rows of k_diff_emit (rows4: mA, dA, mB, dB) or over interval sums (sums5: N, MA, DA, MB, DB; NaN
+// where N == 0), whichever pointer is not null.  Every lane has a row; the lanes of a wave differ in the length of their walks (the row's support).
+__global__ __launch_bounds__(256) void k_meth_fisher(const uint4 *rows4, const u64 *sums5, u64 n, double *p)
+{
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (rows4) {
+        const uint4 c = rows4[i];
+        p[i] = bsx_meth_diff::fisher_p((double)c.x, (double)c.y, (double)c.z, (double)c.w);
+    } else {
+        const u64 *s = sums5 + i * 5;
+        p[i] = s[0] ? bsx_meth_diff::fisher_p((double)s[1], (double)s[2], (double)s[3], (double)s[4]) : __longlong_as_double(0x7ff8000000000000ll);
+    }
+}
+
+// The joint form of k_meth_regions<false, REGION_WAVES>: the same tiles, one wave per tile, the same meeting of a block's waves in LDS; the five sums of an
+// interval are N, MA, DA, MB, DB over its common sites.  No common site without a depth in A: the look-ahead loads are A's.
+template <int REGION_WAVES>
+__global__ __launch_bounds__(REGION_WAVES * 64) void k_meth_diff_regions(MethDev A, MethDev B, RowRule R, const bsx_meth_tiles::Tile *tiles, uint32_t n_tiles,
+                                                                        const uint32_t *iv_chr, const uint32_t *iv_start, u64 *sums)
+{
+    __shared__ u64 s_part[REGION_WAVES][5];
+    __shared__ uint32_t s_iv[REGION_WAVES];  // the interval of the wave's tile where it has to be added, ~0 otherwise
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t t = blockIdx.x * REGION_WAVES + wv;
+    uint32_t shared_iv = ~0u;
+    if (t < n_tiles) {  // (uniform over the wave)
+        const bsx_meth_tiles::Tile T = tiles[t];
+        const uint32_t len = T.len & ~bsx_meth_tiles::SINGLE, c = iv_chr[T.iv];
+        const u64 g0 = A.chr_off[c], n = A.chr_off[c + 1] - g0, k0 = (u64)iv_start[T.iv] + T.off;  // the host has clipped the interval: k0 + len <= n
+        u64 v[5] = {0, 0, 0, 0, 0};
+        for (uint32_t j0 = lane; j0 < len; j0 += 256) {
+            uint32_t ahead[4];
+            for (int q = 0; q < 4; q++) ahead[q] = j0 + 64 * q < len ? A.depth[g0 + k0 + j0 + 64 * q] : 0u;
+            for (int q = 0; q < 4; q++) {
+                if (!ahead[q]) continue;
+                uint32_t dA, mA, dB, mB;
+                if (!diff_site(A, B, g0, n, k0 + j0 + 64 * q, R, dA, mA, dB, mB)) continue;
+                v[0]++; v[1] += mA; v[2] += dA; v[3] += mB; v[4] += dB;
+            }
+        }
+        for (int off = 32; off; off >>= 1) for (int q = 0; q < 5; q++) v[q] += __shfl_down(v[q], off);
+        if (lane == 0) {
+            if (T.len & bsx_meth_tiles::SINGLE) { u64 *out = sums + (u64)T.iv * 5; for (int q = 0; q < 5; q++) out[q] = v[q]; }
+            else { shared_iv = T.iv; for (int q = 0; q < 5; q++) s_part[wv][q] = v[q]; }
+        }
+    }
+    if (lane == 0) s_iv[wv] = shared_iv;
+    __syncthreads();
+    if (lane != 0 || shared_iv == ~0u || (wv > 0 && s_iv[wv - 1] == shared_iv)) return;  // the first wave of a run of tiles of one interval goes on
+    u64 tot[5] = {0, 0, 0, 0, 0};
+    for (int w = wv; w < REGION_WAVES && s_iv[w] == shared_iv; w++) for (int q = 0; q < 5; q++) tot[q] += s_part[w][q];
+    if (!tot[0]) return;
+    u64 *out = sums + (u64)shared_iv * 5;
+    for (int q = 0; q < 5; q++) atomicAdd(&out[q], tot[q]);
+}
+
 }  // namespace
 
 enum Count { CNT_VALID, CNT_NC, CNT_ND, CNT_DROPPED, CNT_CELLS = 8 };  // d_counts: valid alignments, the nc and nd of the last table report, alignments the non-conversion filter dropped
@@ -910,6 +1020,12 @@ struct bsx_meth {
     // of the last bsx_meth_epi_report_chr: pos[rows][4], counts[rows][16]
     DevBuf<uint32_t> d_epi_out[2];
     uint32_t epi_last_rows = 0;
+    // of the last bsx_meth_diff_report_chr with this handle as sample A: pos, counts[rows][4] (mA, dA, mB, dB), context class and strand, p
+    DevBuf<uint32_t> d_diff_pos;
+    DevBuf<uint4> d_diff_counts;
+    DevBuf<uint8_t> d_diff_cls;
+    DevBuf<double> d_diff_p;
+    uint32_t diff_last_rows = 0;
     std::vector<std::string> names;  // filled by bsx_meth_create_from_fasta
     MethDev dev() const { MethDev M; M.ref = d_ref.p; M.chr_off = d_chr_off.p; M.depth = d_depth.p; M.meth = d_meth.p; M.first = d_first.p; M.total = chr_off.back(); M.n_chr = n_chr; return M; }
 };
@@ -1631,7 +1747,10 @@ static constexpr size_t REGION_CHUNK = (size_t)1 << 22;  // a launch takes inter
 
 extern "C" uint32_t bsx_meth_region_tile(void) { return bsx_meth_tiles::TILE; }
 
-static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums)
+// The host side of every interval kernel: clip, cut into launches and tiles, zero the sums, launch, copy back.  `launch(wide, tiles, n_tiles, iv_chr,
+// iv_start, sums)` starts the kernel on m's stream: with blocks of 16 waves where `wide` says that the launch is mostly long intervals, of 4 otherwise.
+template <class Launch>
+static int meth_tiled(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint64_t *sums, Launch launch)
 {
     std::vector<uint32_t> cs(n), ce(n);  // the clipped intervals
     for (uint32_t i = 0; i < n; i++) {
@@ -1659,8 +1778,6 @@ static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint
         d_sums.reserve(max_iv * 40) != hipSuccess) {
         g_bsx_err = "bsx_meth_regions: no device memory for the intervals"; return BSX_ERR_NOMEM;
     }
-    const MethDev M = m->dev();
-    const RowRule R{min_depth, m->ctx_mask, 1, m->snp};
     std::vector<bsx_meth_tiles::Tile> tiles;
     for (size_t q = 0; q + 1 < cut_at.size(); q++) {
         const uint32_t a = cut_at[q], b = cut_at[q + 1];
@@ -1674,17 +1791,24 @@ static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint
             const uint32_t nt = (uint32_t)tiles.size();
             size_t in_long = 0;  // tiles of intervals of 64 tiles and more
             for (uint32_t i = a; i < b; i++) { const size_t k = (size_t)bsx_meth_tiles::n_tiles(ce[i] - cs[i]); if (k >= 64) in_long += k; }
-            const bool wide = 2 * in_long > nt;
-            const unsigned waves = wide ? 16 : 4;
-            auto kernel = m->snp ? (wide ? k_meth_regions<true, 16> : k_meth_regions<true, 4>) : (wide ? k_meth_regions<false, 16> : k_meth_regions<false, 4>);
-            hipLaunchKernelGGL(kernel, dim3((nt + waves - 1) / waves), dim3(waves * 64), 0, m->stream, M, R, (const u64 *)m->d_rev.p, (const bsx_meth_tiles::Tile *)d_tiles.p, nt,
-                               (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, d_sums.p);
+            launch(2 * in_long > nt, (const bsx_meth_tiles::Tile *)d_tiles.p, nt, (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, d_sums.p);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(sums + (size_t)a * 5, d_sums.p, (size_t)(b - a) * 40, hipMemcpyDeviceToHost, m->stream));
         HIP_TRY(hipStreamSynchronize(m->stream));  // (the host vectors are reused by the next launch)
     }
     return BSX_OK;
+}
+
+static int meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums)
+{
+    const MethDev M = m->dev();
+    const RowRule R{min_depth, m->ctx_mask, 1, m->snp};
+    return meth_tiled(m, n, chr, start, end, sums, [&](bool wide, const bsx_meth_tiles::Tile *tiles, uint32_t nt, const uint32_t *iv_chr, const uint32_t *iv_start, u64 *d_sums) {
+        const unsigned waves = wide ? 16 : 4;
+        auto kernel = m->snp ? (wide ? k_meth_regions<true, 16> : k_meth_regions<true, 4>) : (wide ? k_meth_regions<false, 16> : k_meth_regions<false, 4>);
+        hipLaunchKernelGGL(kernel, dim3((nt + waves - 1) / waves), dim3(waves * 64), 0, m->stream, M, R, (const u64 *)m->d_rev.p, tiles, nt, iv_chr, iv_start, d_sums);
+    });
 }
 
 extern "C" int bsx_meth_regions(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums)
@@ -1744,20 +1868,26 @@ int write_wig(bsx_meth *m, const char *path, uint32_t bin, uint32_t min_depth)
     return out.finish();
 }
 
+// the records of a BED file on the handle's sequences, under the rules of bsx_meth_write_regions
+int read_bed(bsx_meth *m, const char *bed_path, bsx_meth_parse::BedRecords &bed)
+{
+    Mapping map;
+    const int rc_open = map.open(bed_path);
+    if (rc_open != BSX_OK) return rc_open;
+    std::unordered_map<std::string, uint32_t> cid;
+    std::vector<bsx_meth_parse::u64> lens;
+    for (uint32_t c = 0; c < m->n_chr; c++) { cid.emplace(m->names[c], c); lens.push_back(m->chr_off[c + 1] - m->chr_off[c]); }
+    const u64 bad = map.len ? bsx_meth_parse::parse_bed(map.base, map.len, cid, lens, bed) : 0;
+    if (bad) { g_bsx_err = std::string(bed_path) + ": line " + std::to_string(bad) + ": not a BED record (name, start <= end as numbers)"; return BSX_ERR_IO; }
+    if (bed.chr.size() > 0xffffffffull) { g_bsx_err = std::string(bed_path) + ": more than 2^32 - 1 records"; return BSX_ERR_LIMIT; }
+    return BSX_OK;
+}
+
 int write_regions(bsx_meth *m, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
 {
     bsx_meth_parse::BedRecords bed;
-    {
-        Mapping map;
-        const int rc_open = map.open(bed_path);
-        if (rc_open != BSX_OK) return rc_open;
-        std::unordered_map<std::string, uint32_t> cid;
-        std::vector<bsx_meth_parse::u64> lens;
-        for (uint32_t c = 0; c < m->n_chr; c++) { cid.emplace(m->names[c], c); lens.push_back(m->chr_off[c + 1] - m->chr_off[c]); }
-        const u64 bad = map.len ? bsx_meth_parse::parse_bed(map.base, map.len, cid, lens, bed) : 0;
-        if (bad) { g_bsx_err = std::string(bed_path) + ": line " + std::to_string(bad) + ": not a BED record (name, start <= end as numbers)"; return BSX_ERR_IO; }
-    }
-    if (bed.chr.size() > 0xffffffffull) { g_bsx_err = std::string(bed_path) + ": more than 2^32 - 1 records"; return BSX_ERR_LIMIT; }
+    const int rc_bed = read_bed(m, bed_path, bed);
+    if (rc_bed) return rc_bed;
     const size_t n = bed.chr.size();
     std::vector<uint64_t> sums(n * 5 + 1);
     const int rc = bsx_meth_regions(m, (uint32_t)n, bed.chr.data(), bed.start.data(), bed.end.data(), min_depth, sums.data());
@@ -1857,4 +1987,216 @@ extern "C" int bsx_meth_write_regions(bsx_meth *m, const char *bed_path, const c
     if (n_written) *n_written = 0;
     if (n_dropped) *n_dropped = 0;
     return guarded(out_path, "writing", [&] { return write_regions(m, bed_path, out_path, min_depth, n_written, n_dropped); });
+}
+
+// ---- two samples: differential methylation ----
+// What every diff call checks first: two handles on one device over sequences of the same lengths, the C/T-SNP mode off in both, one context mask.  On
+// BSX_OK the device is current and B's stream has been waited for: the kernels run on A's stream and read B's counters.
+static int diff_pair(bsx_meth *a, bsx_meth *b)
+{
+    if (!a || !b || a->device != b->device || a->n_chr != b->n_chr || a->chr_off != b->chr_off) return BSX_ERR_ARG;
+    if (a->snp || b->snp) { g_bsx_err = "a diff call needs the C/T-SNP mode off in both handles (bsx_meth_set_ct_snp)"; return BSX_ERR_STATE; }
+    if (a->ctx_mask != b->ctx_mask) return BSX_ERR_ARG;
+    HIP_TRY(hipSetDevice(a->device));
+    if (b != a) HIP_TRY(hipStreamSynchronize(b->stream));
+    return BSX_OK;
+}
+
+// B's counters under A's letters and offsets
+static MethDev diff_dev_b(const bsx_meth *a, const bsx_meth *b)
+{
+    MethDev B = a->dev();
+    B.depth = b->d_depth.p; B.meth = b->d_meth.p; B.first = nullptr;
+    return B;
+}
+
+// p[n] of n rows or interval sums that lie on the device (k_meth_fisher), on m's stream
+static void diff_fisher(bsx_meth *m, const uint4 *rows4, const u64 *sums5, size_t n, double *d_p)
+{
+    hipLaunchKernelGGL(k_meth_fisher, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, rows4, sums5, (u64)n, d_p);
+}
+
+extern "C" int bsx_meth_diff_report_chr(bsx_meth *a, bsx_meth *b, uint32_t chr, uint32_t min_depth, uint32_t min_delta_permille, uint32_t *n_rows)
+{
+    if (!a || !b || !n_rows || chr >= a->n_chr || min_delta_permille > 1000) return BSX_ERR_ARG;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    const u64 g0 = a->chr_off[chr], n = a->chr_off[chr + 1] - g0;
+    const MethDev A = a->dev(), B = diff_dev_b(a, b);
+    const RowRule R{min_depth, a->ctx_mask, 1, 0};
+    size_t n_out = 0;
+    return meth_compact(a, n, n_rows, a->diff_last_rows,
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_diff_count, dim3(nblk), dim3(256), 0, a->stream, A, B, g0, n, R, min_delta_permille, a->d_blk.p); },
+        [&](size_t rows) -> int {
+            HIP_TRY(a->d_diff_pos.reserve(rows * 4)); HIP_TRY(a->d_diff_counts.reserve(rows * 16)); HIP_TRY(a->d_diff_cls.reserve(rows)); HIP_TRY(a->d_diff_p.reserve(rows * 8));
+            n_out = rows;
+            return BSX_OK;
+        },
+        [&](unsigned nblk) {  // the rows, then on the same stream p of every row
+            hipLaunchKernelGGL(k_diff_emit, dim3(nblk), dim3(256), 0, a->stream, A, B, g0, n, R, min_delta_permille, (const uint32_t *)a->d_blk_start.p, a->d_diff_pos.p,
+                               a->d_diff_counts.p, a->d_diff_cls.p);
+            diff_fisher(a, a->d_diff_counts.p, nullptr, n_out, a->d_diff_p.p);
+        });
+}
+
+extern "C" int bsx_meth_diff_fetch_rows(bsx_meth *a, uint32_t *pos0, uint32_t *counts, double *p)
+{
+    if (!a || !pos0 || !counts || !p) return BSX_ERR_ARG;
+    HIP_TRY(hipSetDevice(a->device));
+    const size_t rows = a->diff_last_rows;
+    if (!rows) return BSX_OK;
+    HIP_TRY(hipMemcpy(pos0, a->d_diff_pos.p, rows * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, a->d_diff_counts.p, rows * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(p, a->d_diff_p.p, rows * 8, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// sums[n][5] and p[n] of n intervals; the sums come back through meth_tiled, p is computed from them on the device in pieces of REGION_CHUNK
+static int diff_regions(bsx_meth *a, bsx_meth *b, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums, double *p)
+{
+    const MethDev A = a->dev(), B = diff_dev_b(a, b);
+    const RowRule R{min_depth, a->ctx_mask, 1, 0};
+    const int rc = meth_tiled(a, n, chr, start, end, sums, [&](bool wide, const bsx_meth_tiles::Tile *tiles, uint32_t nt, const uint32_t *iv_chr, const uint32_t *iv_start, u64 *d_sums) {
+        if (wide) hipLaunchKernelGGL(k_meth_diff_regions<16>, dim3((nt + 15) / 16), dim3(1024), 0, a->stream, A, B, R, tiles, nt, iv_chr, iv_start, d_sums);
+        else hipLaunchKernelGGL(k_meth_diff_regions<4>, dim3((nt + 3) / 4), dim3(256), 0, a->stream, A, B, R, tiles, nt, iv_chr, iv_start, d_sums);
+    });
+    if (rc) return rc;
+    DevBuf<u64> d_sums;
+    DevBuf<double> d_p;
+    const size_t piece = std::min<size_t>(n, REGION_CHUNK);
+    if (d_sums.reserve(piece * 40) != hipSuccess || d_p.reserve(piece * 8) != hipSuccess) { g_bsx_err = "bsx_meth_diff_regions: no device memory for the intervals"; return BSX_ERR_NOMEM; }
+    for (size_t lo = 0; lo < n; lo += piece) {
+        const size_t k = std::min(piece, (size_t)n - lo);
+        HIP_TRY(hipMemcpyAsync(d_sums.p, sums + lo * 5, k * 40, hipMemcpyHostToDevice, a->stream));
+        diff_fisher(a, nullptr, d_sums.p, k, d_p.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(p + lo, d_p.p, k * 8, hipMemcpyDeviceToHost, a->stream));
+        HIP_TRY(hipStreamSynchronize(a->stream));
+    }
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_diff_regions(bsx_meth *a, bsx_meth *b, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums,
+                                     double *p)
+{
+    if (!a || !b || (n && (!chr || !start || !end || !sums || !p))) return BSX_ERR_ARG;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair || !n) return rc_pair;
+    try {
+        return diff_regions(a, b, n, chr, start, end, min_depth, sums, p);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = "bsx_meth_diff_regions: out of host memory"; return BSX_ERR_NOMEM;
+    }
+}
+
+namespace {
+
+int write_diff(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, uint64_t *n_rows)
+{
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs(bsx_meth_diff::POS_HEADER, out.f);
+    std::vector<uint32_t> pos, counts;
+    std::vector<uint8_t> cls;
+    std::vector<double> p;
+    uint64_t total = 0;
+    for (const uint32_t c : sorted_chromosomes(a)) {
+        uint32_t rows = 0;
+        int rc = bsx_meth_diff_report_chr(a, b, c, min_depth, min_delta_permille, &rows);
+        if (rc) return rc;
+        if (!rows) continue;
+        pos.resize(rows); counts.resize((size_t)rows * 4); cls.resize(rows); p.resize(rows);
+        rc = bsx_meth_diff_fetch_rows(a, pos.data(), counts.data(), p.data());
+        if (rc) return rc;
+        if (hipMemcpy(cls.data(), a->d_diff_cls.p, rows, hipMemcpyDeviceToHost) != hipSuccess) return BSX_ERR_DEVICE;
+        const char *name = a->names[c].c_str();
+        format_rows(out.f, rows, 72, [&](size_t i, std::string &o) { if (!max_p || p[i] <= *max_p) bsx_meth_diff::append_pos_row(o, name, pos[i], cls[i], &counts[i * 4], p[i]); });
+        for (size_t i = 0; i < rows; i++) total += !max_p || p[i] <= *max_p;
+    }
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
+    if (n_rows) *n_rows = total;
+    return BSX_OK;
+}
+
+int write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
+{
+    bsx_meth_parse::BedRecords bed;
+    const int rc_bed = read_bed(a, bed_path, bed);
+    if (rc_bed) return rc_bed;
+    const size_t n = bed.chr.size();
+    std::vector<uint64_t> sums(n * 5 + 1);
+    std::vector<double> p(n + 1);
+    const int rc = bsx_meth_diff_regions(a, b, (uint32_t)n, bed.chr.data(), bed.start.data(), bed.end.data(), min_depth, sums.data(), p.data());
+    if (rc) return rc;
+    OutFile out(out_path);
+    if (!out.f) return out.cannot_write();
+    fputs(bsx_meth_diff::REGION_HEADER, out.f);
+    format_rows(out.f, n, 80, [&](size_t i, std::string &o) {
+        bsx_meth_diff::append_interval_row(o, a->names[bed.chr[i]].c_str(), bed.start[i], bed.end[i], &bed.label[i], &sums[i * 5], p[i]);
+    });
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
+    if (n_written) *n_written = n;
+    if (n_dropped) *n_dropped = bed.dropped;
+    return BSX_OK;
+}
+
+// the bins of every sequence as intervals [j bin, min((j + 1) bin, length)) of bsx_meth_diff_regions, REGION_CHUNK of them per call
+int write_diff_bins(bsx_meth *a, bsx_meth *b, const char *path, uint32_t bin, uint32_t min_depth, uint64_t *n_rows)
+{
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs(bsx_meth_diff::BIN_HEADER, out.f);
+    std::vector<uint32_t> chr, start, end;
+    std::vector<uint64_t> sums;
+    std::vector<double> p;
+    uint64_t total = 0;
+    for (const uint32_t c : sorted_chromosomes(a)) {
+        const u64 len = a->chr_off[c + 1] - a->chr_off[c], n_bins = (len + bin - 1) / bin;
+        const char *name = a->names[c].c_str();
+        for (u64 j0 = 0; j0 < n_bins; j0 += REGION_CHUNK) {
+            const size_t k = (size_t)std::min<u64>(REGION_CHUNK, n_bins - j0);
+            chr.assign(k, c); start.resize(k); end.resize(k); sums.resize(k * 5); p.resize(k);
+            for (size_t j = 0; j < k; j++) { start[j] = (uint32_t)((j0 + j) * bin); end[j] = (uint32_t)std::min<u64>((j0 + j + 1) * bin, len); }
+            const int rc = bsx_meth_diff_regions(a, b, (uint32_t)k, chr.data(), start.data(), end.data(), min_depth, sums.data(), p.data());
+            if (rc) return rc;
+            format_rows(out.f, k, 16, [&](size_t j, std::string &o) { if (sums[j * 5]) bsx_meth_diff::append_interval_row(o, name, start[j], end[j], nullptr, &sums[j * 5], p[j]); });
+            for (size_t j = 0; j < k; j++) total += sums[j * 5] != 0;
+        }
+    }
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
+    if (n_rows) *n_rows = total;
+    return BSX_OK;
+}
+
+}  // namespace
+
+extern "C" int bsx_meth_write_diff(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, uint64_t *n_rows)
+{
+    if (!a || !b || !path || min_delta_permille > 1000 || a->names.size() != a->n_chr) return BSX_ERR_ARG;
+    if (n_rows) *n_rows = 0;
+    const int rc_pair = diff_pair(a, b);  // ahead of the file: a pair that cannot be compared leaves nothing behind
+    if (rc_pair) return rc_pair;
+    return guarded(path, "writing", [&] { return write_diff(a, b, path, min_depth, min_delta_permille, max_p, n_rows); });
+}
+
+extern "C" int bsx_meth_write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
+{
+    if (!a || !b || !bed_path || !out_path || a->names.size() != a->n_chr) return BSX_ERR_ARG;
+    if (n_written) *n_written = 0;
+    if (n_dropped) *n_dropped = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    return guarded(out_path, "writing", [&] { return write_diff_regions(a, b, bed_path, out_path, min_depth, n_written, n_dropped); });
+}
+
+extern "C" int bsx_meth_write_diff_bins(bsx_meth *a, bsx_meth *b, const char *path, uint32_t bin, uint32_t min_depth, uint64_t *n_rows)
+{
+    if (!a || !b || !path || !bin || a->names.size() != a->n_chr) return BSX_ERR_ARG;
+    if (n_rows) *n_rows = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    return guarded(path, "writing", [&] { return write_diff_bins(a, b, path, bin, min_depth, n_rows); });
 }

@@ -87,6 +87,12 @@ PROTOTYPES = {
     "bsx_meth_epi_report_chr": (_I32, [_VP, _U32, _U32, _VP]),
     "bsx_meth_epi_fetch_rows": (_I32, [_VP, _VP, _VP]),
     "bsx_meth_write_epi": (_I32, [_VP, _STR, _U32, _VP]),
+    "bsx_meth_diff_report_chr": (_I32, [_VP, _VP, _U32, _U32, _U32, _VP]),
+    "bsx_meth_diff_fetch_rows": (_I32, [_VP, _VP, _VP, _VP]),
+    "bsx_meth_write_diff": (_I32, [_VP, _VP, _STR, _U32, _U32, _VP, _VP]),
+    "bsx_meth_diff_regions": (_I32, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP]),
+    "bsx_meth_write_diff_regions": (_I32, [_VP, _VP, _STR, _STR, _U32, _VP, _VP]),
+    "bsx_meth_write_diff_bins": (_I32, [_VP, _VP, _STR, _U32, _U32, _VP]),
 }
 _path = os.fsencode  # str or os.PathLike -> the bytes of a const char *path
 
@@ -299,6 +305,49 @@ class Meth:
         h, nw, nd = self._live(), C.c_uint64(), C.c_uint64()
         _check(self.L.bsx_meth_write_regions(h, _path(bed_path), _path(out_path), min_depth, C.byref(nw), C.byref(nd)))
         return nw.value, nd.value
+
+    # ---- two samples: self is sample A, other sample B; no call changes a counter of either ----
+    def _pair(self, other):
+        """(A's handle, B's handle): self is checked first, then other"""
+        h = self._live()
+        return h, other._live()
+
+    def diff_report(self, other, c, min_depth=1, min_delta_permille=0):
+        """the common sites of sequence c whose ratios differ by min_delta_permille / 1000 or more: (pos0 uint32, counts uint32 [rows][4] = mA, dA, mB, dB,
+        p float64: the two-sided Fisher exact test of every row)"""
+        (h, hb), nr = self._pair(other), C.c_uint32()
+        _check(self.L.bsx_meth_diff_report_chr(h, hb, c, min_depth, min_delta_permille, C.byref(nr)))
+        pos0, counts, p = np.zeros(nr.value, np.uint32), np.zeros((nr.value, 4), np.uint32), np.zeros(nr.value, np.float64)
+        _check(self.L.bsx_meth_diff_fetch_rows(h, pos0.ctypes.data, counts.ctypes.data, p.ctypes.data))
+        return pos0, counts, p
+
+    def diff_regions(self, other, chr, start, end, min_depth=1):
+        """(sums uint64 [len(chr)][5] = N, MA, DA, MB, DB over the common sites of every interval, p float64: the test on the sums, NaN where N is 0)"""
+        h, hb = self._pair(other)
+        a = [np.ascontiguousarray(x, np.uint32) for x in (chr, start, end)]
+        if not a[0].size == a[1].size == a[2].size:
+            raise ValueError("chr, start and end differ in length")
+        sums, p = np.zeros((a[0].size, 5), np.uint64), np.zeros(a[0].size, np.float64)
+        _check(self.L.bsx_meth_diff_regions(h, hb, a[0].size, *[x.ctypes.data for x in a], min_depth, sums.ctypes.data, p.ctypes.data))
+        return sums, p
+
+    def write_diff(self, other, path, min_depth=1, min_delta_permille=0, max_p=None):
+        """the rows of every sequence in sorted name order, with max_p those with p <= max_p; returns the rows written"""
+        (h, hb), n = self._pair(other), C.c_uint64()
+        _check(self.L.bsx_meth_write_diff(h, hb, _path(path), min_depth, min_delta_permille, None if max_p is None else C.byref(C.c_double(max_p)), C.byref(n)))
+        return n.value
+
+    def write_diff_regions(self, other, bed_path, out_path, min_depth=1):
+        """one row per interval of a BED file; returns (intervals written, intervals dropped: on sequences that are not loaded)"""
+        (h, hb), nw, nd = self._pair(other), C.c_uint64(), C.c_uint64()
+        _check(self.L.bsx_meth_write_diff_regions(h, hb, _path(bed_path), _path(out_path), min_depth, C.byref(nw), C.byref(nd)))
+        return nw.value, nd.value
+
+    def write_diff_bins(self, other, path, width, min_depth=1):
+        """one row per bin of `width` positions that holds a common site; returns the rows written"""
+        (h, hb), n = self._pair(other), C.c_uint64()
+        _check(self.L.bsx_meth_write_diff_bins(h, hb, _path(path), width, min_depth, C.byref(n)))
+        return n.value
 
 
 def load_reference(path, chroms):

@@ -498,6 +498,39 @@ int bsx_meth_epi_fetch_rows(bsx_meth *m, uint32_t *pos0, uint32_t *counts);
  * without rows is the header alone.  Needs a handle that knows its names, else BSX_ERR_ARG; n_rows may be NULL. */
 int bsx_meth_write_epi(bsx_meth *m, const char *path, uint32_t min_reads, uint64_t *n_rows);
 
+/* Differential methylation of two samples (an extension).  A and B are two handles on the same device with the same number of sequences and
+ * the same length of each (BSX_ERR_ARG otherwise), both with the C/T-SNP mode off (BSX_ERR_STATE otherwise) and with the same context mask (BSX_ERR_ARG
+ * otherwise); a == b is allowed.  The letters and the names are A's.  The calls change no counter of either handle and may be made any number of times,
+ * before or after bsx_meth_combine_cpg and the table; a process that never makes them runs what it ran without them.
+ *
+ * Position k is a COMMON SITE when the row rule of bsx_meth_report_chr (min_depth of the call, the context filter) holds for it in A and in B and its raw
+ * depth is above 0 in both; its counts are mA, dA, mB, dB (methylated, depth; m <= d).  p is the two-sided Fisher exact test of [[mA, dA - mA], [mB, dB - mB]]
+ * with R's rule for ties: over x in [max(0, mA + mB - dB), min(dA, mA + mB)] with w(x) = C(dA, x) C(dB, mA + mB - x),
+ * p = sum{w(x) : w(x) <= w(mA) (1 + 1e-7)} / sum w(x), in double precision by the ratio recurrence from the mode (csrc/bsx_meth_diff.h: no lgamma, no
+ * floating-point atomics; two calls give the same bits, a support of one table gives exactly 1.0; relative error at most 64 (s + 16) 2^-53 for a support
+ * of s tables while p >= 1e-290, and a result in [0, 1e-289] below that).  Per interval five uint64 sums over its common sites: N, MA, DA, MB, DB, and p is
+ * the same test on the four sums taken as doubles, NaN where N == 0.
+ *
+ * Rows of one sequence in position order: the common sites with |mA dB - mB dA| 1000 >= min_delta_permille dA dB (compared as 128-bit integers; 0 keeps
+ * every common site, above 1000 is BSX_ERR_ARG).  The row buffers are A's own: the rows of A's other reports stay fetchable. */
+int bsx_meth_diff_report_chr(bsx_meth *a, bsx_meth *b, uint32_t chr, uint32_t min_depth, uint32_t min_delta_permille, uint32_t *n_rows);
+/* the rows of the last diff_report_chr with `a` as sample A: 0-based positions, counts[n_rows][4] = mA, dA, mB, dB, and p[n_rows] */
+int bsx_meth_diff_fetch_rows(bsx_meth *a, uint32_t *pos0, uint32_t *counts, double *p);
+/* The rows of every sequence in sorted name order (the table's) as a tab-separated file: header "chr pos strand context C_a CT_a ratio_a C_b CT_b ratio_b
+ * delta p"; the 1-based position, "+" over a C and "-" over a G, the context class (CG CHG CHH CN), the counts, the ratios (double)m / d as "%.3f",
+ * delta = ratio_b - ratio_a as "%+.3f" and p as "%.4e".  max_p == NULL: every row; otherwise the writer lists the rows with p <= *max_p (the report and
+ * the fetch always give every row).  n_rows (may be NULL): the rows written.  Needs a handle `a` that knows its names, else BSX_ERR_ARG. */
+int bsx_meth_write_diff(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, uint64_t *n_rows);
+/* n intervals under the coordinate rules of bsx_meth_regions (clipping, BSX_ERR_ARG cases, n == 0); sums[n][5] = N, MA, DA, MB, DB and p[n] */
+int bsx_meth_diff_regions(bsx_meth *a, bsx_meth *b, uint32_t n, const uint32_t *chr, const uint32_t *start, const uint32_t *end, uint32_t min_depth, uint64_t *sums,
+                          double *p);
+/* The intervals of a BED file, under the BED rules and the error behaviour of bsx_meth_write_regions, in the file's order: header "chr start end name n_C
+ * C_a CT_a ratio_a C_b CT_b ratio_b delta p", the numbers formatted as in bsx_meth_write_diff; a record without a common site is "0 0 0 NA 0 0 NA NA NA". */
+int bsx_meth_write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped);
+/* The bins [j bin, min((j + 1) bin, length)) of every sequence in sorted name order, as intervals of bsx_meth_diff_regions: the same columns without
+ * "name", and only the bins with N > 0; n_rows (may be NULL): the bins written.  bin == 0 is BSX_ERR_ARG. */
+int bsx_meth_write_diff_bins(bsx_meth *a, bsx_meth *b, const char *path, uint32_t bin, uint32_t min_depth, uint64_t *n_rows);
+
 #ifdef __cplusplus
 }
 #endif

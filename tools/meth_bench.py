@@ -9,8 +9,12 @@ reference letter, reverse calls in the pile-up, the SNP tests in the report).  `
 totals and the PDR rows.  (The reads here keep 30 % of ALL their cytosines, whatever the context: nearly every read has three methylated non-CpG calls, so
 `--nonconv-filter 3` drops nearly all of them and the pile-up behind it has little left to do; a threshold such as 40 drops nearly none.)  `--epi` turns the
 epiallele tally on (k_meth_epi behind the per-read pass: DESIGN §3.11) and times the build of the CpG index (bsx_meth_n_cpg on the whole reference, ahead of
-the first add) and bsx_meth_epi_report_chr over all chromosomes; the JSON line then carries the CpGs and the epiallele rows.
-usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--epi] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
+the first add) and bsx_meth_epi_report_chr over all chromosomes; the JSON line then carries the CpGs and the epiallele rows.  `--diff` makes a second handle
+over the same reference, fed the same alignments converted under another seed (sample B), and times bsx_meth_diff_report_chr over all chromosomes (with
+`--diff-delta PERMILLE` as its filter) and, for every `--regions` entry, bsx_meth_diff_regions on the same intervals right behind bsx_meth_regions (DESIGN
+§3.12): in a kernel trace of the run k_diff_count / k_diff_emit / k_meth_fisher stand beside k_meth_count / k_meth_emit, and k_meth_diff_regions beside
+k_meth_regions; the JSON line carries the rows and the host-side times.  (Not with --ct-snp: a diff call needs the mode off.)
+usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--epi] [--diff] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,7 +36,11 @@ def main():
     ap.add_argument("--pdr", dest="pdr", action="store_true")
     ap.add_argument("--pdr-min-cpg", dest="pdr_min_cpg", type=int, default=4)
     ap.add_argument("--epi", dest="epi", action="store_true")
+    ap.add_argument("--diff", dest="diff", action="store_true")
+    ap.add_argument("--diff-delta", dest="diff_delta", type=int, default=0)
     a = ap.parse_args()
+    if a.diff and a.ct_snp != "no-action":
+        ap.error("--diff needs the C/T-SNP mode off")
     rng = np.random.default_rng(1)
     lens = np.array([int(x * a.genome) for x in (248956422, 242193529, 198295559, 190214555, 181538259, 170805979, 159345973, 145138636, 138394717, 133797422,
                                                 135086622, 133275309, 114364328, 107043718, 101991189, 90338345, 83257441, 80373285, 58617616, 64444167,
@@ -73,10 +81,21 @@ def main():
         seq[sel] = chunks[c][idx]
     conv = rng.random((n, ln)) < 0.7  # unmethylated fraction
     plus = (strand & 1) == 0
+    seq_b = seq.copy() if a.diff else None   # sample B: the same reads, converted under another seed
     seq[plus[:, None] & (seq == ord("C")) & conv] = ord("T")
     seq[(~plus)[:, None] & (seq == ord("G")) & conv] = ord("A")
     ins = np.zeros(n, np.int32); cut = np.full(n, -1, np.int64)
     off = (np.arange(n + 1, dtype=np.uint64) * ln)
+    mb = None
+    if a.diff:
+        conv = np.random.default_rng(2).random((n, ln)) < 0.5
+        seq_b[plus[:, None] & (seq_b == ord("C")) & conv] = ord("T")
+        seq_b[(~plus)[:, None] & (seq_b == ord("G")) & conv] = ord("A")
+        mb = MR.Meth.from_lengths(lens, rm_dup=True)
+        for c in (0, 1):   # the alignments lie on the first two chromosomes: B's pile-up reads no other letters, and the diff calls read A's
+            mb.set_reference(c, chunks[c])
+        mb.add_arrays(n, chr_, pos, strand, ins, cut, seq_b, off, 2)
+        del seq_b, conv
     m.add_arrays(min(n, 1 << 20), chr_, pos, strand, ins, cut, seq, off, 2)
     t0 = time.perf_counter()
     m.add_arrays(n, chr_, pos, strand, ins, cut, seq, off, 2)   # every array has its type already: passed as it is
@@ -106,6 +125,13 @@ def main():
             B._check(L.bsx_meth_epi_report_chr(h, c, 1, C.byref(nr)))
             epi_rows += nr.value
         extra.update(epi_rows=epi_rows, epi_report_s_all_chromosomes=round(time.perf_counter() - t6, 3))
+    if a.diff:
+        t7, diff_rows = time.perf_counter(), 0
+        for c in range(len(lens)):
+            nr = C.c_uint32()
+            B._check(L.bsx_meth_diff_report_chr(h, mb.h, c, 1, a.diff_delta, C.byref(nr)))
+            diff_rows += nr.value
+        extra.update(diff_delta_permille=a.diff_delta, diff_rows=diff_rows, diff_report_s_all_chromosomes=round(time.perf_counter() - t7, 3))
     for width in [int(x) for x in a.wig_bin.split(",") if x]:
         out = np.zeros((int(lens.max()) // width + 1, 5), np.uint64)
         nb, took = C.c_uint64(), []
@@ -130,6 +156,15 @@ def main():
             B._check(L.bsx_meth_regions(h, n_iv, ic.ctypes.data, start.ctypes.data, end.ctypes.data, 1, sums.ctypes.data))
             took.append(round(time.perf_counter() - t3, 3))
         extra.setdefault("regions_s", []).append({"intervals": n_iv, "len": iv_len, "s": took, "sites": int(sums[:, 0].sum())})
+        if a.diff:
+            p, took = np.zeros(n_iv, np.float64), []
+            for _ in range(a.repeat):
+                t8 = time.perf_counter()
+                B._check(L.bsx_meth_diff_regions(h, mb.h, n_iv, ic.ctypes.data, start.ctypes.data, end.ctypes.data, 1, sums.ctypes.data, p.ctypes.data))
+                took.append(round(time.perf_counter() - t8, 3))
+            extra.setdefault("diff_regions_s", []).append({"intervals": n_iv, "len": iv_len, "s": took, "common_sites": int(sums[:, 0].sum())})
+    if mb is not None:
+        mb.close()
     m.close()
     print(json.dumps(dict({"alignments": n, "read_len": ln, "ct_snp": a.ct_snp, "add_s_incl_pcie": round(dt, 3), "alignments_per_s_incl_pcie": round(n / dt),
                            "report_s_all_chromosomes": round(dt_rep, 3), "rows": rows, "covered": cov, "genome_bp": int(lens.sum())}, **extra)))
