@@ -11,8 +11,11 @@
 #include <cstring>
 #include <fstream>
 #include <cmath>
+#include <memory>
+#include <utility>
 #include <vector>
 
+#include "bsx_devbuf.h"
 #include "bsx_internal.h"
 #include "bsx_kernel_args.h"
 
@@ -250,80 +253,142 @@ void bsx_fill_devparams(const bsx_ref *r, DevParams &d)
 // ---------------------------------------------------------------------------------------------------------------
 #define BSX_MAX_GROUPS 8
 #define BSX_POLL_SLOTS 4
+
+// Tuning knobs, diagnostics and test hooks of a batch: environment variables, all read in one place (read_knobs) and ONCE per batch, when it is created — a
+// batch keeps its settings, and what sized its memory is what its kernels are told.  bsx_batch_plan_bytes and bsx_default_heavy_limits read them the same way.
+struct BatchKnobs {
+    uint32_t kcap, heavy_kcap, bin_log2;
+    int n_groups, chunk_passes, hctrl_blocks, same, work_counters;
+    uint32_t xcd_map, tail_tasks, tail_grid_tasks, same_d, same_r, group_tile, group_big, spread;
+    bool spread_set, trace, sig_hist, sector_stats, poison;
+};
+static long knob(const char *name, long dflt, long lo, long hi, bool *set = nullptr)
+{
+    const char *e = getenv(name);
+    if (set) *set = e != nullptr;
+    return e ? std::min(hi, std::max(lo, atol(e))) : dflt;
+}
+static BatchKnobs read_knobs()
+{
+    const long none = 0, any = 0x7fffffffL;
+    BatchKnobs K;
+    // one row per knob — knob(variable, default, lowest, highest) under what it means and what was measured
+    // keys of the main kernel's per-wave duplicate set for single-end RRBS (key_cap): test hook that makes the large set small, to exercise the BSX_F_LIMIT path
+    K.kcap = (uint32_t)knob("BSX_KCAP", 1 << 18, 64, any);
+    // keys of the small set in the slabs of deferred units (heavy_key_cap; 0: by -v and the row length): test hook that makes it overflow, into the redo launch
+    K.heavy_kcap = (uint32_t)knob("BSX_HEAVY_KCAP", none, 64, any);
+    // scan order of a pass: at most 2^this bins of index entries (plan_batch; 0: by mode, 20 for RRBS, 21 for WGBS) — tuning
+    K.bin_log2 = (uint32_t)knob("BSX_BIN_LOG2", none, 8, 21);
+    // unit groups of the heavy pipeline.  1: the control and scan passes of a batch alternate and overlap those of the OTHER batch in flight — measured best
+    // with two batches in flight, C3 131 ms per step against 148 with two groups each; a caller that keeps a single batch in flight gains from 2: 158 against 177 ms
+    K.n_groups = (int)knob("BSX_HEAVY_GROUPS", 1, 1, BSX_MAX_GROUPS);
+    // passes of every open group that the host enqueues per poll
+    K.chunk_passes = (int)knob("BSX_HEAVY_CHUNK", 2, 1, 64);
+    // control blocks per CU (at most what is resident, bsx_hctrl_occupancy): one, although two fit.  A control wave holds half of its SIMD's registers: with two
+    // blocks per CU the scan kernel's waves cannot be resident beside them and the two only alternate; with one, four scan waves per SIMD run beside it
+    // (C3 with two batches in flight 136.5 -> 131.3 ms per step, C4 211 -> 195) — tuning
+    K.hctrl_blocks = (int)knob("BSX_HCTRL_BLOCKS", 1, 1, any);
+    // the scan kernel: k_hscan_same (tasks of one window and read offset share fetch and shift) for WGBS unless 0 (k_hscan: one task per wave), for RRBS only with 2.
+    // RRBS lists through it: scan 75.9 against 90.5 ms per step, but the step does not move — 142.2 against 141.0 ms —, it waits for the control passes there:
+    // k_hscan_shared (runs of tasks over one window, scanned together) stays the default for RRBS
+    K.same = (int)knob("BSX_SAME", 1, -any, any);
+    // the default of bsx_batch_set_work_counters (test hook)
+    K.work_counters = knob("BSX_WORK_COUNTERS", 1, -any, any) != 0;
+    // how k_hscan's blocks map onto the scan order (order_block, bsx_align.hip): 0 as dispatched, 1 one contiguous eighth per XCD, N >= 2 pieces of N blocks dealt to the XCDs in turn
+    K.xcd_map = (uint32_t)knob("BSX_XCD_MAP", 128, 0, any);
+    // a group whose passes publish fewer tasks than this scans them on its control stream (0: no tail mode) ... with a grid for this many tasks — tuning
+    K.tail_tasks = (uint32_t)knob("BSX_TAIL_TASKS", 16384, 0, any);
+    K.tail_grid_tasks = (uint32_t)knob("BSX_TAIL_GRID", 4096, 64, any);
+    // k_hscan_same: offset classes a group spans beyond its first (up to the build's HG_D); tasks a group holds at most (up to the build's HG_R)
+    K.same_d = (uint32_t)knob("BSX_SAME_D", (long)bsx_same_d_max(), 0, (long)bsx_same_d_max());
+    K.same_r = (uint32_t)knob("BSX_SAME_R", (long)bsx_same_r_max(), 1, (long)bsx_same_r_max());
+    // ... groups formed over tiles of this many slots of the scan order (a power of two from 64; 0: the build's HG_TILE), those of this many tasks and more started first (0: the build's HG_BIG)
+    K.group_tile = (uint32_t)knob("BSX_GROUP_TILE", none, 0, 0x7fffffffffffffffL);
+    K.group_big = (uint32_t)knob("BSX_GROUP_BIG", none, 0, 0x7fffffffffffffffL);
+    // how the tasks of one window are dealt over the order bins (bsx_launch_task_order).  Unset: 0 without k_hscan_same, with it 1 (by read offset) or, where a group
+    // can span offset classes (BSX_SAME_D > 0), 2 (by the low bits of the offset: the offsets a group can span go to one bin)
+    K.spread = (uint32_t)knob("BSX_SPREAD", none, -any - 1, any, &K.spread_set);
+    // per-poll trace of the heavy pipeline on stderr; histogram of tasks per identical window (bsx_sig_hist_pass); with a -DBSX_SECTOR_STATS build, distinct
+    // sectors per scan launch; test hook: the recycled memory of the pools is not zero (the suite sets it)
+    K.trace = getenv("BSX_TRACE_HEAVY") != nullptr;
+    K.sig_hist = getenv("BSX_SIGHIST") != nullptr;
+    K.sector_stats = getenv("BSX_SECTOR_STATS") != nullptr;
+    K.poison = getenv("BSX_POISON") != nullptr;
+    return K;
+}
+
 struct bsx_batch {
     bsx_ref *ref = nullptr;
+    BatchKnobs K = {};   // as the environment had them when the batch was created
     int paired = 0, debug = 0, has_qual = 0, leak_exact = 0, work_counters = 1;
     uint32_t n_hist = 0;
-    uint8_t *d_hist_seq[2] = {nullptr, nullptr}, *d_hist_qual[2] = {nullptr, nullptr};
-    uint64_t *d_hist_off[2] = {nullptr, nullptr};
-    uint8_t *d_leak_rec = nullptr;
+    DevBuf<uint8_t> d_hist_seq[2], d_hist_qual[2];
+    DevBuf<uint64_t> d_hist_off[2];
+    DevBuf<uint8_t> d_leak_rec;
     // exact mode: per-position records of the mate streams (k_leak_meta), block summaries, the state before / behind the stream
-    uint16_t *d_leak_meta[2] = {nullptr, nullptr};
-    uint32_t *d_leak_blk = nullptr;   // [4][n_blk]: blkmax mate 0 / 1, blkset mate 0 / 1
+    DevBuf<uint16_t> d_leak_meta[2];
+    DevBuf<uint32_t> d_leak_blk;   // [4][n_blk]: blkmax mate 0 / 1, blkset mate 0 / 1
     uint32_t leak_nblk = 0;
-    uint8_t *d_leak_init = nullptr, *d_leak_final = nullptr;
+    DevBuf<uint8_t> d_leak_init, d_leak_final;
     bool leak_meta_valid = false, leak_has_init = false;
     uint32_t max_units = 0, n_units = 0, first_index = 0;
-    hipStream_t stream = nullptr;
+    DevStream stream;
     // heavy pipeline: unit groups whose passes run out of phase — the scan passes of all groups on `stream`, the control passes of
     // group g on its own high-priority stream, ordered against each other by events on the device (no host read-back per pass)
     struct Group {
-        hipStream_t s_ctrl = nullptr;
-        hipEvent_t ev_ctrl = nullptr, ev_scan = nullptr, ev_poll[BSX_POLL_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
-        uint32_t *d_bins = nullptr, *d_bstart = nullptr, *d_chunk_tot = nullptr, *d_rank = nullptr, *d_order = nullptr, *d_glist = nullptr;
+        DevStream s_ctrl;
+        DevEvent ev_ctrl, ev_scan, ev_poll[BSX_POLL_SLOTS];
+        DevBuf<uint32_t> d_bins, d_bstart, d_chunk_tot, d_rank, d_order, d_glist;   // the group's share of the pools (pool_rows)
     } grp[BSX_MAX_GROUPS];
-    int n_groups = 1, chunk_passes = 2, trace = 0, hctrl_blocks_per_cu = 1;
-    uint32_t tail_tasks = 16384, tail_grid_tasks = 4096;  // a group whose passes publish fewer tasks than tail_tasks scans them with a grid for tail_grid_tasks on its control stream
+    int hctrl_blocks_per_cu = 1;
     uint32_t bin_shift = 0, n_bins = 1;
-    hipEvent_t ev_sync = nullptr, ev_wait = nullptr;
-    std::vector<hipEvent_t> scan_ev;  // pairs of timing events around every k_hscan launch of the last run (pool grows on demand)
+    DevEvent ev_sync, ev_wait;
+    std::vector<DevEvent> scan_ev;  // pairs of timing events around every k_hscan launch of the last run (pool grows on demand)
     size_t scan_ev_used = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t *d_seq[2] = {nullptr, nullptr}, *d_qual[2] = {nullptr, nullptr};
-    uint64_t *d_off[2] = {nullptr, nullptr};
+    DevEvent ev0, ev1;
+    DevBuf<uint8_t> d_seq[2], d_qual[2];
+    DevBuf<uint64_t> d_off[2];
     size_t seq_cap[2] = {0, 0};
-    bsx_hit *d_hits = nullptr;
-    bsx_pair *d_pairs = nullptr;
-    bsx_class_counts *d_cc[2] = {nullptr, nullptr};
-    uint16_t *d_npairs = nullptr;
-    uint8_t *d_scratch = nullptr, *d_dbg = nullptr;
-    uint32_t *d_cycles = nullptr;
-    uint32_t *d_heavy_list = nullptr, *d_heavy_count = nullptr;
-    // heavy pipeline pools
-    uint8_t *d_hstate = nullptr, *d_hslabs = nullptr, *d_htasks = nullptr, *d_htout = nullptr;
-    uint32_t *d_hactive[2] = {nullptr, nullptr}, *d_hcnt = nullptr;  // d_hcnt: per group two ping-pong counter blocks (BSX_HCNT_*: active units, tasks, queue head)
+    DevBuf<bsx_hit> d_hits;
+    DevBuf<bsx_pair> d_pairs;
+    DevBuf<bsx_class_counts> d_cc[2];
+    DevBuf<uint16_t> d_npairs;
+    DevBuf<uint8_t> d_scratch, d_dbg;
+    DevBuf<uint32_t> d_cycles;
+    DevBuf<uint32_t> d_heavy_list, d_heavy_count;
+    // work pools of the heavy pipeline (with the groups' arrays above): sized by the plan, halved until they fit (fit_pools)
+    struct Pools {
+        DevBuf<uint8_t> hstate, hslabs, htasks, htout;
+        DevBuf<uint32_t> hactive[2];
+    } pool;
+    DevBuf<uint32_t> d_hcnt;  // per group two ping-pong counter blocks (BSX_HCNT_*: active units, tasks, queue head)
     uint32_t hcap = 0, task_cap = 0;
-    bool sig_hist = false;    // diagnostics: histogram of tasks per identical window (bsx_sig_hist_pass)
-    bool same_kernel = false;    // the scan kernel is k_hscan_same (WGBS unless BSX_SAME=0, RRBS with BSX_SAME=2): read once, at creation
-    uint32_t same_d = 0;         // ... and its groups span this many offset classes beyond their first (BSX_SAME_D, 0 .. the build's HG_D, which is the default): read with it
-    uint32_t same_r = 0;         // ... and hold this many tasks at most (BSX_SAME_R, 1 .. the build's HG_R, which is the default; 0 until the batch is created: the build's HG_R)
-    uint32_t group_tile = 0;     // ... formed over tiles of this many slots of the scan order (BSX_GROUP_TILE, a power of two from 64; 0: the build's HG_TILE)
-    uint32_t group_big = 0;      // ... of which those of this many tasks and more are started first (BSX_GROUP_BIG; 0: the build's HG_BIG)
-    bool sector_stats = false;   // diagnostics (a build with -DBSX_SECTOR_STATS): distinct sectors per scan launch
-    uint32_t xcd_map = 128;   // order_block (bsx_align.hip): pieces of 128 scan blocks dealt to the XCDs in turn
+    bool same_kernel = false;    // the scan kernel is k_hscan_same (BatchKnobs::same): its group lists exist or not
+    uint32_t spread = 0;         // BatchKnobs::spread, resolved for that kernel
     uint32_t *h_pinned = nullptr;  // pinned host words for the per-pass count read-backs
     int n_cu = 0;
     uint32_t last_heavy = 0, last_heavy_iters = 0, last_redo = 0;
     size_t scratch_bytes = 0;
-    uint32_t *d_queue = nullptr;
-    uint64_t *d_counters = nullptr, *d_scan_stats = nullptr;
+    DevBuf<uint32_t> d_queue;
+    DevBuf<uint64_t> d_counters, d_scan_stats;
     uint64_t slab_bytes = 0, hslab_bytes = 0;
-    uint32_t *d_redo = nullptr;  // [max_units + 1]: count, then unit ids
-    uint32_t rowcap = 0, hkcap = 0;  // hkcap: key capacity of a deferred unit's duplicate set (BSX_HEAVY_KCAP test hook, read at creation)
+    DevBuf<uint32_t> d_redo;  // [max_units + 1]: count, then unit ids
+    uint32_t rowcap = 0, kcap = 0, hkcap = 0;  // keys of a slab's duplicate set: the main kernel's per-wave slabs, those of deferred units (key_cap, heavy_key_cap)
     int grid_blocks = 0;
-    std::vector<hipEvent_t> ctrl_ev;   // per control pass: before k_hctrl, behind it, behind the order kernels (bsx_batch_stage_ms)
+    std::vector<DevEvent> ctrl_ev;   // per control pass: before k_hctrl, behind it, behind the order kernels (bsx_batch_stage_ms)
     size_t ctrl_ev_used = 0;
-    hipEvent_t ev_align = nullptr;     // behind the main kernel (and the exact mode's pre-pass)
+    DevEvent ev_align;                 // behind the main kernel (and the exact mode's pre-pass)
     bool stage_timing = false;         // bsx_batch_set_stage_timing: the events above are only recorded on request (three more per control pass on its stream)
     // all-hits pool (bsx_batch_set_all_hits): null / 0 unless attached
-    uint32_t *d_ah_pool = nullptr;
+    DevBuf<uint32_t> d_ah_pool;
     uint64_t ah_cap = 0;
-    uint64_t *d_ah_ctl = nullptr;      // [0] cursor in words, [1] (low word) dropped units
-    bsx_span *d_ah_spans = nullptr;    // [max_units][3]
+    DevBuf<uint64_t> d_ah_ctl;      // [0] cursor in words, [1] (low word) dropped units
+    DevBuf<bsx_span> d_ah_spans;    // [max_units][3]
     uint32_t run_first = 0, run_units = 0;   // the units of the last run
     bool ah_ran = false;               // a run has filled the attached pool (a pool attached after the run holds nothing yet)
     bool ran = false;
     bool counted = false;        // the batch is in its reference's n_batches
+    ~bsx_batch() { if (h_pinned) (void)hipHostFree(h_pinned); }
 };
 
 // Waiting without burning a CPU.  hipStreamSynchronize busy-waits, and so — measured on this ROCm (tools/driver_cpu.py: thread CPU time =
@@ -342,33 +407,6 @@ static hipError_t wait_event(hipEvent_t ev)
         nanosleep(&ts, nullptr);
     }
 }
-static hipError_t stream_wait(bsx_batch *b);
-
-// duplicate-suppression set of one mate slab (Slab in bsx_align.hip).  WGBS and paired RRBS: every remembered coordinate is a
-// hit, the -w caps bound them.  Single-end RRBS also remembers the coordinates its fragment-size filter rejects
-// (align.cpp:201-207), which nothing caps: a poly-T read of the hg38-sized genome collects thousands — 2^18 keys, 2^19 slots.
-// (BSX_KCAP: test hook that makes the large set of single-end RRBS small, to exercise the BSX_F_LIMIT path)
-static uint32_t key_cap(const bsx_params &p, uint32_t rowcap) { return (p.rrbs && !p.pairend) ? (getenv("BSX_KCAP") ? (uint32_t)std::max(64, atoi(getenv("BSX_KCAP"))) : (1u << 18)) : (uint32_t)(p.max_snp_num + 2) * rowcap; }
-static uint32_t hset_bits(const bsx_params &p) { return (p.rrbs && !p.pairend) ? 19u : (uint32_t)BSX_HSET_BITS; }
-
-// the small set of the heavy pipeline's slabs (BSX_HEAVY_KCAP: test hook that makes it overflow)
-static uint32_t heavy_key_cap(const bsx_params &p, uint32_t rowcap) { return getenv("BSX_HEAVY_KCAP") ? (uint32_t)std::max(64, atoi(getenv("BSX_HEAVY_KCAP"))) : (uint32_t)(p.max_snp_num + 2) * rowcap; }
-
-static uint64_t mate_bytes(const bsx_params &p, uint32_t rowcap, bool heavy = false)
-{
-    const uint64_t rows = (uint64_t)p.max_snp_num + 2;  // nclass + 1 spare row (see Slab in bsx_align.hip)
-    const uint64_t kc = heavy ? heavy_key_cap(p, rowcap) : key_cap(p, rowcap), hb = heavy ? (uint64_t)BSX_HSET_BITS : hset_bits(p);
-    return 2 * rows * rowcap * 8 + 2 * kc * 4 + ((uint64_t)4 << hb) + (uint64_t)BSX_SORT_TMP * 8;
-}
-
-static uint64_t slab_size(const bsx_params &p, int paired, uint32_t rowcap, bool heavy = false)
-{
-    const uint64_t mate = mate_bytes(p, rowcap, heavy);
-    uint64_t s = mate;
-    if (paired) s = 2 * mate + (2 * (uint64_t)p.max_snp_num + 2) * rowcap * 24;
-    return (s + 255) & ~255ull;
-}
-
 static hipError_t stream_wait(bsx_batch *b)
 {
     if (!b->ev_wait) return hipStreamSynchronize(b->stream);
@@ -376,22 +414,100 @@ static hipError_t stream_wait(bsx_batch *b)
     if (e != hipSuccess) return e;
     return wait_event(b->ev_wait);
 }
+// a pool of events that grows on demand and is reused by the next run: at least `need` of them
+static int grow_events(std::vector<DevEvent> &pool, size_t need)
+{
+    while (pool.size() < need) {
+        DevEvent e;
+        HIP_TRY(e.create());
+        pool.push_back(std::move(e));
+    }
+    return BSX_OK;
+}
 
-// What a device batch will allocate, computed on the host from its parameters alone (bsx_batch_plan_bytes: bench.py and the CPU suite
-// check a run's whole plan against the device's memory before anything is allocated; ensure_scratch allocates exactly this).
+// duplicate-suppression set of one mate slab (Slab in bsx_align.hip).  WGBS and paired RRBS: every remembered coordinate is a
+// hit, the -w caps bound them.  Single-end RRBS also remembers the coordinates its fragment-size filter rejects
+// (align.cpp:201-207), which nothing caps: a poly-T read of the hg38-sized genome collects thousands — 2^18 keys (BatchKnobs::kcap), 2^19 slots.
+static uint32_t key_cap(const bsx_params &p, const BatchKnobs &K, uint32_t rowcap) { return (p.rrbs && !p.pairend) ? K.kcap : (uint32_t)(p.max_snp_num + 2) * rowcap; }
+static uint32_t hset_bits(const bsx_params &p) { return (p.rrbs && !p.pairend) ? 19u : (uint32_t)BSX_HSET_BITS; }
+// the small set of the heavy pipeline's slabs
+static uint32_t heavy_key_cap(const bsx_params &p, const BatchKnobs &K, uint32_t rowcap) { return K.heavy_kcap ? K.heavy_kcap : (uint32_t)(p.max_snp_num + 2) * rowcap; }
+
+static uint64_t mate_bytes(const bsx_params &p, uint32_t rowcap, uint64_t kcap, uint64_t hbits)
+{
+    const uint64_t rows = (uint64_t)p.max_snp_num + 2;  // nclass + 1 spare row (see Slab in bsx_align.hip)
+    return 2 * rows * rowcap * 8 + 2 * kcap * 4 + ((uint64_t)4 << hbits) + (uint64_t)BSX_SORT_TMP * 8;
+}
+static uint64_t slab_size(const bsx_params &p, int paired, uint32_t rowcap, uint64_t kcap, uint64_t hbits)
+{
+    const uint64_t mate = mate_bytes(p, rowcap, kcap, hbits);
+    uint64_t s = mate;
+    if (paired) s = 2 * mate + (2 * (uint64_t)p.max_snp_num + 2) * rowcap * 24;
+    return (s + 255) & ~255ull;
+}
+
+// what follows from the parameters, the knobs and the shape of a batch alone (no device): bsx_batch_create, and bsx_batch_plan_bytes on a batch that is never allocated
+static void init_shape(bsx_batch &b, const bsx_params &P, uint32_t max_units, int paired)
+{
+    b.K = read_knobs();
+    b.paired = paired ? 1 : 0; b.max_units = max_units; b.work_counters = b.K.work_counters;
+    b.rowcap = BSX_ROWCAP;
+    b.kcap = key_cap(P, b.K, b.rowcap); b.hkcap = heavy_key_cap(P, b.K, b.rowcap);
+    b.slab_bytes = slab_size(P, b.paired, b.rowcap, b.kcap, hset_bits(P));
+    b.hslab_bytes = slab_size(P, b.paired, b.rowcap, b.hkcap, BSX_HSET_BITS);
+    b.same_kernel = P.rrbs ? b.K.same == 2 : b.K.same != 0;
+    b.spread = b.K.spread_set ? b.K.spread : (b.same_kernel ? (b.K.same_d ? 2u : 1u) : 0u);
+}
+
+// One row of a batch's memory plan: a member and the bytes it gets.  The plan is these rows — bsx_batch_create allocates by walking them, and the byte counts
+// that bsx_batch_plan_bytes returns (bench.py and the CPU suite check a run's whole plan against the device's memory before anything is allocated) are their sums.
+struct PlanRow {
+    uint64_t bytes;
+    void *buf;   // the DevBuf (null: counted, never allocated)
+    hipError_t (*reserve)(void *, size_t);
+    void (*reset)(void *);
+    template <class T>
+    PlanRow(DevBuf<T> &b, uint64_t n, bool wanted = true)
+        : bytes(n), buf(wanted ? &b : nullptr), reserve([](void *q, size_t k) { return ((DevBuf<T> *)q)->reserve(k); }), reset([](void *q) { ((DevBuf<T> *)q)->reset(); }) {}
+};
+typedef std::vector<PlanRow> PlanRows;
+static uint64_t rows_bytes(const PlanRows &rows) { uint64_t s = 0; for (const PlanRow &r : rows) s += r.bytes; return s; }
+static void rows_reset(const PlanRows &rows) { for (const PlanRow &r : rows) if (r.buf) r.reset(r.buf); }
+static hipError_t rows_alloc(const PlanRows &rows)
+{
+    for (const PlanRow &r : rows) {
+        const hipError_t e = r.buf ? r.reserve(r.buf, (size_t)r.bytes) : hipSuccess;
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 struct BatchPlan {
-    uint64_t per_unit_bytes = 0;   // reads, offsets, result records, deferred / redo lists: follows max_units
+    PlanRows per_unit;             // reads, offsets, result records, deferred / redo lists: follow max_units
+    PlanRows pools;                // work pools of the heavy pipeline at their starting size (halved until they fit)
+    PlanRows fixed;                // small arrays of a fixed size (with them: BSX_PINNED_BYTES of pinned host words): allocated, not counted
     uint64_t scratch_bytes = 0;    // the main kernel's per-wave slabs: follows the grid, cannot shrink
-    uint64_t pool_bytes = 0;       // work pools of the heavy pipeline at their starting size (halved until they fit)
     uint32_t hcap = 0, task_cap = 0, n_bins = 1, bin_shift = 0;
     int grid_blocks = 0;
 };
-static uint64_t pool_bytes_for(const bsx_params &P, int paired, uint32_t hcap, uint32_t task_cap, uint32_t n_bins, int n_groups, uint64_t hslab_bytes)
+#define BSX_PINNED_BYTES 1024
+
+// the pools for rounds of `hcap` deferred units and `task_cap` scan tasks
+static PlanRows pool_rows(bsx_batch &b, uint32_t hcap, uint32_t task_cap, uint32_t n_bins)
 {
-    (void)P; (void)paired;
+    const int n_groups = b.K.n_groups;
     const uint64_t tcap = task_cap / (uint32_t)n_groups;
-    return (uint64_t)hcap * (bsx_hstate_bytes() + hslab_bytes + 8) + (uint64_t)task_cap * (bsx_htask_bytes() + bsx_htaskout_bytes()) +
-           (uint64_t)n_groups * ((uint64_t)n_bins * 8 + (uint64_t)bsx_bin_chunks(n_bins) * 4 + tcap * 12 + 16);
+    PlanRows rows = {{b.pool.hstate, (uint64_t)hcap * bsx_hstate_bytes()}, {b.pool.hslabs, (uint64_t)hcap * b.hslab_bytes},
+                     {b.pool.htasks, (uint64_t)task_cap * bsx_htask_bytes()}, {b.pool.htout, (uint64_t)task_cap * bsx_htaskout_bytes()},
+                     {b.pool.hactive[0], (uint64_t)hcap * 4}, {b.pool.hactive[1], (uint64_t)hcap * 4}};
+    for (int g = 0; g < n_groups; g++) {
+        bsx_batch::Group &q = b.grp[g];
+        rows.insert(rows.end(), {{q.d_bins, (uint64_t)n_bins * 4}, {q.d_bstart, (uint64_t)n_bins * 4}, {q.d_chunk_tot, (uint64_t)bsx_bin_chunks(n_bins) * 4},
+                                 {q.d_rank, tcap * 4}, {q.d_order, tcap * 4},
+                                 // (k_hscan_same: start slots of the groups, then their count; planned for the other scan kernels too, which have none: an upper bound)
+                                 {q.d_glist, (tcap + 4) * 4, b.same_kernel}});
+    }
+    return rows;
 }
 // starting sizes of the heavy pipeline's pools for runs of `units` units (bsx_set_heavy_limits replaces them)
 static void default_pools(const bsx_params &P, uint64_t hslab, uint32_t units, uint32_t &hcap, uint32_t &task_cap)
@@ -411,38 +527,42 @@ static void default_pools(const bsx_params &P, uint64_t hslab, uint32_t units, u
 extern "C" int bsx_default_heavy_limits(const bsx_params *p, uint32_t units, int paired, uint32_t *units_per_round, uint32_t *task_pool)
 {
     if (!p || !units || !units_per_round || !task_pool) return BSX_ERR_ARG;
-    default_pools(*p, slab_size(*p, paired ? 1 : 0, BSX_ROWCAP, true), units, *units_per_round, *task_pool);
+    default_pools(*p, slab_size(*p, paired ? 1 : 0, BSX_ROWCAP, heavy_key_cap(*p, read_knobs(), BSX_ROWCAP), BSX_HSET_BITS), units, *units_per_round, *task_pool);
     return BSX_OK;
 }
 
-static BatchPlan plan_batch(const bsx_params &P, int paired, uint32_t max_units, uint64_t n_entries, int n_cu, int blocks_per_cu, int n_groups, bool debug)
+// What a batch of this shape (init_shape) allocates on a device of n_cu CUs: the only place a size is computed.
+static BatchPlan plan_batch(bsx_batch &b, const bsx_params &P, uint64_t n_entries, int n_cu, int blocks_per_cu)
 {
     BatchPlan pl;
-    const uint32_t rowcap = BSX_ROWCAP;
-    const uint64_t slab = slab_size(P, paired, rowcap), hslab = slab_size(P, paired, rowcap, true);
+    const uint64_t mu = b.max_units;
     int grid = n_cu * std::min(8, std::max(1, blocks_per_cu));
-    const int need = (int)((max_units + 3) / 4);
+    const int need = (int)((b.max_units + 3) / 4);
     if (grid > need) grid = need > 0 ? need : 1;
     pl.grid_blocks = grid;
-    pl.scratch_bytes = (debug ? (uint64_t)max_units : (uint64_t)grid * 4) * slab;
-    const int nm = paired ? 2 : 1;
-    pl.per_unit_bytes = (uint64_t)nm * (2 * ((uint64_t)max_units * 160 + 256) + ((uint64_t)max_units + 1) * 8 + (uint64_t)max_units * sizeof(bsx_class_counts)) +
-                        (paired ? (uint64_t)max_units * (sizeof(bsx_pair) + 64) : (uint64_t)max_units * sizeof(bsx_hit)) + 2 * ((uint64_t)max_units + 1) * 4;
+    pl.scratch_bytes = (b.debug ? mu : (uint64_t)grid * 4) * b.slab_bytes;
+    for (int m = 0; m < (b.paired ? 2 : 1); m++)
+        pl.per_unit.insert(pl.per_unit.end(), {{b.d_seq[m], mu * 160 + 256}, {b.d_qual[m], mu * 160 + 256}, {b.d_off[m], (mu + 1) * 8}, {b.d_cc[m], mu * sizeof(bsx_class_counts)}});
+    if (b.paired) pl.per_unit.insert(pl.per_unit.end(), {{b.d_pairs, mu * sizeof(bsx_pair)}, {b.d_npairs, mu * 64}});
+    else pl.per_unit.push_back({b.d_hits, mu * sizeof(bsx_hit)});
+    pl.per_unit.insert(pl.per_unit.end(), {{b.d_heavy_list, (mu + 1) * 4}, {b.d_redo, (mu + 1) * 4}});
+    static_assert(BSX_N_COUNTERS <= 24, "the diagnostic clocks start at word 24");
+    pl.fixed = {{b.d_queue, 256}, {b.d_counters, 24 * 8 + 256}, {b.d_scan_stats, 64 * 64}, {b.d_heavy_count, 256}, {b.d_hcnt, (uint64_t)BSX_MAX_GROUPS * 2 * BSX_HCNT_BLOCK * 4}};
     // deferred units handled per round (more than this: several rounds): what 26 GB of slabs hold — 24 576 units of the 1.07 MB paired
     // -v 6 slab, 111 K of the 234 KB single-end -v 2 one.  RRBS defers a third of its reads (Alu-like fragments) and its scan kernel
     // shares work between the reads that walk one window in the same pass: the more units a round holds, the longer those runs — 40 GB
     // of slabs (170 K units) and 2 M tasks: C4 195 -> 159 ms per step.  Task records (8 KB each): 1 M for WGBS (C5 358 -> 328 ms against
     // 512 K: fewer requests refused), following the batch size for small batches.  bsx_set_heavy_limits replaces the STARTING sizes;
-    // either way the pools are halved until they fit (ensure_scratch).
-    if (g_user_limits) { pl.hcap = std::min<uint32_t>(max_units, g_hcap); pl.task_cap = g_task_cap; }
-    else default_pools(P, hslab, max_units, pl.hcap, pl.task_cap);
+    // either way the pools are halved until they fit (fit_pools).
+    if (g_user_limits) { pl.hcap = std::min<uint32_t>(b.max_units, g_hcap); pl.task_cap = g_task_cap; }
+    else default_pools(P, b.hslab_bytes, b.max_units, pl.hcap, pl.task_cap);
     // scan order of a pass: bins of 2^shift index entries, at most 2^20 of them (bsx_launch_task_order)
     // (WGBS: 2^21 — the tasks of one window are dealt over the bins it covers by read offset, for k_hscan_same: 8 bins of 1 024 entries per window at hg38 size)
     const uint64_t ne = std::max<uint64_t>(1, n_entries);
-    const uint32_t bin_log2 = getenv("BSX_BIN_LOG2") ? (uint32_t)std::max(8, std::min(21, atoi(getenv("BSX_BIN_LOG2")))) : (P.rrbs ? 20u : 21u);  // tuning knob
+    const uint32_t bin_log2 = b.K.bin_log2 ? b.K.bin_log2 : (P.rrbs ? 20u : 21u);
     while (((ne >> pl.bin_shift) + 1) > (1u << bin_log2)) pl.bin_shift++;
     pl.n_bins = (uint32_t)(ne >> pl.bin_shift) + 1;
-    pl.pool_bytes = pool_bytes_for(P, paired, pl.hcap, pl.task_cap, pl.n_bins, n_groups, hslab);
+    pl.pools = pool_rows(b, pl.hcap, pl.task_cap, pl.n_bins);
     return pl;
 }
 
@@ -455,123 +575,119 @@ extern "C" int bsx_set_pool_reserve(uint64_t bytes) { g_pool_reserve = bytes; re
 extern "C" int bsx_batch_plan_bytes(const bsx_params *p, uint32_t max_units, int paired, uint64_t n_entries, uint32_t n_cu, uint32_t blocks_per_cu, uint64_t *out3)
 {
     if (!p || !out3 || max_units == 0 || n_cu == 0) return BSX_ERR_ARG;
-    int ng = 1;
-    if (const char *e = getenv("BSX_HEAVY_GROUPS")) ng = std::max(1, std::min(BSX_MAX_GROUPS, atoi(e)));
-    const BatchPlan pl = plan_batch(*p, paired ? 1 : 0, max_units, n_entries, (int)n_cu, (int)blocks_per_cu, ng, false);
-    out3[0] = pl.per_unit_bytes; out3[1] = pl.scratch_bytes; out3[2] = pl.pool_bytes;
+    bsx_batch shape;   // (never allocated: the plan's rows only name its members)
+    init_shape(shape, *p, max_units, paired);
+    const BatchPlan pl = plan_batch(shape, *p, n_entries, (int)n_cu, (int)blocks_per_cu);
+    out3[0] = rows_bytes(pl.per_unit); out3[1] = pl.scratch_bytes; out3[2] = rows_bytes(pl.pools);
     return BSX_OK;
 }
 
-static int ensure_scratch(bsx_batch *b)
+// the plan of a batch on its own device, for the batch as it is now (the debug mode keeps a slab per unit); sets the main kernel's grid
+static int plan_on_device(bsx_batch *b, BatchPlan &pl)
 {
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, b->ref->device));
     int blocks_per_cu = bsx_align_occupancy(b->paired);
     if (g_waves_per_cu > 0) blocks_per_cu = std::max(1, std::min(blocks_per_cu, g_waves_per_cu / 4));
-    if (blocks_per_cu > 8) blocks_per_cu = 8;
-    int grid = prop.multiProcessorCount * blocks_per_cu;
-    const int need = (int)((b->max_units + 3) / 4);
-    if (grid > need) grid = need > 0 ? need : 1;
-    b->grid_blocks = grid;
     b->n_cu = prop.multiProcessorCount;
-    // control blocks per CU: one, although two fit.  A control wave holds half of its SIMD's registers: with two blocks per CU the scan
-    // kernel's waves cannot be resident beside them and the two only alternate; with one, four scan waves per SIMD run beside it
-    // (C3 with two batches in flight 136.5 -> 131.3 ms per step, C4 211 -> 195; BSX_HCTRL_BLOCKS: tuning knob)
-    b->hctrl_blocks_per_cu = 1;
-    if (const char *e = getenv("BSX_HCTRL_BLOCKS")) b->hctrl_blocks_per_cu = std::max(1, std::min(bsx_hctrl_occupancy(b->paired), atoi(e)));
-    if (const char *e = getenv("BSX_TAIL_TASKS")) b->tail_tasks = (uint32_t)std::max(0, atoi(e));           // 0: no tail mode (tuning)
-    if (const char *e = getenv("BSX_TAIL_GRID")) b->tail_grid_tasks = (uint32_t)std::max(64, atoi(e));
-    // (the main kernel's per-wave slabs first: what cannot shrink; the pools below take what is left)
-    const uint64_t slots = b->debug ? b->max_units : (uint64_t)grid * 4;
-    const size_t bytes = (size_t)(slots * b->slab_bytes);
-    if (bytes > b->scratch_bytes) {
-        if (b->d_scratch) (void)hipFree(b->d_scratch);
-        b->d_scratch = nullptr;
-        HIP_TRY(hipMalloc((void **)&b->d_scratch, bytes));
-        HIP_TRY(hipMemsetAsync(b->d_scratch, 0, bytes, b->stream));  // the per-slab hash sets must start empty (same stream as the kernels)
-        b->scratch_bytes = bytes;
-    }
-    if (!b->d_heavy_list) {
-        const BatchPlan pl = plan_batch(b->ref->P, b->paired, b->max_units, b->ref->n_entries, prop.multiProcessorCount, blocks_per_cu, b->n_groups, b->debug != 0);
-        b->hcap = pl.hcap; b->task_cap = pl.task_cap;
-        HIP_TRY(hipMalloc((void **)&b->d_heavy_list, ((size_t)b->max_units + 1) * 4));
-        HIP_TRY(hipMalloc((void **)&b->d_heavy_count, 256));
-        HIP_TRY(hipHostMalloc((void **)&b->h_pinned, 1024, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&b->d_redo, ((size_t)b->max_units + 1) * 4));
-        HIP_TRY(hipMalloc((void **)&b->d_hcnt, (size_t)BSX_MAX_GROUPS * 2 * BSX_HCNT_BLOCK * 4));
-        b->bin_shift = pl.bin_shift; b->n_bins = pl.n_bins;
-        // The pools proper.  Their default sizes are for a device that holds two or three batches (31 GB each for WGBS, 74 GB for RRBS);
-        // where that much is not free — more batches per device, a smaller or shared device — the pools are halved until they fit
-        // (more rounds and refused requests then, same results) instead of failing the batch.
-        auto free_pools = [&]() {
-            void **ptrs[] = {(void **)&b->d_hstate, (void **)&b->d_hslabs, (void **)&b->d_htasks, (void **)&b->d_htout, (void **)&b->d_hactive[0], (void **)&b->d_hactive[1]};
-            for (void **q : ptrs) { if (*q) (void)hipFree(*q); *q = nullptr; }
-            for (int g = 0; g < b->n_groups; g++) {
-                bsx_batch::Group &q = b->grp[g];
-                void **gp[] = {(void **)&q.d_bins, (void **)&q.d_bstart, (void **)&q.d_chunk_tot, (void **)&q.d_rank, (void **)&q.d_order, (void **)&q.d_glist};
-                for (void **x : gp) { if (*x) (void)hipFree(*x); *x = nullptr; }
-            }
-        };
-        // (the group scan kernel: WGBS unless BSX_SAME=0, RRBS with BSX_SAME=2 — the same rule as bsx_batch_run_range)
-        const int same_env0 = getenv("BSX_SAME") ? atoi(getenv("BSX_SAME")) : 1;
-        const bool same_kernel = b->same_kernel = b->ref->P.rrbs ? same_env0 == 2 : same_env0 != 0;
-        b->same_d = getenv("BSX_SAME_D") ? (uint32_t)std::min<long>(std::max<long>(0, atol(getenv("BSX_SAME_D"))), (long)bsx_same_d_max()) : bsx_same_d_max();
-        b->same_r = getenv("BSX_SAME_R") ? (uint32_t)std::min<long>(std::max<long>(1, atol(getenv("BSX_SAME_R"))), (long)bsx_same_r_max()) : bsx_same_r_max();
-        b->group_tile = getenv("BSX_GROUP_TILE") ? (uint32_t)std::max<long>(0, atol(getenv("BSX_GROUP_TILE"))) : 0u;
-        b->group_big = getenv("BSX_GROUP_BIG") ? (uint32_t)std::max<long>(0, atol(getenv("BSX_GROUP_BIG"))) : 0u;
-        auto alloc_pools = [&]() -> hipError_t {
-            hipError_t e;
-#define POOL_TRY(x) do { if ((e = (x)) != hipSuccess) return e; } while (0)
-            POOL_TRY(hipMalloc((void **)&b->d_hstate, (size_t)b->hcap * bsx_hstate_bytes()));
-            POOL_TRY(hipMalloc((void **)&b->d_hslabs, (size_t)b->hcap * b->hslab_bytes));
-            POOL_TRY(hipMalloc((void **)&b->d_htasks, (size_t)b->task_cap * bsx_htask_bytes()));
-            POOL_TRY(hipMalloc((void **)&b->d_htout, (size_t)b->task_cap * bsx_htaskout_bytes()));
-            for (int k = 0; k < 2; k++) POOL_TRY(hipMalloc((void **)&b->d_hactive[k], (size_t)b->hcap * 4));
-            const uint32_t tcap = b->task_cap / (uint32_t)b->n_groups;
-            for (int g = 0; g < b->n_groups; g++) {
-                bsx_batch::Group &q = b->grp[g];
-                POOL_TRY(hipMalloc((void **)&q.d_bins, (size_t)b->n_bins * 4));
-                POOL_TRY(hipMalloc((void **)&q.d_bstart, (size_t)b->n_bins * 4));
-                POOL_TRY(hipMalloc((void **)&q.d_chunk_tot, (size_t)bsx_bin_chunks(b->n_bins) * 4));
-                POOL_TRY(hipMalloc((void **)&q.d_rank, (size_t)tcap * 4));
-                POOL_TRY(hipMalloc((void **)&q.d_order, (size_t)tcap * 4));
-                if (same_kernel) POOL_TRY(hipMalloc((void **)&q.d_glist, ((size_t)tcap + 4) * 4));   // (k_hscan_same: start slots of the groups, then their count)
-            }
-#undef POOL_TRY
-            return hipSuccess;
-        };
-        // Starting sizes (the defaults above, or bsx_set_heavy_limits) are halved until the pools fit with `reserve` bytes to spare: first by
-        // arithmetic against hipMemGetInfo, then — another process or thread may be allocating at the same moment — on a failed hipMalloc.
-        const uint64_t reserve = g_pool_reserve ? g_pool_reserve : ((4ull << 30) + pl.scratch_bytes + pl.per_unit_bytes);
-        for (int attempt = 0;; attempt++) {
-            size_t fr = 0, tot = 0;
-            const bool smallest = b->hcap <= std::min<uint32_t>(1024u, b->max_units) && b->task_cap <= 4096;
-            hipError_t e = hipErrorOutOfMemory;
-            if (smallest || hipMemGetInfo(&fr, &tot) != hipSuccess ||
-                pool_bytes_for(b->ref->P, b->paired, b->hcap, b->task_cap, b->n_bins, b->n_groups, b->hslab_bytes) + reserve <= fr) {
-                e = alloc_pools();
-                if (e == hipSuccess) break;
-                free_pools();
-            }
-            if (e != hipErrorOutOfMemory || attempt == 12 || smallest) return bsx_hip_fail(e, "hipMalloc (work pools of the heavy pipeline)", __FILE__, __LINE__);
-            (void)hipGetLastError();
-            // (the floors never RAISE a pool: a caller's small limits — the tests' way into the many-round paths — stay as they are)
-            b->hcap = std::min<uint32_t>(b->hcap, std::max<uint32_t>(std::min<uint32_t>(1024u, b->max_units), b->hcap / 2));
-            b->task_cap = std::min<uint32_t>(b->task_cap, std::max<uint32_t>(4096u, b->task_cap / 2));
-        }
-        if (b->trace) fprintf(stderr, "[bsx] batch %p: pools for %u deferred units per round, %u scan tasks (planned %u / %u)\n", (void *)b, b->hcap, b->task_cap, pl.hcap, pl.task_cap);
-        if (getenv("BSX_POISON")) HIP_TRY(hipMemsetAsync(b->d_hstate, 0xA5, (size_t)b->hcap * bsx_hstate_bytes(), b->stream));  // test hook: recycled memory is not zero
-        HIP_TRY(hipMemsetAsync(b->d_hslabs, 0, (size_t)b->hcap * b->hslab_bytes, b->stream));
-        if (getenv("BSX_POISON")) {
-            HIP_TRY(hipMemsetAsync(b->d_htout, 0xA5, (size_t)b->task_cap * bsx_htaskout_bytes(), b->stream));
-            HIP_TRY(hipMemsetAsync(b->d_htasks, 0xA5, (size_t)b->task_cap * bsx_htask_bytes(), b->stream));
-        }
-        for (int g = 0; g < b->n_groups; g++) HIP_TRY(hipMemsetAsync(b->grp[g].d_bins, 0, (size_t)b->n_bins * 4, b->stream));
-    }
+    pl = plan_batch(*b, b->ref->P, b->ref->n_entries, b->n_cu, blocks_per_cu);
+    b->grid_blocks = pl.grid_blocks;
     return BSX_OK;
 }
 
-static int batch_create_once(bsx_ref *r, uint32_t max_units, int paired, bsx_batch **out);
+// the main kernel's per-wave slabs (what cannot shrink; the pools take what is left): grown where the plan asks for more
+static int ensure_scratch(bsx_batch *b, const BatchPlan &pl)
+{
+    if (pl.scratch_bytes <= b->scratch_bytes) return BSX_OK;
+    b->d_scratch.reset();
+    HIP_TRY(b->d_scratch.reserve((size_t)pl.scratch_bytes));
+    HIP_TRY(hipMemsetAsync(b->d_scratch, 0, (size_t)pl.scratch_bytes, b->stream));  // the per-slab hash sets must start empty (same stream as the kernels)
+    b->scratch_bytes = (size_t)pl.scratch_bytes;
+    return BSX_OK;
+}
+
+// The pools proper.  Their default sizes are for a device that holds two or three batches (31 GB each for WGBS, 74 GB for RRBS);
+// where that much is not free — more batches per device, a smaller or shared device — the pools are halved until they fit
+// (more rounds and refused requests then, same results) instead of failing the batch.
+static int fit_pools(bsx_batch *b, const BatchPlan &pl)
+{
+    b->hcap = pl.hcap; b->task_cap = pl.task_cap;
+    b->bin_shift = pl.bin_shift; b->n_bins = pl.n_bins;
+    // Starting sizes (the defaults above, or bsx_set_heavy_limits) are halved until the pools fit with `reserve` bytes to spare: first by
+    // arithmetic against hipMemGetInfo, then — another process or thread may be allocating at the same moment — on a failed hipMalloc.
+    const uint64_t reserve = g_pool_reserve ? g_pool_reserve : ((4ull << 30) + pl.scratch_bytes + rows_bytes(pl.per_unit));
+    for (int attempt = 0;; attempt++) {
+        size_t fr = 0, tot = 0;
+        const bool smallest = b->hcap <= std::min<uint32_t>(1024u, b->max_units) && b->task_cap <= 4096;
+        const PlanRows rows = pool_rows(*b, b->hcap, b->task_cap, b->n_bins);
+        hipError_t e = hipErrorOutOfMemory;
+        if (smallest || hipMemGetInfo(&fr, &tot) != hipSuccess || rows_bytes(rows) + reserve <= fr) {
+            e = rows_alloc(rows);
+            if (e == hipSuccess) break;
+            rows_reset(rows);
+        }
+        if (e != hipErrorOutOfMemory || attempt == 12 || smallest) return bsx_hip_fail(e, "hipMalloc (work pools of the heavy pipeline)", __FILE__, __LINE__);
+        (void)hipGetLastError();
+        // (the floors never RAISE a pool: a caller's small limits — the tests' way into the many-round paths — stay as they are)
+        b->hcap = std::min<uint32_t>(b->hcap, std::max<uint32_t>(std::min<uint32_t>(1024u, b->max_units), b->hcap / 2));
+        b->task_cap = std::min<uint32_t>(b->task_cap, std::max<uint32_t>(4096u, b->task_cap / 2));
+    }
+    if (b->K.trace) fprintf(stderr, "[bsx] batch %p: pools for %u deferred units per round, %u scan tasks (planned %u / %u)\n", (void *)b, b->hcap, b->task_cap, pl.hcap, pl.task_cap);
+    if (b->K.poison) HIP_TRY(hipMemsetAsync(b->pool.hstate, 0xA5, (size_t)b->hcap * bsx_hstate_bytes(), b->stream));  // test hook: recycled memory is not zero
+    HIP_TRY(hipMemsetAsync(b->pool.hslabs, 0, (size_t)b->hcap * b->hslab_bytes, b->stream));
+    if (b->K.poison) {
+        HIP_TRY(hipMemsetAsync(b->pool.htout, 0xA5, (size_t)b->task_cap * bsx_htaskout_bytes(), b->stream));
+        HIP_TRY(hipMemsetAsync(b->pool.htasks, 0xA5, (size_t)b->task_cap * bsx_htask_bytes(), b->stream));
+    }
+    for (int g = 0; g < b->K.n_groups; g++) HIP_TRY(hipMemsetAsync(b->grp[g].d_bins, 0, (size_t)b->n_bins * 4, b->stream));
+    return BSX_OK;
+}
+
+static int batch_create_once(bsx_ref *r, uint32_t max_units, int paired, bsx_batch **out)
+{
+    if (!r || !out || max_units == 0) return BSX_ERR_ARG;
+    if (!r->has_index) { g_bsx_err = "bsx_index_build must run before bsx_batch_create"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(r->device));
+    // (a batch that fails half-built goes the way of a whole one: its streams are synchronised, then every member frees what it holds)
+    std::unique_ptr<bsx_batch, void (*)(bsx_batch *)> owner(new bsx_batch(), bsx_batch_destroy);
+    bsx_batch *b = owner.get();
+    b->ref = r;
+    init_shape(*b, r->P, max_units, paired);
+    if (b->K.sector_stats) bsx_sector_pass(r, nullptr);   // (sets the bitmap up)
+    if (b->stream.create(hipStreamNonBlocking) != hipSuccess) return BSX_ERR_DEVICE;
+    {
+        int lo_p = 0, hi_p = 0;
+        (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
+        for (int g = 0; g < b->K.n_groups; g++) {
+            bsx_batch::Group &q = b->grp[g];
+            if (q.s_ctrl.create(hipStreamNonBlocking, hi_p) != hipSuccess) return BSX_ERR_DEVICE;
+            for (DevEvent *e : {&q.ev_ctrl, &q.ev_scan})
+                if (e->create(hipEventDisableTiming) != hipSuccess) return BSX_ERR_DEVICE;
+            for (DevEvent &e : q.ev_poll)  // the host polls these and sleeps in between (wait_event: one driver thread per device batch)
+                if (e.create(hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) return BSX_ERR_DEVICE;
+        }
+        if (b->ev_sync.create(hipEventDisableTiming) != hipSuccess) return BSX_ERR_DEVICE;
+        if (b->ev_wait.create(hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) return BSX_ERR_DEVICE;
+    }
+    if (b->ev0.create() != hipSuccess || b->ev1.create() != hipSuccess) return BSX_ERR_DEVICE;
+    b->hctrl_blocks_per_cu = std::max(1, std::min(bsx_hctrl_occupancy(b->paired), b->K.hctrl_blocks));
+    BatchPlan pl;
+    int rc = plan_on_device(b, pl);
+    if (rc != BSX_OK) return rc;
+    for (const PlanRows *rows : {&pl.per_unit, &pl.fixed}) {
+        const hipError_t e = rows_alloc(*rows);
+        if (e != hipSuccess) return bsx_hip_fail(e, "hipMalloc (per-unit arrays of the batch)", __FILE__, __LINE__);
+    }
+    for (int m = 0; m < (b->paired ? 2 : 1); m++) b->seq_cap[m] = b->d_seq[m].cap;
+    HIP_TRY(hipHostMalloc((void **)&b->h_pinned, BSX_PINNED_BYTES, hipHostMallocDefault));
+    HIP_TRY(hipMemsetAsync(b->d_counters, 0, 24 * 8 + 256, b->stream));
+    HIP_TRY(hipMemsetAsync(b->d_scan_stats, 0, 64 * 64, b->stream));
+    if ((rc = ensure_scratch(b, pl)) != BSX_OK || (rc = fit_pools(b, pl)) != BSX_OK) return rc;
+    b->counted = true;
+    *out = owner.release();
+    return BSX_OK;
+}
+
 extern "C" int bsx_batch_create(bsx_ref *r, uint32_t max_units, int paired, bsx_batch **out)
 {
     int rc = batch_create_once(r, max_units, paired, out);
@@ -582,73 +698,11 @@ extern "C" int bsx_batch_create(bsx_ref *r, uint32_t max_units, int paired, bsx_
         (void)hipGetLastError();
         if (bsx_ref_drop_context(r) == BSX_OK) {
             rc = batch_create_once(r, max_units, paired, out);
-            if (rc == BSX_OK && getenv("BSX_TRACE_HEAVY")) fprintf(stderr, "[bsx] the index's context table was dropped to make room for the batch (%s)\n", first.c_str());
+            if (rc == BSX_OK && (*out)->K.trace) fprintf(stderr, "[bsx] the index's context table was dropped to make room for the batch (%s)\n", first.c_str());
         }
     }
     if (rc == BSX_OK) r->n_batches++;
     return rc;
-}
-static int batch_create_once(bsx_ref *r, uint32_t max_units, int paired, bsx_batch **out)
-{
-    if (!r || !out || max_units == 0) return BSX_ERR_ARG;
-    if (!r->has_index) { g_bsx_err = "bsx_index_build must run before bsx_batch_create"; return BSX_ERR_STATE; }
-    HIP_TRY(hipSetDevice(r->device));
-    bsx_batch *b = new bsx_batch();
-    b->ref = r; b->paired = paired ? 1 : 0; b->max_units = max_units;
-    b->rowcap = BSX_ROWCAP;
-    b->slab_bytes = slab_size(r->P, b->paired, b->rowcap);
-    b->hslab_bytes = slab_size(r->P, b->paired, b->rowcap, true);
-    b->hkcap = heavy_key_cap(r->P, b->rowcap);
-    int rc = BSX_OK;
-    auto fail = [&](int code) { bsx_batch_destroy(b); return code; };
-    // tuning / diagnostic knobs are read once, here (a batch keeps its settings): unit groups of the heavy pipeline (default 1: the
-    // control and scan passes of a batch alternate and overlap those of the OTHER batch in flight — measured best with two batches in
-    // flight, C3 131 ms per step against 148 with two groups each; a caller that keeps a single batch in flight gains from 2: 158 against
-    // 177 ms), passes enqueued per host poll
-    if (const char *e = getenv("BSX_HEAVY_GROUPS")) b->n_groups = std::max(1, std::min(BSX_MAX_GROUPS, atoi(e)));
-    if (const char *e = getenv("BSX_XCD_MAP")) b->xcd_map = (uint32_t)std::max(0, atoi(e));   // how k_hscan's blocks map onto the scan order: 0 as dispatched, 1 one contiguous eighth per XCD, N >= 2 pieces of N blocks dealt to the XCDs in turn
-    if (const char *e = getenv("BSX_HEAVY_CHUNK")) b->chunk_passes = std::max(1, std::min(64, atoi(e)));
-    b->trace = getenv("BSX_TRACE_HEAVY") != nullptr;
-    if (const char *e = getenv("BSX_WORK_COUNTERS")) b->work_counters = atoi(e) != 0;   // the default of bsx_batch_set_work_counters (test hook)
-    b->sig_hist = getenv("BSX_SIGHIST") != nullptr;
-    b->sector_stats = getenv("BSX_SECTOR_STATS") != nullptr;
-    if (b->sector_stats) bsx_sector_pass(r, nullptr);   // (sets the bitmap up)
-    if (hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    {
-        int lo_p = 0, hi_p = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
-        for (int g = 0; g < b->n_groups; g++) {
-            bsx_batch::Group &q = b->grp[g];
-            if (hipStreamCreateWithPriority(&q.s_ctrl, hipStreamNonBlocking, hi_p) != hipSuccess) return fail(BSX_ERR_DEVICE);
-            for (hipEvent_t *e : {&q.ev_ctrl, &q.ev_scan})
-                if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return fail(BSX_ERR_DEVICE);
-            for (int k = 0; k < BSX_POLL_SLOTS; k++)  // the host polls these and sleeps in between (wait_event: one driver thread per device batch)
-                if (hipEventCreateWithFlags(&q.ev_poll[k], hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) return fail(BSX_ERR_DEVICE);
-        }
-        if (hipEventCreateWithFlags(&b->ev_sync, hipEventDisableTiming) != hipSuccess) return fail(BSX_ERR_DEVICE);
-        if (hipEventCreateWithFlags(&b->ev_wait, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    }
-    if (hipEventCreate(&b->ev0) != hipSuccess || hipEventCreate(&b->ev1) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    const int nm = b->paired ? 2 : 1;
-    for (int m = 0; m < nm; m++) {
-        b->seq_cap[m] = (size_t)max_units * 160 + 256;
-        if (hipMalloc((void **)&b->d_seq[m], b->seq_cap[m]) != hipSuccess || hipMalloc((void **)&b->d_qual[m], b->seq_cap[m]) != hipSuccess ||
-            hipMalloc((void **)&b->d_off[m], ((size_t)max_units + 1) * 8) != hipSuccess || hipMalloc((void **)&b->d_cc[m], (size_t)max_units * sizeof(bsx_class_counts)) != hipSuccess)
-            return fail(BSX_ERR_NOMEM);
-    }
-    if (b->paired) {
-        if (hipMalloc((void **)&b->d_pairs, (size_t)max_units * sizeof(bsx_pair)) != hipSuccess || hipMalloc((void **)&b->d_npairs, (size_t)max_units * 64) != hipSuccess)
-            return fail(BSX_ERR_NOMEM);
-    } else if (hipMalloc((void **)&b->d_hits, (size_t)max_units * sizeof(bsx_hit)) != hipSuccess) return fail(BSX_ERR_NOMEM);
-    if (hipMalloc((void **)&b->d_queue, 256) != hipSuccess || hipMalloc((void **)&b->d_counters, 24 * 8 + 256) != hipSuccess) return fail(BSX_ERR_NOMEM);
-    static_assert(BSX_N_COUNTERS <= 24, "the diagnostic clocks start at word 24");
-    if (hipMemsetAsync(b->d_counters, 0, 24 * 8 + 256, b->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    if (hipMalloc((void **)&b->d_scan_stats, 64 * 64) != hipSuccess) return fail(BSX_ERR_NOMEM);
-    if (hipMemsetAsync(b->d_scan_stats, 0, 64 * 64, b->stream) != hipSuccess) return fail(BSX_ERR_DEVICE);
-    if ((rc = ensure_scratch(b)) != BSX_OK) return fail(rc);
-    b->counted = true;
-    *out = b;
-    return BSX_OK;
 }
 
 extern "C" void bsx_batch_destroy(bsx_batch *b)
@@ -656,31 +710,9 @@ extern "C" void bsx_batch_destroy(bsx_batch *b)
     if (!b) return;
     (void)hipSetDevice(b->ref->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    if (b->sig_hist) bsx_sig_hist_report();
-    if (b->sector_stats) bsx_sector_report();
-    for (int m = 0; m < 2; m++)
-        for (void *q : {(void *)b->d_seq[m], (void *)b->d_qual[m], (void *)b->d_off[m], (void *)b->d_cc[m]})
-            if (q) (void)hipFree(q);
-    for (void *q : {(void *)b->d_hits, (void *)b->d_pairs, (void *)b->d_npairs, (void *)b->d_scratch, (void *)b->d_dbg, (void *)b->d_queue, (void *)b->d_counters, (void *)b->d_scan_stats, (void *)b->d_cycles, (void *)b->d_heavy_list, (void *)b->d_heavy_count,
-                    (void *)b->d_hstate, (void *)b->d_hslabs, (void *)b->d_htasks, (void *)b->d_htout, (void *)b->d_hactive[0], (void *)b->d_hactive[1], (void *)b->d_hcnt, (void *)b->d_redo, (void *)b->d_ah_pool, (void *)b->d_ah_ctl, (void *)b->d_ah_spans})
-        if (q) (void)hipFree(q);
-    for (int m = 0; m < 2; m++) for (void *q : {(void *)b->d_hist_seq[m], (void *)b->d_hist_qual[m], (void *)b->d_hist_off[m]}) if (q) (void)hipFree(q);
-    for (void *q : {(void *)b->d_leak_rec, (void *)b->d_leak_meta[0], (void *)b->d_leak_meta[1], (void *)b->d_leak_blk, (void *)b->d_leak_init, (void *)b->d_leak_final}) if (q) (void)hipFree(q);
-    if (b->h_pinned) (void)hipHostFree(b->h_pinned);
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    for (int g = 0; g < BSX_MAX_GROUPS; g++) {
-        bsx_batch::Group &q = b->grp[g];
-        if (q.s_ctrl) { (void)hipStreamSynchronize(q.s_ctrl); (void)hipStreamDestroy(q.s_ctrl); }
-        for (hipEvent_t e : {q.ev_ctrl, q.ev_scan, q.ev_poll[0], q.ev_poll[1], q.ev_poll[2], q.ev_poll[3]}) if (e) (void)hipEventDestroy(e);
-        for (void *p_ : {(void *)q.d_bins, (void *)q.d_bstart, (void *)q.d_chunk_tot, (void *)q.d_rank, (void *)q.d_order, (void *)q.d_glist}) if (p_) (void)hipFree(p_);
-    }
-    if (b->ev_sync) (void)hipEventDestroy(b->ev_sync);
-    if (b->ev_wait) (void)hipEventDestroy(b->ev_wait);
-    for (hipEvent_t e : b->scan_ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : b->ctrl_ev) (void)hipEventDestroy(e);
-    if (b->ev_align) (void)hipEventDestroy(b->ev_align);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
+    for (bsx_batch::Group &q : b->grp) if (q.s_ctrl) (void)hipStreamSynchronize(q.s_ctrl);
+    if (b->K.sig_hist) bsx_sig_hist_report();
+    if (b->K.sector_stats) bsx_sector_report();
     if (b->counted && b->ref->n_batches > 0) b->ref->n_batches--;
     delete b;
 }
@@ -689,12 +721,12 @@ static int upload_mate(bsx_batch *b, int m, uint32_t n, const char *seqs, const 
 {
     const uint64_t bytes = off[n] - off[0];
     if (off[0] != 0) { g_bsx_err = "off[0] must be 0"; return BSX_ERR_ARG; }
-    if (bytes + 256 > b->seq_cap[m]) {
-        (void)hipFree(b->d_seq[m]); (void)hipFree(b->d_qual[m]);
-        b->d_seq[m] = b->d_qual[m] = nullptr;
+    if (bytes + 256 > b->seq_cap[m]) {   // (both go before either comes back; if one does not, the capacity stays 0 and the next upload allocates again)
+        b->d_seq[m].reset(); b->d_qual[m].reset();
+        b->seq_cap[m] = 0;
+        HIP_TRY(b->d_seq[m].reserve(bytes + 256));
+        HIP_TRY(b->d_qual[m].reserve(bytes + 256));
         b->seq_cap[m] = bytes + 256;
-        HIP_TRY(hipMalloc((void **)&b->d_seq[m], b->seq_cap[m]));
-        HIP_TRY(hipMalloc((void **)&b->d_qual[m], b->seq_cap[m]));
     }
     HIP_TRY(hipMemcpyAsync(b->d_seq[m], seqs, bytes, hipMemcpyHostToDevice, b->stream));
     if (quals) HIP_TRY(hipMemcpyAsync(b->d_qual[m], quals, bytes, hipMemcpyHostToDevice, b->stream));
@@ -767,16 +799,15 @@ extern "C" int bsx_batch_set_history(bsx_batch *b, uint32_t n, const char *seqs_
     const char *sq[2] = {seqs_a, seqs_b}, *ql[2] = {quals_a, quals_b};
     const uint64_t *of[2] = {off_a, off_b};
     for (int m = 0; m < (b->paired ? 2 : 1); m++) {
-        for (void *q : {(void *)b->d_hist_seq[m], (void *)b->d_hist_qual[m], (void *)b->d_hist_off[m]}) if (q) (void)hipFree(q);
-        b->d_hist_seq[m] = b->d_hist_qual[m] = nullptr; b->d_hist_off[m] = nullptr;
+        b->d_hist_seq[m].reset(); b->d_hist_qual[m].reset(); b->d_hist_off[m].reset();
         if (!n) continue;
         if (of[m][0] != 0) { g_bsx_err = "off[0] must be 0"; return BSX_ERR_ARG; }
         const uint64_t bytes = of[m][n];
-        HIP_TRY(hipMalloc((void **)&b->d_hist_seq[m], bytes + 256));
-        HIP_TRY(hipMalloc((void **)&b->d_hist_off[m], ((size_t)n + 1) * 8));
+        HIP_TRY(b->d_hist_seq[m].reserve(bytes + 256));
+        HIP_TRY(b->d_hist_off[m].reserve(((size_t)n + 1) * 8));
         HIP_TRY(hipMemcpy(b->d_hist_seq[m], sq[m], bytes, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b->d_hist_off[m], of[m], ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
-        if (ql[m]) { HIP_TRY(hipMalloc((void **)&b->d_hist_qual[m], bytes + 256)); HIP_TRY(hipMemcpy(b->d_hist_qual[m], ql[m], bytes, hipMemcpyHostToDevice)); }
+        if (ql[m]) { HIP_TRY(b->d_hist_qual[m].reserve(bytes + 256)); HIP_TRY(hipMemcpy(b->d_hist_qual[m], ql[m], bytes, hipMemcpyHostToDevice)); }
     }
     b->n_hist = n; b->leak_meta_valid = false;
     return BSX_OK;
@@ -795,10 +826,12 @@ extern "C" int bsx_batch_set_debug(bsx_batch *b, int keep)
     if (!b) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ref->device));
     b->debug = keep == 1 ? 1 : 0;
-    if (keep == 2 && !b->d_cycles) HIP_TRY(hipMalloc((void **)&b->d_cycles, (size_t)b->max_units * 4));
-    if (keep == 0 && b->d_cycles) { (void)hipFree(b->d_cycles); b->d_cycles = nullptr; }
-    if (keep == 1 && !b->d_dbg) HIP_TRY(hipMalloc((void **)&b->d_dbg, (size_t)b->max_units * 128));
-    return ensure_scratch(b);
+    if (keep == 2) HIP_TRY(b->d_cycles.reserve((size_t)b->max_units * 4));
+    if (keep == 0) b->d_cycles.reset();
+    if (keep == 1) HIP_TRY(b->d_dbg.reserve((size_t)b->max_units * 128));
+    BatchPlan pl;   // (the debug mode keeps a slab per unit: the slabs may have to grow)
+    const int rc = plan_on_device(b, pl);
+    return rc ? rc : ensure_scratch(b, pl);
 }
 
 // exact mode: device arrays of the pre-pass and the argument fields that describe the mate streams
@@ -806,14 +839,14 @@ static int leak_prepare(bsx_batch *b, AlignArgs &A)
 {
     const uint32_t cap = b->max_units + 65536u, nblk = cap / bsx_leak_blk() + 2;
     if (!b->d_leak_meta[0]) {
-        for (int m = 0; m < (b->paired ? 2 : 1); m++) HIP_TRY(hipMalloc((void **)&b->d_leak_meta[m], (size_t)cap * 2));
-        HIP_TRY(hipMalloc((void **)&b->d_leak_blk, (size_t)nblk * 16));
-        HIP_TRY(hipMalloc((void **)&b->d_leak_final, bsx_leakstate_bytes()));
-        HIP_TRY(hipMalloc((void **)&b->d_leak_rec, (size_t)b->max_units * 2 * bsx_leakrec_bytes()));
+        for (int m = 0; m < (b->paired ? 2 : 1); m++) HIP_TRY(b->d_leak_meta[m].reserve((size_t)cap * 2));
+        HIP_TRY(b->d_leak_blk.reserve((size_t)nblk * 16));
+        HIP_TRY(b->d_leak_final.reserve(bsx_leakstate_bytes()));
+        HIP_TRY(b->d_leak_rec.reserve((size_t)b->max_units * 2 * bsx_leakrec_bytes()));
         b->leak_nblk = nblk;
     }
     for (int m = 0; m < 2; m++) { A.leak_meta[m] = b->d_leak_meta[m]; A.leak_blkmax[m] = b->d_leak_blk + (size_t)m * nblk; A.leak_blkset[m] = b->d_leak_blk + (size_t)(2 + m) * nblk; }
-    A.leak_init = b->leak_has_init ? b->d_leak_init : nullptr;
+    A.leak_init = b->leak_has_init ? b->d_leak_init.p : nullptr;
     A.leak_rec = b->d_leak_rec;
     A.n_units_all = b->n_units;
     A.n_hist = b->n_hist;
@@ -821,15 +854,24 @@ static int leak_prepare(bsx_batch *b, AlignArgs &A)
     return BSX_OK;
 }
 
-static void fill_stream_args(bsx_batch *b, AlignArgs &A)
+// the argument block of the batch as it stands: everything but the range of units (the caller's) and the exact mode's arrays (leak_prepare)
+static void fill_args(bsx_batch *b, AlignArgs &A)
 {
     memset(&A, 0, sizeof(A));
     bsx_fill_devparams(b->ref, A.P);
-    A.first_index = b->first_index;
+    A.first_index = b->first_index; A.debug = b->debug; A.rowcap = b->rowcap; A.kcap = b->kcap; A.hbits = hset_bits(b->ref->P);
+    A.hkcap = b->hkcap; A.hhbits = BSX_HSET_BITS; A.hslab_bytes = b->hslab_bytes;
+    A.redo_count = b->d_redo; A.redo_list = b->d_redo + 1; A.unit_list = nullptr;
     for (int m = 0; m < 2; m++) {
-        A.seq[m] = b->d_seq[m]; A.off[m] = b->d_off[m]; A.qual[m] = b->has_qual ? b->d_qual[m] : nullptr;
+        A.seq[m] = b->d_seq[m]; A.off[m] = b->d_off[m]; A.qual[m] = b->has_qual ? b->d_qual[m].p : nullptr; A.cc[m] = b->d_cc[m];
         A.hist_seq[m] = b->d_hist_seq[m]; A.hist_off[m] = b->d_hist_off[m]; A.hist_qual[m] = b->d_hist_qual[m];
     }
+    A.hits_out = b->d_hits; A.pairs_out = b->d_pairs; A.npairs_out = b->d_npairs;
+    A.scratch = b->d_scratch; A.slab_bytes = b->slab_bytes; A.queue = b->d_queue; A.counters = b->d_counters; A.scan_stats = b->d_scan_stats; A.work_counters = (uint32_t)b->work_counters;
+    A.dbg_plan = b->d_dbg; A.dbg_cycles = b->d_cycles; A.dbg_cat = b->d_cycles ? b->d_counters + 24 : nullptr;
+    A.heavy_list = b->d_heavy_list; A.heavy_count = b->d_heavy_count;
+    A.leak_exact = b->leak_exact; A.n_hist = b->leak_exact ? b->n_hist : 0; A.n_units_all = b->n_units;
+    A.heavy_threshold = heavy_threshold_for(b->ref->P);
 }
 
 extern "C" int bsx_batch_set_leak_state(bsx_batch *b, const void *state, size_t bytes)
@@ -838,7 +880,7 @@ extern "C" int bsx_batch_set_leak_state(bsx_batch *b, const void *state, size_t 
     HIP_TRY(hipSetDevice(b->ref->device));
     HIP_TRY(stream_wait(b));
     if (!state) { b->leak_has_init = false; return BSX_OK; }
-    if (!b->d_leak_init) HIP_TRY(hipMalloc((void **)&b->d_leak_init, bsx_leakstate_bytes()));
+    HIP_TRY(b->d_leak_init.reserve(bsx_leakstate_bytes()));
     HIP_TRY(hipMemcpy(b->d_leak_init, state, bytes, hipMemcpyHostToDevice));
     b->leak_has_init = true;
     return BSX_OK;
@@ -851,7 +893,7 @@ extern "C" int bsx_batch_get_leak_state(bsx_batch *b, void *state, size_t bytes)
     if (b->ref->P.rrbs) { memset(state, 0, bytes); return BSX_OK; }   // RRBS plans every read from offset 0 (align.cpp:456): no state
     HIP_TRY(hipSetDevice(b->ref->device));
     AlignArgs A;
-    fill_stream_args(b, A);
+    fill_args(b, A);
     A.n_units = b->n_units; A.first_unit = 0;
     int rc = leak_prepare(b, A);
     if (rc) return rc;
@@ -860,6 +902,197 @@ extern "C" int bsx_batch_get_leak_state(bsx_batch *b, void *state, size_t bytes)
     b->leak_meta_valid = true;
     HIP_TRY(hipMemcpyAsync(state, b->d_leak_final, bytes, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(stream_wait(b));
+    return BSX_OK;
+}
+
+// One round of the heavy pipeline: up to hcap deferred units (those from `base` of the deferred list), split into unit groups whose passes run out of phase.
+// One pass of a group =
+//   k_hctrl (advance every active unit of the group, publish scan tasks)          on the group's high-priority stream
+//   task order (bsx_launch_task_order) + k_hscan over the published tasks          on the batch's stream
+// chained by events on the device: the counts a control pass leaves (active units, tasks) stay there — the next control
+// pass reads its input count from memory, the scan launches are sized for the whole task pool and their surplus blocks exit.
+// The host enqueues `chunk_passes` passes per group at a time, keeps two such chunks queued ahead, and only looks at a
+// group's active count once per chunk (polling an event, asleep in between) to learn when the group is finished; passes that were queued
+// beyond that point find nothing to do.  While k_hscan evaluates the tasks of one group, the control kernels of the others
+// run beside it — they are latency-bound chains of a few thousand waves.
+namespace {
+struct HeavyRound {
+    bsx_batch *b;
+    const AlignArgs &A;
+    const AllHitsArgs *ah;
+    uint32_t base;
+    int n_open = 0;
+    struct GroupState { uint32_t n0 = 0, passes = 0, polls = 0, polled = 0; int cur = 0; bool done = true, tail = false; HeavyArgsRaw H; uint32_t *blk[2]; } G[BSX_MAX_GROUPS];
+
+    int enqueue_pass(int g);
+    int enqueue_chunk();
+    int poll();
+    int run_round(uint32_t n_round);
+};
+
+int HeavyRound::enqueue_pass(int g)
+{
+    GroupState &q = G[g];
+    bsx_batch::Group &hw = b->grp[g];
+    uint32_t *in = q.blk[q.cur], *out = q.blk[q.cur ^ 1];
+    const bool fresh = q.passes == 0;
+    if (fresh) {
+        HIP_TRY(hipStreamWaitEvent(hw.s_ctrl, b->ev_sync, 0));
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)BSX_HCNT_BLOCK * 4, hw.s_ctrl));
+    } else HIP_TRY(hipStreamWaitEvent(hw.s_ctrl, hw.ev_scan, 0));  // the scan of the previous pass (its first kernel also cleared `out`)
+    q.H.active_in = b->pool.hactive[q.cur] + q.H.hidx_base; q.H.active_out = b->pool.hactive[q.cur ^ 1] + q.H.hidx_base;
+    q.H.n_active_in_ptr = in; q.H.n_active_in = q.n0; q.H.n_active_out = out; q.H.n_tasks = out + BSX_HCNT_TASKS; q.H.queue = out + BSX_HCNT_QUEUE;   // (apart: see BSX_HCNT_*)
+    q.H.fresh = fresh ? 1 : 0;
+    if (b->stage_timing) {
+        int rc = grow_events(b->ctrl_ev, b->ctrl_ev_used + 3);
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used], hw.s_ctrl));
+    }
+    // (no more blocks than are resident at once — two per CU by their LDS —: blocks of a high-priority kernel that wait for a slot
+    //  keep the dispatcher from placing the kernels of the normal-priority stream, 300 us per pass when the grid was twice that)
+    bsx_launch_hctrl(A, q.H, b->paired, (int)std::min<uint32_t>((q.n0 + 3) / 4, (uint32_t)b->n_cu * b->hctrl_blocks_per_cu), hw.s_ctrl, ah);
+    HIP_TRY(hipGetLastError());
+    if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 1], hw.s_ctrl));
+    // scan order of the tasks this pass published, still on the group's stream: done by the time the main stream gets to the scan
+    q.H.order = hw.d_order; q.H.xcd_map = b->K.xcd_map; q.H.ghead = hw.d_rank; q.H.glist = hw.d_glist;
+    bsx_launch_task_order(q.H, b->bin_shift, b->n_bins, hw.d_bins, hw.d_bstart, hw.d_chunk_tot, hw.d_rank, hw.d_order, in, hw.s_ctrl, b->spread, b->same_kernel, b->K.same_d, b->K.same_r,
+                          b->K.group_tile, b->K.group_big);
+    // The scan: on the batch's stream with a grid for the whole task pool — or, once the group is in its tail (few tasks per
+    // pass, see poll), behind the control kernel on the group's own high-priority stream with a small grid whose
+    // blocks sweep: beside ANOTHER batch's bulk scans a pool-sized grid of mostly empty blocks only trickles through the
+    // dispatcher, which stretched the tail of the older batch until the younger one's bulk was done — two batches in flight
+    // always finished together, and their transfers never overlapped the other's kernels.
+    if (b->stage_timing) { HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 2], hw.s_ctrl)); b->ctrl_ev_used += 3; }
+    if (b->K.sig_hist) bsx_sig_hist_pass(q.H, hw.s_ctrl, b->same_kernel, b->K.group_tile);
+    hipStream_t s_scan = b->stream;
+    if (q.tail) s_scan = hw.s_ctrl;
+    else {
+        HIP_TRY(hipEventRecord(hw.ev_ctrl, hw.s_ctrl));
+        HIP_TRY(hipStreamWaitEvent(b->stream, hw.ev_ctrl, 0));
+    }
+    { int rc = grow_events(b->scan_ev, b->scan_ev_used + 2); if (rc) return rc; }
+    HIP_TRY(hipEventRecord(b->scan_ev[b->scan_ev_used], s_scan));
+    // (which scan kernel was decided when the batch was created, BatchKnobs::same: the group lists exist or not)
+    if (b->same_kernel) bsx_launch_hscan_same(A, q.H, s_scan, q.tail ? b->K.tail_grid_tasks : 0);
+    else if (b->ref->P.rrbs) bsx_launch_hscan_shared(A, q.H, s_scan, q.tail ? b->K.tail_grid_tasks : 0);
+    else bsx_launch_hscan(A, q.H, s_scan, q.tail ? b->K.tail_grid_tasks : 0);
+    HIP_TRY(hipGetLastError());
+    if (b->K.sector_stats) bsx_sector_pass(b->ref, s_scan);
+    HIP_TRY(hipEventRecord(b->scan_ev[b->scan_ev_used + 1], s_scan));
+    b->scan_ev_used += 2;
+    HIP_TRY(hipEventRecord(hw.ev_scan, s_scan));
+    q.cur ^= 1; q.passes++;
+    b->last_heavy_iters++;
+    return BSX_OK;
+}
+
+// one chunk: `chunk_passes` passes of every open group, interleaved pass by pass — the main stream takes the scans in the order
+// they are queued, and the scan of group g's next pass can only start after that group's control pass, which runs beside
+// the scans of the other groups — then the counts each group's last control pass of the chunk left: {active units, tasks}
+int HeavyRound::enqueue_chunk()
+{
+    const int n_groups = b->K.n_groups;
+    for (int k = 0; k < b->K.chunk_passes; k++)
+        for (int g = 0; g < n_groups; g++)
+            if (!G[g].done) { int rc = enqueue_pass(g); if (rc) return rc; }
+    for (int g = 0; g < n_groups; g++) {
+        GroupState &q = G[g];
+        if (q.done) continue;
+        const uint32_t slot = q.polls % BSX_POLL_SLOTS;
+        HIP_TRY(hipMemcpyAsync(b->h_pinned + 32 + 16 * g + 2 * slot, q.blk[q.cur], 4, hipMemcpyDeviceToHost, b->grp[g].s_ctrl));
+        HIP_TRY(hipMemcpyAsync(b->h_pinned + 32 + 16 * g + 2 * slot + 1, q.blk[q.cur] + BSX_HCNT_TASKS, 4, hipMemcpyDeviceToHost, b->grp[g].s_ctrl));
+        HIP_TRY(hipEventRecord(b->grp[g].ev_poll[slot], b->grp[g].s_ctrl));
+        q.polls++;
+    }
+    return BSX_OK;
+}
+
+// the oldest chunk in flight: what it left of every open group
+int HeavyRound::poll()
+{
+    volatile uint32_t *pinned = (volatile uint32_t *)b->h_pinned;
+    for (int g = 0; g < b->K.n_groups; g++) {
+        GroupState &q = G[g];
+        if (q.done) continue;
+        const uint32_t slot = q.polled % BSX_POLL_SLOTS;
+        HIP_TRY(wait_event(b->grp[g].ev_poll[slot]));
+        const uint32_t n_act = pinned[32 + 16 * g + 2 * slot], n_tasks = pinned[32 + 16 * g + 2 * slot + 1];
+        q.polled++;
+        if (b->K.trace) fprintf(stderr, "[bsx heavy] paired %d base %u group %d passes %u active %u tasks %u\n", b->paired, base, g, q.polled * b->K.chunk_passes, n_act, n_tasks);
+        if (n_act == 0) { q.done = true; n_open--; }  // (passes already queued for this group find no active unit)
+        else {
+            // (tested before the tail decision: a stuck unit publishes few tasks per pass — exactly what the tail mode looks like)
+            if (q.passes > 200000) { g_bsx_err = "heavy pipeline did not converge"; return BSX_ERR_DEVICE; }
+            if (b->K.tail_tasks && n_tasks < b->K.tail_tasks) q.tail = true;  // (the counts are two chunks old: a later pass may publish more — its blocks then sweep)
+        }
+    }
+    return BSX_OK;
+}
+
+int HeavyRound::run_round(uint32_t n_round)
+{
+    const int n_groups = b->K.n_groups;
+    HIP_TRY(hipEventRecord(b->ev_sync, b->stream));             // everything queued so far (k_align, earlier rounds)
+    for (int g = 0; g < n_groups; g++) {
+        GroupState &q = G[g];
+        const uint32_t lo = (uint32_t)((uint64_t)n_round * g / n_groups), hi = (uint32_t)((uint64_t)n_round * (g + 1) / n_groups);
+        q.n0 = hi - lo; q.done = q.n0 == 0;
+        memset(&q.H, 0, sizeof(q.H));
+        const uint32_t tcap = b->task_cap / n_groups, toff = tcap * g;
+        q.H.state = b->pool.hstate; q.H.slabs = b->pool.hslabs;
+        q.H.tasks = b->pool.htasks + (size_t)toff * bsx_htask_bytes(); q.H.tout = b->pool.htout + (size_t)toff * bsx_htaskout_bytes();
+        q.H.task_cap = tcap; q.H.list_base = base; q.H.hidx_base = lo;
+        q.blk[0] = b->d_hcnt + (size_t)(2 * g) * BSX_HCNT_BLOCK; q.blk[1] = b->d_hcnt + (size_t)(2 * g + 1) * BSX_HCNT_BLOCK;
+        if (!q.done) n_open++;
+    }
+    for (int depth = 0; depth < 2; depth++) { int rc = enqueue_chunk(); if (rc) return rc; }
+    while (n_open > 0) {
+        int rc = poll();
+        if (rc == BSX_OK && n_open > 0) rc = enqueue_chunk();
+        if (rc) return rc;
+    }
+    for (int g = 0; g < n_groups; g++) {   // the main stream continues behind the last control pass of every group
+        if (G[g].passes == 0) continue;
+        HIP_TRY(hipEventRecord(b->grp[g].ev_ctrl, b->grp[g].s_ctrl));
+        HIP_TRY(hipStreamWaitEvent(b->stream, b->grp[g].ev_ctrl, 0));
+    }
+    return BSX_OK;
+}
+}  // namespace
+
+// heavy pipeline: passes of k_hctrl / k_hscan until every deferred unit is finished (returns once the last pass
+// is queued and known to be the last; units that were not deferred are already complete)
+static int run_heavy(bsx_batch *b, const AlignArgs &A, const AllHitsArgs *ah)
+{
+    HIP_TRY(hipMemcpyAsync(b->h_pinned, b->d_heavy_count, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(stream_wait(b));
+    const uint32_t n_heavy = b->h_pinned[0];
+    b->last_heavy = n_heavy;
+    // (rounds of equal size: the reads of one window and offset that a pass holds are what k_hscan_same groups — a full round followed by
+    //  a short one would scan the short one's candidates in small groups)
+    const uint32_t n_rounds = (n_heavy + b->hcap - 1) / b->hcap, per_round = n_rounds ? (n_heavy + n_rounds - 1) / n_rounds : 0;
+    for (uint32_t base = 0; base < n_heavy; base += per_round) {
+        HeavyRound round{b, A, ah, base};
+        const int rc = round.run_round(std::min(per_round, n_heavy - base));
+        if (rc) return rc;
+    }
+    return BSX_OK;
+}
+
+// deferred units whose small duplicate set overflowed (single-end RRBS only, see k_hctrl): the main kernel redoes them,
+// undeferred, with its large per-wave set
+static int run_redo(bsx_batch *b, const AlignArgs &A, const AllHitsArgs *ah)
+{
+    HIP_TRY(hipMemcpyAsync(b->h_pinned, b->d_redo, 4, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(stream_wait(b));
+    const uint32_t n_redo = b->h_pinned[0];
+    b->last_redo = n_redo;
+    if (!n_redo) return BSX_OK;
+    AlignArgs R = A;
+    R.unit_list = b->d_redo + 1; R.first_unit = 0; R.n_units = n_redo; R.heavy_threshold = 0;
+    HIP_TRY(hipMemsetAsync(b->d_queue, 0, 4, b->stream));
+    bsx_launch_align(R, b->paired, std::min<int>(b->grid_blocks, (int)((n_redo + 3) / 4)), b->stream, ah);
+    HIP_TRY(hipGetLastError());
     return BSX_OK;
 }
 
@@ -872,19 +1105,8 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
     if (n_units == 0 || (uint64_t)first_unit + n_units > b->n_units) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(b->ref->device));
     AlignArgs A;
-    memset(&A, 0, sizeof(A));
-    bsx_fill_devparams(b->ref, A.P);
-    A.n_units = first_unit + n_units; A.first_index = b->first_index; A.debug = b->debug; A.rowcap = b->rowcap; A.kcap = key_cap(b->ref->P, b->rowcap); A.hbits = hset_bits(b->ref->P);
-    A.hkcap = b->hkcap; A.hhbits = BSX_HSET_BITS; A.hslab_bytes = b->hslab_bytes;
-    A.redo_count = b->d_redo; A.redo_list = b->d_redo + 1; A.unit_list = nullptr;
-    A.first_unit = first_unit;
-    for (int m = 0; m < 2; m++) { A.seq[m] = b->d_seq[m]; A.off[m] = b->d_off[m]; A.qual[m] = b->has_qual ? b->d_qual[m] : nullptr; A.cc[m] = b->d_cc[m]; }
-    A.hits_out = b->d_hits; A.pairs_out = b->d_pairs; A.npairs_out = b->d_npairs;
-    A.scratch = b->d_scratch; A.slab_bytes = b->slab_bytes; A.queue = b->d_queue; A.counters = b->d_counters; A.scan_stats = b->d_scan_stats; A.work_counters = (uint32_t)b->work_counters; A.dbg_plan = b->d_dbg; A.dbg_cycles = b->d_cycles; A.dbg_cat = b->d_cycles ? b->d_counters + 24 : nullptr;
-    A.heavy_list = b->d_heavy_list; A.heavy_count = b->d_heavy_count;
-    A.leak_exact = b->leak_exact; A.n_hist = b->leak_exact ? b->n_hist : 0; A.n_units_all = b->n_units;
-    for (int m = 0; m < 2; m++) { A.hist_seq[m] = b->d_hist_seq[m]; A.hist_off[m] = b->d_hist_off[m]; A.hist_qual[m] = b->d_hist_qual[m]; }
-    A.heavy_threshold = heavy_threshold_for(b->ref->P);
+    fill_args(b, A);
+    A.n_units = first_unit + n_units; A.first_unit = first_unit;
     HIP_TRY(hipMemsetAsync(b->d_queue, 0, 4, b->stream));
     HIP_TRY(hipMemsetAsync(b->d_heavy_count, 0, 4, b->stream));
     HIP_TRY(hipMemsetAsync(b->d_redo, 0, 4, b->stream));
@@ -892,7 +1114,7 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
     AllHitsArgs X;   // with a pool attached the emitting twins of the kernels that finish units are launched (bsx_align_ah.hip)
     const AllHitsArgs *ah = b->d_ah_pool ? &X : nullptr;
     if (ah) {
-        X.pool = b->d_ah_pool; X.cap = b->ah_cap; X.cursor = (unsigned long long *)b->d_ah_ctl; X.dropped = (uint32_t *)(b->d_ah_ctl + 1); X.spans = b->d_ah_spans;
+        X.pool = b->d_ah_pool; X.cap = b->ah_cap; X.cursor = (unsigned long long *)b->d_ah_ctl.p; X.dropped = (uint32_t *)(b->d_ah_ctl + 1); X.spans = b->d_ah_spans;
         HIP_TRY(hipMemsetAsync(b->d_ah_ctl, 0, 16, b->stream));
         HIP_TRY(hipMemsetAsync(b->d_ah_spans + (size_t)first_unit * 3, 0, (size_t)n_units * 3 * sizeof(bsx_span), b->stream));
     }
@@ -908,170 +1130,16 @@ extern "C" int bsx_batch_run_range(bsx_batch *b, uint32_t first_unit, uint32_t n
     bsx_launch_align(A, b->paired, b->grid_blocks, b->stream, ah);
     HIP_TRY(hipGetLastError());
     if (b->stage_timing) {
-        if (!b->ev_align) HIP_TRY(hipEventCreate(&b->ev_align));
+        if (!b->ev_align) HIP_TRY(b->ev_align.create());
         HIP_TRY(hipEventRecord(b->ev_align, b->stream));
     }
     b->last_heavy = 0; b->last_heavy_iters = 0; b->last_redo = 0; b->scan_ev_used = 0; b->ctrl_ev_used = 0;
-    if (A.heavy_threshold) {
-        // heavy pipeline: passes of k_hctrl / k_hscan until every deferred unit is finished (this call returns once the last pass
-        // is queued and known to be the last; units that were not deferred are already complete)
-        HIP_TRY(hipMemcpyAsync(b->h_pinned, b->d_heavy_count, 4, hipMemcpyDeviceToHost, b->stream));
-        HIP_TRY(stream_wait(b));
-        const uint32_t n_heavy = b->h_pinned[0];
-        b->last_heavy = n_heavy;
-        // Each round handles up to hcap deferred units, split into unit groups whose passes run out of phase.  One pass of a group =
-        //   k_hctrl (advance every active unit of the group, publish scan tasks)          on the group's high-priority stream
-        //   task order (bsx_launch_task_order) + k_hscan over the published tasks          on the batch's stream
-        // chained by events on the device: the counts a control pass leaves (active units, tasks) stay there — the next control
-        // pass reads its input count from memory, the scan launches are sized for the whole task pool and their surplus blocks exit.
-        // The host enqueues `chunk_passes` passes per group at a time, keeps two such chunks queued ahead, and only looks at a
-        // group's active count once per chunk (polling an event, asleep in between) to learn when the group is finished; passes that were queued
-        // beyond that point find nothing to do.  While k_hscan evaluates the tasks of one group, the control kernels of the others
-        // run beside it — they are latency-bound chains of a few thousand waves.
-        const bool shared_scan = b->ref->P.rrbs != 0;  // RRBS: runs of tasks over one window, scanned together
-        // WGBS: the tasks of one window AND read offset share fetch and shift (k_hscan_same); BSX_SAME=0: one task per wave (k_hscan)
-        // RRBS lists go through the same kernel with BSX_SAME=2 (scan 75.9 against 90.5 ms per step; the step does not move — 142.2 against 141.0 ms —, it
-        // waits for the control passes there: k_hscan_shared stays the default for RRBS)
-        const bool same_scan = b->same_kernel;   // (decided when the batch was created: its group list exists or not)
-        const uint32_t spread = getenv("BSX_SPREAD") ? (uint32_t)atoi(getenv("BSX_SPREAD")) : (same_scan ? (b->same_d ? 2u : 1u) : 0u);   // (2: the offsets a group can span go to one bin)
-        const int n_groups = b->n_groups;
-        struct Group { uint32_t n0 = 0, passes = 0, polls = 0, polled = 0; int cur = 0; bool done = true, tail = false; HeavyArgsRaw H; uint32_t *blk[2]; };
-        volatile uint32_t *pinned = (volatile uint32_t *)b->h_pinned;
-        // (rounds of equal size: the reads of one window and offset that a pass holds are what k_hscan_same groups — a full round followed by
-        //  a short one would scan the short one's candidates in small groups)
-        const uint32_t n_rounds = (n_heavy + b->hcap - 1) / b->hcap, per_round = n_rounds ? (n_heavy + n_rounds - 1) / n_rounds : 0;
-        for (uint32_t base = 0; base < n_heavy; base += per_round) {
-            const uint32_t n_round = std::min(per_round, n_heavy - base);
-            Group G[BSX_MAX_GROUPS];
-            HIP_TRY(hipEventRecord(b->ev_sync, b->stream));             // everything queued so far (k_align, earlier rounds)
-            auto enqueue_pass = [&](int g) -> int {
-                Group &q = G[g];
-                bsx_batch::Group &hw = b->grp[g];
-                uint32_t *in = q.blk[q.cur], *out = q.blk[q.cur ^ 1];
-                const bool fresh = q.passes == 0;
-                if (fresh) {
-                    HIP_TRY(hipStreamWaitEvent(hw.s_ctrl, b->ev_sync, 0));
-                    HIP_TRY(hipMemsetAsync(out, 0, (size_t)BSX_HCNT_BLOCK * 4, hw.s_ctrl));
-                } else HIP_TRY(hipStreamWaitEvent(hw.s_ctrl, hw.ev_scan, 0));  // the scan of the previous pass (its first kernel also cleared `out`)
-                q.H.active_in = b->d_hactive[q.cur] + q.H.hidx_base; q.H.active_out = b->d_hactive[q.cur ^ 1] + q.H.hidx_base;
-                q.H.n_active_in_ptr = in; q.H.n_active_in = q.n0; q.H.n_active_out = out; q.H.n_tasks = out + BSX_HCNT_TASKS; q.H.queue = out + BSX_HCNT_QUEUE;   // (apart: see BSX_HCNT_*)
-                q.H.fresh = fresh ? 1 : 0;
-                while (b->stage_timing && b->ctrl_ev_used + 3 > b->ctrl_ev.size()) { hipEvent_t ev_new = nullptr; HIP_TRY(hipEventCreate(&ev_new)); b->ctrl_ev.push_back(ev_new); }
-                if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used], hw.s_ctrl));
-                // (no more blocks than are resident at once — two per CU by their LDS —: blocks of a high-priority kernel that wait for a slot
-                //  keep the dispatcher from placing the kernels of the normal-priority stream, 300 us per pass when the grid was twice that)
-                bsx_launch_hctrl(A, q.H, b->paired, (int)std::min<uint32_t>((q.n0 + 3) / 4, (uint32_t)b->n_cu * b->hctrl_blocks_per_cu), hw.s_ctrl, ah);
-                HIP_TRY(hipGetLastError());
-                if (b->stage_timing) HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 1], hw.s_ctrl));
-                // scan order of the tasks this pass published, still on the group's stream: done by the time the main stream gets to the scan
-                q.H.order = hw.d_order; q.H.xcd_map = b->xcd_map; q.H.ghead = hw.d_rank; q.H.glist = hw.d_glist;
-                bsx_launch_task_order(q.H, b->bin_shift, b->n_bins, hw.d_bins, hw.d_bstart, hw.d_chunk_tot, hw.d_rank, hw.d_order, in, hw.s_ctrl, spread, same_scan, b->same_d, b->same_r, b->group_tile, b->group_big);
-                // The scan: on the batch's stream with a grid for the whole task pool — or, once the group is in its tail (few tasks per
-                // pass, see the poll loop), behind the control kernel on the group's own high-priority stream with a small grid whose
-                // blocks sweep: beside ANOTHER batch's bulk scans a pool-sized grid of mostly empty blocks only trickles through the
-                // dispatcher, which stretched the tail of the older batch until the younger one's bulk was done — two batches in flight
-                // always finished together, and their transfers never overlapped the other's kernels.
-                if (b->stage_timing) { HIP_TRY(hipEventRecord(b->ctrl_ev[b->ctrl_ev_used + 2], hw.s_ctrl)); b->ctrl_ev_used += 3; }
-                if (b->sig_hist) bsx_sig_hist_pass(q.H, hw.s_ctrl, same_scan, b->group_tile);
-                hipStream_t s_scan = b->stream;
-                if (q.tail) s_scan = hw.s_ctrl;
-                else {
-                    HIP_TRY(hipEventRecord(hw.ev_ctrl, hw.s_ctrl));
-                    HIP_TRY(hipStreamWaitEvent(b->stream, hw.ev_ctrl, 0));
-                }
-                if (b->scan_ev_used + 2 > b->scan_ev.size()) {
-                    hipEvent_t e0, e1;
-                    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-                    b->scan_ev.push_back(e0); b->scan_ev.push_back(e1);
-                }
-                HIP_TRY(hipEventRecord(b->scan_ev[b->scan_ev_used], s_scan));
-                if (same_scan) bsx_launch_hscan_same(A, q.H, s_scan, q.tail ? b->tail_grid_tasks : 0);
-                else if (shared_scan) bsx_launch_hscan_shared(A, q.H, s_scan, q.tail ? b->tail_grid_tasks : 0);
-                else bsx_launch_hscan(A, q.H, s_scan, q.tail ? b->tail_grid_tasks : 0);
-                HIP_TRY(hipGetLastError());
-                if (b->sector_stats) bsx_sector_pass(b->ref, s_scan);
-                HIP_TRY(hipEventRecord(b->scan_ev[b->scan_ev_used + 1], s_scan));
-                b->scan_ev_used += 2;
-                HIP_TRY(hipEventRecord(hw.ev_scan, s_scan));
-                q.cur ^= 1; q.passes++;
-                b->last_heavy_iters++;
-                return BSX_OK;
-            };
-            // one chunk: `chunk_passes` passes of every open group, interleaved pass by pass — the main stream takes the scans in the order
-            // they are queued, and the scan of group g's next pass can only start after that group's control pass, which runs beside
-            // the scans of the other groups — then the counts each group's last control pass of the chunk left: {active units, tasks}
-            auto enqueue_chunk = [&]() -> int {
-                for (int k = 0; k < b->chunk_passes; k++)
-                    for (int g = 0; g < n_groups; g++)
-                        if (!G[g].done) { int rc = enqueue_pass(g); if (rc) return rc; }
-                for (int g = 0; g < n_groups; g++) {
-                    Group &q = G[g];
-                    if (q.done) continue;
-                    const uint32_t slot = q.polls % BSX_POLL_SLOTS;
-                    HIP_TRY(hipMemcpyAsync(b->h_pinned + 32 + 16 * g + 2 * slot, q.blk[q.cur], 4, hipMemcpyDeviceToHost, b->grp[g].s_ctrl));
-                    HIP_TRY(hipMemcpyAsync(b->h_pinned + 32 + 16 * g + 2 * slot + 1, q.blk[q.cur] + BSX_HCNT_TASKS, 4, hipMemcpyDeviceToHost, b->grp[g].s_ctrl));
-                    HIP_TRY(hipEventRecord(b->grp[g].ev_poll[slot], b->grp[g].s_ctrl));
-                    q.polls++;
-                }
-                return BSX_OK;
-            };
-            int n_open = 0;
-            for (int g = 0; g < n_groups; g++) {
-                Group &q = G[g];
-                const uint32_t lo = (uint32_t)((uint64_t)n_round * g / n_groups), hi = (uint32_t)((uint64_t)n_round * (g + 1) / n_groups);
-                q.n0 = hi - lo; q.done = q.n0 == 0;
-                memset(&q.H, 0, sizeof(q.H));
-                const uint32_t tcap = b->task_cap / n_groups, toff = tcap * g;
-                q.H.state = b->d_hstate; q.H.slabs = b->d_hslabs;
-                q.H.tasks = b->d_htasks + (size_t)toff * bsx_htask_bytes(); q.H.tout = b->d_htout + (size_t)toff * bsx_htaskout_bytes();
-                q.H.task_cap = tcap; q.H.list_base = base; q.H.hidx_base = lo;
-                q.blk[0] = b->d_hcnt + (size_t)(2 * g) * BSX_HCNT_BLOCK; q.blk[1] = b->d_hcnt + (size_t)(2 * g + 1) * BSX_HCNT_BLOCK;
-                if (!q.done) n_open++;
-            }
-            for (int depth = 0; depth < 2; depth++) { int rc = enqueue_chunk(); if (rc) return rc; }
-            while (n_open > 0) {
-                for (int g = 0; g < n_groups; g++) {  // the oldest chunk in flight
-                    Group &q = G[g];
-                    if (q.done) continue;
-                    const uint32_t slot = q.polled % BSX_POLL_SLOTS;
-                    HIP_TRY(wait_event(b->grp[g].ev_poll[slot]));
-                    const uint32_t n_act = pinned[32 + 16 * g + 2 * slot], n_tasks = pinned[32 + 16 * g + 2 * slot + 1];
-                    q.polled++;
-                    if (b->trace) fprintf(stderr, "[bsx heavy] paired %d base %u group %d passes %u active %u tasks %u\n", b->paired, base, g, q.polled * b->chunk_passes, n_act, n_tasks);
-                    if (n_act == 0) { q.done = true; n_open--; }  // (passes already queued for this group find no active unit)
-                    else {
-                        // (tested before the tail decision: a stuck unit publishes few tasks per pass — exactly what the tail mode looks like)
-                        if (q.passes > 200000) { g_bsx_err = "heavy pipeline did not converge"; return BSX_ERR_DEVICE; }
-                        if (b->tail_tasks && n_tasks < b->tail_tasks) q.tail = true;  // (the counts are two chunks old: a later pass may publish more — its blocks then sweep)
-                    }
-                }
-                if (n_open > 0) { int rc = enqueue_chunk(); if (rc) return rc; }
-            }
-            for (int g = 0; g < n_groups; g++) {   // the main stream continues behind the last control pass of every group
-                if (G[g].passes == 0) continue;
-                HIP_TRY(hipEventRecord(b->grp[g].ev_ctrl, b->grp[g].s_ctrl));
-                HIP_TRY(hipStreamWaitEvent(b->stream, b->grp[g].ev_ctrl, 0));
-            }
-        }
-    }
-    if (A.heavy_threshold && b->last_heavy) {
-        // deferred units whose small duplicate set overflowed (single-end RRBS only, see k_hctrl): the main kernel redoes them,
-        // undeferred, with its large per-wave set
-        HIP_TRY(hipMemcpyAsync(b->h_pinned, b->d_redo, 4, hipMemcpyDeviceToHost, b->stream));
-        HIP_TRY(stream_wait(b));
-        const uint32_t n_redo = b->h_pinned[0];
-        b->last_redo = n_redo;
-        if (n_redo) {
-            AlignArgs R = A;
-            R.unit_list = b->d_redo + 1; R.first_unit = 0; R.n_units = n_redo; R.heavy_threshold = 0;
-            HIP_TRY(hipMemsetAsync(b->d_queue, 0, 4, b->stream));
-            bsx_launch_align(R, b->paired, std::min<int>(b->grid_blocks, (int)((n_redo + 3) / 4)), b->stream, ah);
-            HIP_TRY(hipGetLastError());
-        }
-    }
+    int rc = A.heavy_threshold ? run_heavy(b, A, ah) : BSX_OK;
+    if (rc == BSX_OK && A.heavy_threshold && b->last_heavy) rc = run_redo(b, A, ah);
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(b->ev1, b->stream));
     b->ran = true;
-    b->ah_ran = b->d_ah_pool != nullptr;
+    b->ah_ran = b->d_ah_pool.p != nullptr;
     return BSX_OK;
 }
 
@@ -1181,7 +1249,7 @@ extern "C" int bsx_batch_counters(bsx_batch *b, uint64_t c[BSX_N_COUNTERS])
 #else
     uint64_t dg[3] = {0, 0, 0};
     for (int i = 0; i < 64; i++) { for (int k = 0; k < 4; k++) c[7 + k] += sh[i * 8 + k]; c[15] += sh[i * 8 + 4]; for (int k = 0; k < 3; k++) dg[k] += sh[i * 8 + 5 + k]; }
-    if (b->sig_hist && c[15]) {
+    if (b->K.sig_hist && c[15]) {
         // (behind the line's own text: what a fetch serves — the harmonic figure, from the groups as formed — and what the tiles of k_task_groups cut; both summed over
         //  the process since the last report, like the histograms)
         unsigned long long gs[4] = {0, 0, 0, 0};
@@ -1223,19 +1291,18 @@ extern "C" int bsx_batch_set_all_hits(bsx_batch *b, uint64_t pool_words)
     HIP_TRY(stream_wait(b));
     if (pool_words == b->ah_cap && (pool_words == 0 || b->d_ah_pool)) return BSX_OK;
     b->ah_ran = false;
-    if (b->d_ah_pool) { (void)hipFree(b->d_ah_pool); b->d_ah_pool = nullptr; b->ah_cap = 0; }
+    b->d_ah_pool.reset(); b->ah_cap = 0;
     if (!pool_words) {
-        if (b->d_ah_ctl) { (void)hipFree(b->d_ah_ctl); b->d_ah_ctl = nullptr; }
-        if (b->d_ah_spans) { (void)hipFree(b->d_ah_spans); b->d_ah_spans = nullptr; }
+        b->d_ah_ctl.reset(); b->d_ah_spans.reset();
         return BSX_OK;
     }
-    if (!b->d_ah_ctl && hipMalloc((void **)&b->d_ah_ctl, 16) != hipSuccess) { (void)hipGetLastError(); return BSX_ERR_NOMEM; }
+    if (b->d_ah_ctl.reserve(16) != hipSuccess) return BSX_ERR_NOMEM;   // (kept from pool to pool, like the spans)
     if (!b->d_ah_spans) {
-        if (hipMalloc((void **)&b->d_ah_spans, (size_t)b->max_units * 3 * sizeof(bsx_span)) != hipSuccess) { (void)hipGetLastError(); b->d_ah_spans = nullptr; return BSX_ERR_NOMEM; }
+        if (b->d_ah_spans.reserve((size_t)b->max_units * 3 * sizeof(bsx_span)) != hipSuccess) return BSX_ERR_NOMEM;
         HIP_TRY(hipMemset(b->d_ah_spans, 0, (size_t)b->max_units * 3 * sizeof(bsx_span)));
     }
     HIP_TRY(hipMemset(b->d_ah_ctl, 0, 16));
-    if (hipMalloc((void **)&b->d_ah_pool, (size_t)pool_words * 4) != hipSuccess) { (void)hipGetLastError(); b->d_ah_pool = nullptr; return BSX_ERR_NOMEM; }
+    if (b->d_ah_pool.reserve((size_t)pool_words * 4) != hipSuccess) return BSX_ERR_NOMEM;
     b->ah_cap = pool_words;
     return BSX_OK;
 }
@@ -1288,7 +1355,7 @@ extern "C" int bsx_batch_debug_hits(bsx_batch *b, uint32_t unit, int mate, int o
     HIP_TRY(hipSetDevice(b->ref->device));
     HIP_TRY(stream_wait(b));
     const uint64_t nclass = (uint64_t)b->ref->P.max_snp_num + 1, rowcap = b->rowcap;
-    const uint64_t mbytes = mate_bytes(b->ref->P, b->rowcap);
+    const uint64_t mbytes = mate_bytes(b->ref->P, b->rowcap, b->kcap, hset_bits(b->ref->P));
     bsx_class_counts cc;
     HIP_TRY(hipMemcpy(&cc, b->d_cc[mate] + unit, sizeof(cc), hipMemcpyDeviceToHost));
     uint32_t n = orient ? cc.n_chit[w] : cc.n_hit[w];
@@ -1306,7 +1373,7 @@ extern "C" int bsx_batch_debug_pairs(bsx_batch *b, uint32_t unit, int w, uint32_
     HIP_TRY(hipSetDevice(b->ref->device));
     HIP_TRY(stream_wait(b));
     const uint64_t rowcap = b->rowcap;
-    const uint64_t mbytes = mate_bytes(b->ref->P, b->rowcap);
+    const uint64_t mbytes = mate_bytes(b->ref->P, b->rowcap, b->kcap, hset_bits(b->ref->P));
     uint16_t np[32];
     HIP_TRY(hipMemcpy(np, b->d_npairs + (size_t)unit * 32, 64, hipMemcpyDeviceToHost));
     uint32_t n = np[w];
@@ -1384,8 +1451,8 @@ extern "C" int bsx_batch_synth_reads_kind(bsx_batch *b, uint32_t n, uint32_t rea
         HIP_TRY(hipMemcpy(b->d_off[m], off.data(), off.size() * 8, hipMemcpyHostToDevice));
     }
     const bool q = kind == 1;  // the trimming workload carries qualities (low-quality 3' tails)
-    int rc = bsx_synth_reads_launch(b->ref, n, read_len, b->paired, seed, first_index, b->d_seq[0], b->d_seq[1], b->stream, kind, q ? b->d_qual[0] : nullptr,
-                                    q && b->paired ? b->d_qual[1] : nullptr);
+    int rc = bsx_synth_reads_launch(b->ref, n, read_len, b->paired, seed, first_index, b->d_seq[0], b->d_seq[1], b->stream, kind, q ? b->d_qual[0].p : nullptr,
+                                    q && b->paired ? b->d_qual[1].p : nullptr);
     if (rc) return rc;
     b->n_units = n; b->first_index = first_index; b->has_qual = q ? 1 : 0; b->leak_meta_valid = false;
     return BSX_OK;

@@ -15,6 +15,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bsx_internal.h"
+#include "bsx_devbuf.h"
 #include "bsx_dev.h"
 
 namespace {
@@ -90,14 +91,6 @@ __global__ void k_context(const uint32_t *__restrict__ skeys, const uint32_t *__
     }
 }
 
-template <class T> struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc(&p, (n ? n : 1) * sizeof(T)) == hipSuccess ? 0 : -1; }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; }
-    T *release() { T *q = p; p = nullptr; return q; }
-};
-
 }  // namespace
 
 // Plane copy of the packed reference for the scan kernels of the heavy pipeline (k_hscan, k_hscan_shared): 2 bits per nt like
@@ -142,8 +135,8 @@ int bsx_index_build_wgbs(bsx_ref *r)
     const uint32_t K = P.total_kmers, nb = (uint32_t)first.size();
     DevBuf<uint32_t> d_off, d_nfwd, d_entries, d_keys, d_skeys, d_vals;
     DevBuf<uint64_t> d_prefix; DevBuf<uint32_t> d_first, d_word0, d_anchor; DevBuf<uint8_t> d_strand; DevBuf<char> d_temp;
-    if (d_off.alloc((size_t)K + 1) || d_nfwd.alloc(K) || d_entries.alloc(total + BSX_ENTRY_PAD) || d_keys.alloc(total) || d_skeys.alloc(total) ||
-        d_vals.alloc(total) || d_prefix.alloc(nb + 1) || d_first.alloc(nb) || d_word0.alloc(nb) || d_anchor.alloc(nb) || d_strand.alloc(nb)) {
+    if (d_off.reserve(((size_t)K + 1) * 4) || d_nfwd.reserve((size_t)K * 4) || d_entries.reserve((total + BSX_ENTRY_PAD) * 4) || d_keys.reserve(total * 4) || d_skeys.reserve(total * 4) ||
+        d_vals.reserve(total * 4) || d_prefix.reserve(((size_t)nb + 1) * 8) || d_first.reserve((size_t)nb * 4) || d_word0.reserve((size_t)nb * 4) || d_anchor.reserve((size_t)nb * 4) || d_strand.reserve(nb)) {
         g_bsx_err = "hipMalloc failed while building the index";
         return BSX_ERR_NOMEM;
     }
@@ -163,7 +156,7 @@ int bsx_index_build_wgbs(bsx_ref *r)
         while ((1ull << bits) < 2ull * K) bits++;
         size_t temp_bytes = 0;
         HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_keys.p, d_skeys.p, d_vals.p, d_entries.p, (size_t)total, 0u, bits, (hipStream_t)0));
-        if (d_temp.alloc(temp_bytes)) { g_bsx_err = "hipMalloc failed for sort workspace"; return BSX_ERR_NOMEM; }
+        if (d_temp.reserve(temp_bytes)) { g_bsx_err = "hipMalloc failed for sort workspace"; return BSX_ERR_NOMEM; }
         HIP_TRY(rocprim::radix_sort_pairs(d_temp.p, temp_bytes, d_keys.p, d_skeys.p, d_vals.p, d_entries.p, (size_t)total, 0u, bits, (hipStream_t)0));
     }
     {
@@ -186,19 +179,19 @@ int bsx_index_build_wgbs(bsx_ref *r)
         if (r->ctx_mode == 1 && hipMemGetInfo(&fr, &tot) == hipSuccess && (uint64_t)fr < ctx_bytes + r->ctx_headroom) want_ctx = false;
     }
     if (want_ctx) {
-        if (d_ctx.alloc((total + BSX_ENTRY_PAD) * 4) == 0) {
-            HIP_TRY(hipMemset(d_ctx.p, 0, (total + BSX_ENTRY_PAD) * 16));
+        if (d_ctx.reserve(ctx_bytes) == hipSuccess) {   // (reserve clears HIP's error itself when it fails)
+            HIP_TRY(hipMemset(d_ctx.p, 0, ctx_bytes));
             const int grid = (int)std::min<uint64_t>((total + 255) / 256, 256 * 32);
             hipLaunchKernelGGL(k_context, dim3(grid), dim3(256), 0, 0, d_skeys.p, d_entries.p, total, r->d_refcat, r->d_crefcat, d_ctx.p);
             HIP_TRY(hipGetLastError());
-        } else (void)hipGetLastError();
+        }
     }
     HIP_TRY(hipDeviceSynchronize());
     if (r->d_bucket_off) (void)hipFree(r->d_bucket_off);
     if (r->d_bucket_nfwd) (void)hipFree(r->d_bucket_nfwd);
     if (r->d_entries) (void)hipFree(r->d_entries);
     if (r->d_ctx) (void)hipFree(r->d_ctx);
-    r->d_bucket_off = d_off.release(); r->d_bucket_nfwd = d_nfwd.release(); r->d_entries = d_entries.release(); r->d_ctx = d_ctx.release();
+    r->d_bucket_off = d_off.detach(); r->d_bucket_nfwd = d_nfwd.detach(); r->d_entries = d_entries.detach(); r->d_ctx = d_ctx.detach();
     r->ctx_bytes = r->d_ctx ? ctx_bytes : 0;
     r->n_entries = total;
     r->has_index = true;
@@ -275,21 +268,21 @@ int bsx_index_build_rrbs(bsx_ref *r, const std::vector<uint32_t> &refcat, const 
     for (uint32_t c = 0; c < r->n_chr; c++) { site_off[c + 1] = site_off[c] + (uint32_t)r->sites[c].size(); sites_flat.insert(sites_flat.end(), r->sites[c].begin(), r->sites[c].end()); }
     sites_flat.push_back(0);  // one-past-the-end read of the reference (dbseq.cpp:562) lands on a defined 0
     DevBuf<uint32_t> d_off, d_nfwd, d_ent, d_sites, d_soff;
-    if (d_off.alloc((size_t)K + 1) || d_nfwd.alloc(K) || d_ent.alloc(ent.size()) || d_sites.alloc(sites_flat.size()) || d_soff.alloc(site_off.size()))
+    if (d_off.reserve(((size_t)K + 1) * 4) || d_nfwd.reserve((size_t)K * 4) || d_ent.reserve(ent.size() * 4) || d_sites.reserve(sites_flat.size() * 4) || d_soff.reserve(site_off.size() * 4))
         return BSX_ERR_NOMEM;
     HIP_TRY(hipMemcpy(d_off.p, off.data(), ((size_t)K + 1) * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(d_nfwd.p, 0, (size_t)K * 4));
     HIP_TRY(hipMemcpy(d_ent.p, grouped ? gent.data() : ent.data(), ent.size() * 4, hipMemcpyHostToDevice));
     if (grouped) {
         DevBuf<uint32_t> d_goff;
-        if (d_goff.alloc(goff.size())) return BSX_ERR_NOMEM;
+        if (d_goff.reserve(goff.size() * 4)) return BSX_ERR_NOMEM;
         HIP_TRY(hipMemcpy(d_goff.p, goff.data(), goff.size() * 4, hipMemcpyHostToDevice));
-        r->d_rrbs_goff = d_goff.release();
+        r->d_rrbs_goff = d_goff.detach();
     }
     HIP_TRY(hipMemcpy(d_sites.p, sites_flat.data(), sites_flat.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_soff.p, site_off.data(), site_off.size() * 4, hipMemcpyHostToDevice));
-    r->d_bucket_off = d_off.release(); r->d_bucket_nfwd = d_nfwd.release(); r->d_entries = d_ent.release();
-    r->d_sites = d_sites.release(); r->d_site_off = d_soff.release();
+    r->d_bucket_off = d_off.detach(); r->d_bucket_nfwd = d_nfwd.detach(); r->d_entries = d_ent.detach();
+    r->d_sites = d_sites.detach(); r->d_site_off = d_soff.detach();
     {   // where a position's 4 kb bin starts in its chromosome's site list: the fragment-size filter's search (ccgg_seglen) starts there
         std::vector<uint32_t> bin_off(r->n_chr + 1, 0), bins;
         for (uint32_t c = 0; c < r->n_chr; c++) {
@@ -305,10 +298,10 @@ int bsx_index_build_rrbs(bsx_ref *r, const std::vector<uint32_t> &refcat, const 
             }
         }
         DevBuf<uint32_t> d_bin, d_boff;
-        if (d_bin.alloc(bins.size()) || d_boff.alloc(bin_off.size())) return BSX_ERR_NOMEM;
+        if (d_bin.reserve(bins.size() * 4) || d_boff.reserve(bin_off.size() * 4)) return BSX_ERR_NOMEM;
         HIP_TRY(hipMemcpy(d_bin.p, bins.data(), bins.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_boff.p, bin_off.data(), bin_off.size() * 4, hipMemcpyHostToDevice));
-        r->d_site_bin = d_bin.release(); r->d_site_bin_off = d_boff.release();
+        r->d_site_bin = d_bin.detach(); r->d_site_bin_off = d_boff.detach();
     }
     r->n_entries = off[K];
     r->has_index = true;

@@ -52,43 +52,12 @@
 #include "bsx_meth_epi.h"
 #include "bsx_meth_parse.h"
 #include "bsx_meth_text.h"
+#include "bsx_devbuf.h"
 #include "bsx_meth_tiles.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-// Device memory that owns itself: freed when it goes out of scope or with the handle it is a member of (bsx_meth_destroy makes the handle's device current
-// first).  A failed allocation leaves it empty and returns HIP's error, for HIP_TRY or a message of the caller's own.
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;  // bytes
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    // at least `bytes` of it; a buffer that is large enough stays (with its contents), a smaller one is replaced (without them)
-    hipError_t reserve(size_t bytes)
-    {
-        if (p && bytes <= cap) return hipSuccess;
-        release();
-        const hipError_t e = hipMalloc((void **)&p, bytes ? bytes : 1);
-        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; return e; }
-        cap = bytes;
-        return hipSuccess;
-    }
-    // `bytes` of zeroes, ready when it returns; on `stream`, so that it does not wait for the null stream
-    hipError_t zeroed(size_t bytes, hipStream_t stream)
-    {
-        hipError_t e = reserve(bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(p, 0, bytes, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) release();
-        return e;
-    }
-};
 
 struct MethDev {
     const uint8_t *ref;      // all chromosomes, upper-case letters, concatenated
@@ -1043,7 +1012,7 @@ static int meth_scan_u32(bsx_meth *m, uint32_t *in, uint32_t *out, size_t n)
 // ---- the CpG index of the epiallele tally ----
 static void meth_epi_drop_index(bsx_meth *m)
 {
-    m->d_cpg_dir.release(); m->d_cpg_pos.release(); m->d_epi.release();
+    m->d_cpg_dir.reset(); m->d_cpg_pos.reset(); m->d_epi.reset();
     m->cpg_first.clear();
     m->cpg_built = false; m->epi_last_rows = 0;
 }
@@ -1196,7 +1165,7 @@ extern "C" int bsx_meth_set_mbias(bsx_meth *m, int on)
     if (!m) return BSX_ERR_ARG;
     if (m->index_base) { g_bsx_err = "bsx_meth_set_mbias after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!on) m->d_mbias.release();
+    if (!on) m->d_mbias.reset();
     else if (!m->d_mbias.p) HIP_TRY(m->d_mbias.zeroed((MB_CELLS + 1) * 8, m->stream));
     return BSX_OK;
 }
@@ -1207,7 +1176,7 @@ extern "C" int bsx_meth_set_ct_snp(bsx_meth *m, int mode)
     if ((mode != 0) == (m->snp != 0)) { m->snp = mode; return BSX_OK; }  // 1 <-> 2 at any time: the counters are the same
     if (m->index_base) { g_bsx_err = "bsx_meth_set_ct_snp on or off after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!mode) m->d_rev.release();
+    if (!mode) m->d_rev.reset();
     else HIP_TRY(m->d_rev.zeroed((size_t)(m->chr_off.back() + 16) * 8, m->stream));
     m->snp = mode;
     return BSX_OK;
@@ -1480,7 +1449,7 @@ extern "C" int bsx_meth_set_read_stats(bsx_meth *m, int on)
     if (!m) return BSX_ERR_ARG;
     if (m->index_base) { g_bsx_err = "bsx_meth_set_read_stats after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!on) m->d_hist.release();
+    if (!on) m->d_hist.reset();
     else if (!m->d_hist.p) HIP_TRY(m->d_hist.zeroed(RS_CELLS * 8, m->stream));
     return BSX_OK;
 }
@@ -1527,7 +1496,7 @@ extern "C" int bsx_meth_set_pdr(bsx_meth *m, uint32_t min_cpg)
     if ((min_cpg != 0) == (m->d_pdr.p != nullptr)) { m->min_cpg = min_cpg; return BSX_OK;}  // another threshold at any time: the cells are the same
     if (m->index_base) { g_bsx_err = "bsx_meth_set_pdr on or off after alignments have been added"; return BSX_ERR_STATE; }
     HIP_TRY(hipSetDevice(m->device));
-    if (!min_cpg) m->d_pdr.release();
+    if (!min_cpg) m->d_pdr.reset();
     else HIP_TRY(m->d_pdr.zeroed((size_t)(m->chr_off.back() + 16) * 8, m->stream));
     m->min_cpg = min_cpg;
     return BSX_OK;

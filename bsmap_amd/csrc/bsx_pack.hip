@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "bsx_cpus.h"
+#include "bsx_devbuf.h"
 #include "bsx_internal.h"
 
 namespace {
@@ -189,21 +190,20 @@ int bsx_pack_fasta_device(const bsx_params &P, const char *text, uint64_t n, bsx
         code_r[c] = P.bit_nt[k < 0 ? 3 : 3 - k];      // rev_alphabet[]: unknown -> code of 'T'
     }
     HIP_TRY(hipSetDevice(r.device));
-    unsigned char *d_text = nullptr, *d_codes = nullptr;
-    FaRec *d_recs = nullptr;
-    uint32_t *d_bad = nullptr, *d_nev = nullptr;
-    u64 *d_ev = nullptr;
+    // the temporaries, and the packed words until they are known to be good (then they go to r): every return below frees what is left in these
+    DevBuf<unsigned char> d_text, d_codes;
+    DevBuf<FaRec> d_recs;
+    DevBuf<uint32_t> d_bad, d_nev, d_words;
+    DevBuf<u64> d_ev;
     const uint32_t EV_CAP = 1u << 22;
-    auto cleanup = [&] { for (void *q : {(void *)d_text, (void *)d_codes, (void *)d_recs, (void *)d_bad, (void *)d_nev, (void *)d_ev}) if (q) (void)hipFree(q); };
-    auto fail = [&](int code) { cleanup(); if (r.d_refcat) { (void)hipFree(r.d_refcat); r.d_refcat = r.d_crefcat = nullptr; } return code; };
     // (no room for the text beside what the device already holds — several lanes on one GPU, a shared device: not an error, the host packer needs none of it)
-#define PK_TRY(x) do { hipError_t e_ = (x); if (e_ == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(1); } if (e_ != hipSuccess) return fail(bsx_hip_fail(e_, #x, __FILE__, __LINE__)); } while (0)
-    PK_TRY(hipMalloc((void **)&d_text, n + 64));
-    PK_TRY(hipMalloc((void **)&d_codes, 512));
-    PK_TRY(hipMalloc((void **)&d_recs, (size_t)n_rec * sizeof(FaRec)));
-    PK_TRY(hipMalloc((void **)&d_bad, (size_t)n_rec * 4));
-    PK_TRY(hipMalloc((void **)&d_nev, 4));
-    PK_TRY(hipMalloc((void **)&d_ev, (size_t)EV_CAP * 8));
+#define PK_TRY(x) do { hipError_t e_ = (x); if (e_ == hipErrorOutOfMemory) { (void)hipGetLastError(); return 1; } if (e_ != hipSuccess) return bsx_hip_fail(e_, #x, __FILE__, __LINE__); } while (0)
+    PK_TRY(d_text.reserve(n + 64));
+    PK_TRY(d_codes.reserve(512));
+    PK_TRY(d_recs.reserve((size_t)n_rec * sizeof(FaRec)));
+    PK_TRY(d_bad.reserve((size_t)n_rec * 4));
+    PK_TRY(d_nev.reserve(4));
+    PK_TRY(d_ev.reserve((size_t)EV_CAP * 8));
     const double t_alloc = now();
     // (one hipMemcpy from the mapping: 9.5 GB/s, 0.33 s at hg38 size.  Page-locked staging buffers filled by six threads with a stream each were tried and are
     //  SLOWER inside the command line — 0.89 s: their hipHostMalloc calls queue behind the gigabytes the command line is page-locking for its ring at that moment)
@@ -215,28 +215,29 @@ int bsx_pack_fasta_device(const bsx_params &P, const char *text, uint64_t n, bsx
     PK_TRY(hipMemset(d_bad, 0, (size_t)n_rec * 4));
     PK_TRY(hipMemset(d_nev, 0, 4));
     const dim3 grid(1024, std::min<uint32_t>(n_rec, 64));
-    hipLaunchKernelGGL(k_fa_check, grid, dim3(256), 0, 0, d_text, d_recs, n_rec, d_bad);
+    hipLaunchKernelGGL(k_fa_check, grid, dim3(256), 0, 0, d_text.p, d_recs.p, n_rec, d_bad.p);
     PK_TRY(hipGetLastError());
     std::vector<uint32_t> bad(n_rec);
     PK_TRY(hipMemcpy(bad.data(), d_bad, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
-    for (uint32_t v : bad) if (v) { cleanup(); return 1; }   // an irregular record: the host packer applies the token rules
+    for (uint32_t v : bad) if (v) return 1;   // an irregular record: the host packer applies the token rules
     r.n_words = words + 2 * BSX_REF_MARGIN;
     // 64 spare words behind each copy; both strand copies in one allocation, the rc copy right behind the forward one (bsx_api.hip: finish_ref_upload)
-    PK_TRY(hipMalloc((void **)&r.d_refcat, 2 * (r.n_words + 64) * 4));
-    r.d_crefcat = r.d_refcat + r.n_words + 64;
-    PK_TRY(hipMemset(r.d_refcat, 0, 2 * (r.n_words + 64) * 4));
-    hipLaunchKernelGGL(k_fa_pack, grid, dim3(256), 0, 0, d_text, d_recs, n_rec, d_codes, d_codes + 256, r.d_refcat, r.d_crefcat);
+    PK_TRY(d_words.reserve(2 * (r.n_words + 64) * 4));
+    PK_TRY(hipMemset(d_words, 0, 2 * (r.n_words + 64) * 4));
+    hipLaunchKernelGGL(k_fa_pack, grid, dim3(256), 0, 0, d_text.p, d_recs.p, n_rec, d_codes.p, d_codes.p + 256, d_words.p, d_words.p + r.n_words + 64);
     PK_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_fa_runs, grid, dim3(256), 0, 0, d_text, d_recs, n_rec, d_ev, EV_CAP, d_nev);
+    hipLaunchKernelGGL(k_fa_runs, grid, dim3(256), 0, 0, d_text.p, d_recs.p, n_rec, d_ev.p, EV_CAP, d_nev.p);
     PK_TRY(hipGetLastError());
     uint32_t nev = 0;
     PK_TRY(hipMemcpy(&nev, d_nev, 4, hipMemcpyDeviceToHost));
-    if (nev > EV_CAP) return fail(1);   // a reference with millions of N / X stretches: the host packer
+    if (nev > EV_CAP) return 1;   // a reference with millions of N / X stretches: the host packer
     std::vector<u64> ev(nev);
     if (nev) PK_TRY(hipMemcpy(ev.data(), d_ev, (size_t)nev * 8, hipMemcpyDeviceToHost));
     PK_TRY(hipDeviceSynchronize());
-    cleanup();
 #undef PK_TRY
+    r.d_refcat = d_words.detach();
+    r.d_crefcat = r.d_refcat + r.n_words + 64;
+    d_text.reset(); d_codes.reset(); d_recs.reset(); d_bad.reset(); d_nev.reset(); d_ev.reset();   // (now, not at the return: the text is as large as the reference, and the host tables come first)
     const double t_kern = now();
     std::sort(ev.begin(), ev.end());
     // ---- host tables (bsx_pack_fasta's, from the same quantities)

@@ -2,6 +2,7 @@
 // measured ceiling"): a streaming read, a streaming copy and the access pattern the scan kernels are made of — 16-byte
 // loads at random 4-byte-aligned addresses.  bench.py puts the three rates into roofline.peak_measured; nothing on the
 // alignment path calls this.
+#include "bsx_devbuf.h"
 #include "bsx_internal.h"
 
 namespace {
@@ -64,14 +65,15 @@ extern "C" int bsx_probe_memory(int device, uint64_t bytes, uint64_t gather_wind
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     const u64 n16 = bytes / 16;
-    uint4 *a = nullptr, *b = nullptr;
-    uint32_t *sink = nullptr;
-    HIP_TRY(hipMalloc((void **)&a, n16 * 16));
-    if (hipMalloc((void **)&b, n16 * 16) != hipSuccess) { (void)hipFree(a); return BSX_ERR_NOMEM; }
-    if (hipMalloc((void **)&sink, 256) != hipSuccess) { (void)hipFree(a); (void)hipFree(b); return BSX_ERR_NOMEM; }
+    DevBuf<uint4> buf_a, buf_b;
+    DevBuf<uint32_t> buf_sink;
+    HIP_TRY(buf_a.reserve(n16 * 16));
+    if (buf_b.reserve(n16 * 16) != hipSuccess || buf_sink.reserve(256) != hipSuccess) return BSX_ERR_NOMEM;
+    uint4 *const a = buf_a, *const b = buf_b;
+    uint32_t *const sink = buf_sink;
     const int grid = prop.multiProcessorCount * 8;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    DevEvent e0, e1;
+    HIP_TRY(e0.create()); HIP_TRY(e1.create());
     hipLaunchKernelGGL(k_probe_fill, dim3(grid), dim3(256), 0, 0, a, n16);
     hipLaunchKernelGGL(k_probe_fill, dim3(grid), dim3(256), 0, 0, b, n16);
     auto timed = [&](auto launch, int reps, float &best) -> int {
@@ -98,7 +100,5 @@ extern "C" int bsx_probe_memory(int device, uint64_t bytes, uint64_t gather_wind
     const double loads = (double)ggrid * 256.0 * per_lane;
     if (rc == BSX_OK && gather16_GBps) *gather16_GBps = loads * 16.0 / (ms * 1e-3) / 1e9;
     if (rc == BSX_OK && gather16_Gloads_per_s) *gather16_Gloads_per_s = loads / (ms * 1e-3) / 1e9;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(sink);
     return rc;
 }

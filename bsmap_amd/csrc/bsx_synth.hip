@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "bsx_devbuf.h"
 #include "bsx_internal.h"
 
 namespace {
@@ -323,16 +324,18 @@ extern "C" int bsx_ref_create_synthetic(const bsx_params *p, uint32_t n_chr, con
     std::sort(r->blocks.begin(), r->blocks.end(), [](const Block &a, const Block &b) { return a.id < b.id || (a.id == b.id && a.begin < b.begin); });
     r->n_words = words + 2 * BSX_REF_MARGIN;
     auto fail = [&](int rc) { bsx_ref_destroy(r); return rc; };
-    if (hipMalloc((void **)&r->d_refcat, 2 * (r->n_words + 64) * 4) != hipSuccess) return fail(BSX_ERR_NOMEM);  // one allocation, see finish_ref_upload
-    r->d_crefcat = r->d_refcat + r->n_words + 64;
-    if (hipMemset(r->d_refcat, 0, 2 * (r->n_words + 64) * 4) != hipSuccess) return fail(BSX_ERR_DEVICE);
+    DevBuf<uint32_t> d_words;   // both strand copies, r's once they are filled
+    if (d_words.reserve(2 * (r->n_words + 64) * 4) != hipSuccess) return fail(BSX_ERR_NOMEM);  // one allocation, see finish_ref_upload
+    if (hipMemset(d_words, 0, 2 * (r->n_words + 64) * 4) != hipSuccess) return fail(BSX_ERR_DEVICE);
     const uint32_t bnp = p->bit_nt[0] | (p->bit_nt[1] << 8) | (p->bit_nt[2] << 16) | ((uint32_t)p->bit_nt[3] << 24);
     for (uint32_t c = 0; c < n_chr; c++) {
         const uint32_t nw = r->rc_offset[c] / 16, w0 = r->anchor[c] / 16;
         const int grid = (int)std::min<uint32_t>((nw + 255) / 256, 256 * 16);
-        hipLaunchKernelGGL(k_synth_pack, dim3(grid), dim3(256), 0, 0, (u64)seed, c, chr_len[c], nw, bnp, r->d_refcat + w0, r->d_crefcat + w0);
+        hipLaunchKernelGGL(k_synth_pack, dim3(grid), dim3(256), 0, 0, (u64)seed, c, chr_len[c], nw, bnp, d_words.p + w0, d_words.p + r->n_words + 64 + w0);
     }
     if (hipDeviceSynchronize() != hipSuccess) return fail(BSX_ERR_DEVICE);
+    r->d_refcat = d_words.detach();
+    r->d_crefcat = r->d_refcat + r->n_words + 64;
     { const int prc = bsx_planes_build(r); if (prc != BSX_OK) return fail(prc); }
     if (hipMalloc((void **)&r->d_anchor, r->anchor.size() * 4) != hipSuccess || hipMalloc((void **)&r->d_chr_size, n_chr * 4) != hipSuccess ||
         hipMalloc((void **)&r->d_rc_offset, n_chr * 4) != hipSuccess) return fail(BSX_ERR_NOMEM);
@@ -348,12 +351,10 @@ extern "C" int bsx_synth_chr_text(const bsx_ref *r, uint32_t c, uint32_t from, u
 {
     if (!r || c >= r->n_chr || !out || (uint64_t)from + n > r->chr_size[c]) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(r->device));
-    char *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, n ? n : 1));
-    hipLaunchKernelGGL(k_synth_text, dim3(std::min<uint32_t>((n + 255) / 256, 4096)), dim3(256), 0, 0, (u64)r->synth_seed, c, r->chr_size[c], from, n, d);
-    hipError_t e = hipMemcpy(out, d, n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIP_TRY(e);
+    DevBuf<char> d;
+    HIP_TRY(d.reserve(n));
+    hipLaunchKernelGGL(k_synth_text, dim3(std::min<uint32_t>((n + 255) / 256, 4096)), dim3(256), 0, 0, (u64)r->synth_seed, c, r->chr_size[c], from, n, d.p);
+    HIP_TRY(hipMemcpy(out, d, n, hipMemcpyDeviceToHost));
     return BSX_OK;
 }
 
@@ -371,9 +372,9 @@ int bsx_synth_reads_launch(const bsx_ref *r, uint32_t n, uint32_t read_len, int 
         prefix.push_back(prefix.back() + (b.end - b.begin - span));
     }
     if (gpos.empty()) { g_bsx_err = "reference has no block long enough to sample reads from"; return BSX_ERR_STATE; }
-    uint32_t *d_gpos = nullptr; u64 *d_prefix = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_gpos, gpos.size() * 4));
-    HIP_TRY(hipMalloc((void **)&d_prefix, prefix.size() * 8));
+    DevBuf<uint32_t> d_gpos; DevBuf<u64> d_prefix;
+    HIP_TRY(d_gpos.reserve(gpos.size() * 4));
+    HIP_TRY(d_prefix.reserve(prefix.size() * 8));
     HIP_TRY(hipMemcpy(d_gpos, gpos.data(), gpos.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_prefix, prefix.data(), prefix.size() * 8, hipMemcpyHostToDevice));
     ReadGen g;
@@ -383,8 +384,6 @@ int bsx_synth_reads_launch(const bsx_ref *r, uint32_t n, uint32_t read_len, int 
     g.kind = (uint32_t)kind; g.sites = r->d_sites; g.site_off = r->d_site_off; g.anchor = r->d_anchor; g.n_chr = r->n_chr;
     g.digest_len = (uint32_t)strlen(r->P.digest_site); g.digest_pos = (uint32_t)r->P.digest_pos;
     hipLaunchKernelGGL(k_synth_reads, dim3(std::min<uint32_t>((n + 255) / 256, 256 * 16)), dim3(256), 0, stream, g, n, d_seq_a, d_seq_b, d_qual_a, d_qual_b);
-    hipError_t e = hipStreamSynchronize(stream);
-    (void)hipFree(d_gpos); (void)hipFree(d_prefix);
-    HIP_TRY(e);
+    HIP_TRY(hipStreamSynchronize(stream));
     return BSX_OK;
 }
