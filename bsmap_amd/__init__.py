@@ -78,6 +78,8 @@ EXPORTS = [
     "bsx_meth_set_pdr", "bsx_meth_pdr_report_chr", "bsx_meth_pdr_fetch_rows", "bsx_meth_write_pdr",
     "bsx_meth_set_epi", "bsx_meth_n_cpg", "bsx_meth_epi_report_chr", "bsx_meth_epi_fetch_rows", "bsx_meth_write_epi",
     "bsx_meth_diff_report_chr", "bsx_meth_diff_fetch_rows", "bsx_meth_write_diff", "bsx_meth_diff_regions", "bsx_meth_write_diff_regions", "bsx_meth_write_diff_bins",
+    "bsx_meth_bh", "bsx_meth_diff_report_all", "bsx_meth_diff_fetch_all", "bsx_meth_diff_dmrs", "bsx_meth_diff_fetch_dmrs", "bsx_meth_write_diff_fdr",
+    "bsx_meth_write_diff_regions_fdr", "bsx_meth_write_dmrs",
 ]
 
 

@@ -19,6 +19,9 @@
 // and one host path, meth_compact (count, scan, size, emit).  A new per-position or per-window report is a rule struct and two wrappers.
 // Two handles at once (differential methylation): k_diff_count / k_diff_emit (DiffRule: the common sites of two samples whose ratios differ),
 //   k_meth_fisher (the two-sided Fisher exact test of every row, bsx_meth_diff.h) and k_meth_diff_regions (the joint form of k_meth_regions; bins are intervals)
+// Over the rows of all sequences at once (the store of bsx_meth_diff_report_all): k_bh_keys / k_bh_ratio / k_bh_scatter around a radix sort and a
+//   running minimum (Benjamini-Hochberg q-values), k_cand_count / k_cand_emit (CandRule) and k_head_count / k_head_emit (HeadRule) on the same compaction with store
+//   rows and candidates as items, and k_dmr_runs (a thread per run: de novo DMRs)
 // One place per idea elsewhere too: meth_forward_call (what a forward call is), meth_chr_of / meth_is_cpg (which chromosome, which CpG), meth_covered (the row
 // rule), meth_site (a site's five values); on the host DevBuf (device memory that owns itself), OutFile, guarded (no exception across the C ABI), format_rows,
 // sorted_chromosomes, and the row formatters of bsx_meth_text.h and bsx_meth_epi.h.
@@ -867,9 +870,7 @@ struct DiffRule {
     __device__ __forceinline__ bool row(u64 k, Row &w) const
     {
         if (!diff_site(A, B, g0, n, k, R, w.dA, w.mA, w.dB, w.mB)) return false;
-        const u64 x = (u64)w.mA * w.dB, y = (u64)w.mB * w.dA, diff = x > y ? x - y : y - x, dd = (u64)w.dA * w.dB;
-        const u64 lhi = __umul64hi(diff, 1000ull), llo = diff * 1000ull, rhi = __umul64hi(dd, (u64)permille), rlo = dd * (u64)permille;
-        return lhi > rhi || (lhi == rhi && llo >= rlo);
+        return bsx_meth_diff::delta_keeps(w.mA, w.dA, w.mB, w.dB, permille);
     }
     __device__ __forceinline__ void store(u64 o, u64 k, const Row &w) const
     {
@@ -949,9 +950,147 @@ __global__ __launch_bounds__(REGION_WAVES * 64) void k_meth_diff_regions(MethDev
     for (int q = 0; q < 5; q++) atomicAdd(&out[q], tot[q]);
 }
 
+// ---- Benjamini-Hochberg q-values (bsx_meth_bh and the store of bsx_meth_diff_report_all) ----
+// The key of a p-value is its bit pattern (p >= 0: the order of the bits is the order of the values; -0.0 counts as 0.0); a NaN is outside the family and
+// gets the largest key, so that the sort leaves the family in front.  nan_count: one integer add per block that holds a NaN.
+constexpr u64 BH_NAN_KEY = ~0ull;
+
+__global__ __launch_bounds__(256) void k_bh_keys(const double *p, u64 n, u64 *keys, uint32_t *idx, u64 *nan_count)
+{
+    __shared__ uint32_t s_nan;
+    if (threadIdx.x == 0) s_nan = 0;
+    __syncthreads();
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    bool nan = false;
+    if (i < n) {
+        const double x = p[i];
+        nan = x != x;
+        keys[i] = nan ? BH_NAN_KEY : (x == 0.0 ? 0ull : (u64)__double_as_longlong(x));
+        idx[i] = (uint32_t)i;
+    }
+    const u64 bal = __ballot(nan);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&s_nan, (uint32_t)__builtin_popcountll(bal));
+    __syncthreads();
+    if (threadIdx.x == 0 && s_nan) atomicAdd(nan_count, (u64)s_nan);
+}
+
+// r_k = (p_(k) n_fam) / k for the k-th smallest p of a family of n_fam = n - *nan_count, k from 1: two roundings, the product first (no contraction is
+// possible between a product and a quotient; the intrinsics say so).  Written back to front, r[n - 1 - j] for the sorted place j = k - 1, so that the
+// suffix minimum of the definition is a forward inclusive scan; the places of the NaN keys, which are in front then, hold +inf.
+__global__ __launch_bounds__(256) void k_bh_ratio(const u64 *sorted_keys, u64 n, const u64 *nan_count, double *r_rev)
+{
+    const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const u64 n_fam = n - *nan_count;
+    r_rev[n - 1 - j] = j < n_fam ? __ddiv_rn(__dmul_rn(__longlong_as_double((long long)sorted_keys[j]), (double)n_fam), (double)(j + 1))
+                                 : __longlong_as_double(0x7ff0000000000000ll);
+}
+
+// q of the row at sorted place j: min(1, the suffix minimum at j), NaN outside the family.  Every row is written once: plain stores.
+__global__ __launch_bounds__(256) void k_bh_scatter(const double *min_rev, const uint32_t *sorted_idx, u64 n, const u64 *nan_count, double *q)
+{
+    const u64 j = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const double v = min_rev[n - 1 - j];
+    q[sorted_idx[j]] = j < n - *nan_count ? (v < 1.0 ? v : 1.0) : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+struct MinDouble {
+    __host__ __device__ double operator()(double a, double b) const { return b < a ? b : a; }
+};
+
+// ---- de novo DMRs over the store (bsx_meth_diff_dmrs) ----
+// The store of bsx_meth_diff_report_all as the kernels see it: row_start[n_seq + 1] in the writer's sequence order, per row pos, counts and q
+struct StoreDev {
+    const uint32_t *row_start, *pos;
+    const uint4 *counts;
+    const double *q;
+    uint32_t n_seq;
+};
+
+// A CANDIDATE is a row of the store with q <= max_q that passes the delta rule and whose ratios differ (sign != 0).  Items are store rows.  Payload: the
+// row's position and key = (rank of its sequence in the writer's order) * 2 + (1 where B's ratio is the higher one): two candidates may share a
+// run only under one key.
+struct CandRule {
+    struct Row { uint32_t key; };
+    StoreDev S;
+    double max_q;
+    uint32_t permille;
+    uint32_t *out_key, *out_pos;
+    __device__ __forceinline__ bool row(u64 i, Row &w) const
+    {
+        const uint4 c = S.counts[i];
+        const int s = bsx_meth_diff::delta_sign(c.x, c.y, c.z, c.w);
+        w.key = s > 0 ? 1u : 0u;
+        return s != 0 && S.q[i] <= max_q && bsx_meth_diff::delta_keeps(c.x, c.y, c.z, c.w, permille);
+    }
+    __device__ __forceinline__ void store(u64 o, u64 i, const Row &w) const
+    {
+        uint32_t lo = 0, hi = S.n_seq;  // the sequence with row_start[lo] <= i < row_start[lo + 1]: the last lo with row_start[lo] <= i
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (S.row_start[mid] <= (uint32_t)i) lo = mid; else hi = mid;
+        }
+        out_key[o] = lo * 2 + w.key; out_pos[o] = S.pos[i];
+    }
+};
+
+__global__ __launch_bounds__(256) void k_cand_count(StoreDev S, u64 n, double max_q, uint32_t permille, uint32_t *blk_rows)
+{
+    CandRule rule{S, max_q, permille, nullptr, nullptr};
+    compact_count(rule, n, blk_rows);
+}
+
+__global__ __launch_bounds__(256) void k_cand_emit(StoreDev S, u64 n, double max_q, uint32_t permille, const uint32_t *blk_start, uint32_t *out_key, uint32_t *out_pos)
+{
+    CandRule rule{S, max_q, permille, out_key, out_pos};
+    compact_emit(rule, n, blk_start);
+}
+
+// Candidate j is the HEAD of a run when it is the first one, or its key differs from its predecessor's (another sequence or another direction), or it lies
+// more than max_gap nt behind it (positions ascend within a key).  Items are candidates; payload: the candidate's index.
+struct HeadRule {
+    struct Row {};
+    const uint32_t *key, *pos;
+    uint32_t max_gap;
+    uint32_t *out_head;
+    __device__ __forceinline__ bool row(u64 j, Row &) const { return j == 0 || key[j] != key[j - 1] || pos[j] - pos[j - 1] > max_gap; }
+    __device__ __forceinline__ void store(u64 o, u64 j, const Row &) const { out_head[o] = (uint32_t)j; }
+};
+
+__global__ __launch_bounds__(256) void k_head_count(const uint32_t *key, const uint32_t *pos, u64 n, uint32_t max_gap, uint32_t *blk_rows)
+{
+    HeadRule rule{key, pos, max_gap, nullptr};
+    compact_count(rule, n, blk_rows);
+}
+
+__global__ __launch_bounds__(256) void k_head_emit(const uint32_t *key, const uint32_t *pos, u64 n, uint32_t max_gap, const uint32_t *blk_start, uint32_t *out_head)
+{
+    HeadRule rule{key, pos, max_gap, out_head};
+    compact_emit(rule, n, blk_start);
+}
+
+// A thread per run: the candidates [head[o], head[o + 1]) (the last run ends with the last candidate) as (sequence id, start, end, n_sig), the span
+// [pos_first, pos_last + 1).  order[rank]: the sequence id at a rank of the writer's order.
+__global__ __launch_bounds__(256) void k_dmr_runs(const uint32_t *head, uint32_t n_runs, uint32_t n_cand, const uint32_t *key, const uint32_t *pos, const uint32_t *order,
+                                                  uint4 *runs)
+{
+    const uint32_t o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= n_runs) return;
+    const uint32_t first = head[o], last = (o + 1 < n_runs ? head[o + 1] : n_cand) - 1;
+    runs[o] = make_uint4(order[key[first] >> 1], pos[first], pos[last] + 1, last - first + 1);
+}
+
 }  // namespace
 
 enum Count { CNT_VALID, CNT_NC, CNT_ND, CNT_DROPPED, CNT_CELLS = 8 };  // d_counts: valid alignments, the nc and nd of the last table report, alignments the non-conversion filter dropped
+
+// a value no earlier call has returned (from 1): the identity of a handle's state, for the store of bsx_meth_diff_report_all
+static u64 meth_next_stamp()
+{
+    static std::atomic<u64> stamp{0};
+    return ++stamp;
+}
 
 struct bsx_meth {
     int device = 0;
@@ -995,6 +1134,24 @@ struct bsx_meth {
     DevBuf<uint8_t> d_diff_cls;
     DevBuf<double> d_diff_p;
     uint32_t diff_last_rows = 0;
+    // The genome-wide store of the last bsx_meth_diff_report_all with this handle as sample A: every common site of every sequence in the
+    // writer's sequence order (store_order[rank] = sequence id), row_start[n_chr + 1] by rank, and per row pos, counts, class byte, p and q: 37 bytes a row.
+    // It stands for (sample B, store_min_depth) while neither handle's counters, letters or context mask have changed since: `changes` is a stamp from one
+    // process-wide counter, new at create and at every such change, so no two handles and no two states of one handle ever share a value (a handle made
+    // at the address of a destroyed one is another sample B).
+    DevBuf<uint32_t> d_store_row_start, d_store_order, d_store_pos;
+    DevBuf<uint4> d_store_counts;
+    DevBuf<uint8_t> d_store_cls;
+    DevBuf<double> d_store_p, d_store_q;
+    std::vector<uint32_t> store_row_start, store_order;
+    bool store_valid = false;
+    uint32_t store_min_depth = 0;
+    u64 store_changes_a = 0, store_changes_b = 0;
+    u64 changes = meth_next_stamp();  // renewed by the calls that change what a diff call reads: add, combine_cpg, set_reference, set_contexts
+    // of the last bsx_meth_diff_dmrs: (sequence id, start, end, n_sig) per DMR, its five sums and p
+    std::vector<uint32_t> dmr_runs;
+    std::vector<uint64_t> dmr_sums;
+    std::vector<double> dmr_p;
     std::vector<std::string> names;  // filled by bsx_meth_create_from_fasta
     MethDev dev() const { MethDev M; M.ref = d_ref.p; M.chr_off = d_chr_off.p; M.depth = d_depth.p; M.meth = d_meth.p; M.first = d_first.p; M.total = chr_off.back(); M.n_chr = n_chr; return M; }
 };
@@ -1096,6 +1253,7 @@ extern "C" int bsx_meth_set_reference(bsx_meth *m, uint32_t chr, const char *upp
     if (!m || chr >= m->n_chr || !upper_seq) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
     if (m->cpg_built) meth_epi_drop_index(m);  // other letters, other CpGs: the index and the cells are built again when they are next needed
+    m->changes = meth_next_stamp();
     HIP_TRY(hipMemcpy(m->d_ref.p + m->chr_off[chr], upper_seq, m->chr_off[chr + 1] - m->chr_off[chr], hipMemcpyHostToDevice));
     return BSX_OK;
 }
@@ -1108,6 +1266,7 @@ extern "C" int bsx_meth_add(bsx_meth *m, uint32_t n, const uint32_t *chr, const 
     if ((u64)m->index_base + n >= 0xFFFFFFFFull) return BSX_ERR_LIMIT;
     for (uint32_t i = 0; i < n; i++) if (chr[i] >= m->n_chr || strand[i] > 3) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
+    m->changes = meth_next_stamp();
     if (m->epi) { const int erc = meth_epi_index(m); if (erc) return erc; }
     const u64 nbytes = seq_off[n];
     uint32_t *d_chr = nullptr; int64_t *d_pos = nullptr, *d_cut = nullptr; uint8_t *d_strand = nullptr, *d_seq = nullptr, *d_drop = nullptr; int32_t *d_ins = nullptr; u64 *d_off = nullptr;
@@ -1186,6 +1345,7 @@ extern "C" int bsx_meth_set_contexts(bsx_meth *m, uint32_t mask)
 {
     if (!m || mask > 0xF) return BSX_ERR_ARG;
     m->ctx_mask = mask;
+    m->changes = meth_next_stamp();
     return BSX_OK;
 }
 
@@ -1330,6 +1490,7 @@ extern "C" int bsx_meth_combine_cpg(bsx_meth *m)
 {
     if (!m) return BSX_ERR_ARG;
     HIP_TRY(hipSetDevice(m->device));
+    m->changes = meth_next_stamp();
     hipLaunchKernelGGL(k_meth_cpg, dim3(4096), dim3(256), 0, m->stream, m->dev(), m->d_rev.p, m->d_pdr.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -2058,6 +2219,240 @@ extern "C" int bsx_meth_diff_regions(bsx_meth *a, bsx_meth *b, uint32_t n, const
     }
 }
 
+// ---- q-values over all rows and de novo DMRs ----
+static constexpr u64 BH_MAX_ROWS = 0xFFFFFFFFull;  // row indices are 32 bits wide
+
+// q[n] of p[n], both on the device, on `stream`: keys and row indices, one radix sort of the pairs, r back to front, its running minimum, the scatter.
+// The workspace (24 bytes a row and the sort's own) lives for the call.  n < 2^32.
+static int meth_bh(hipStream_t stream, const double *d_p, size_t n, double *d_q)
+{
+    if (!n) return BSX_OK;
+    DevBuf<u64> d_keys, d_skeys, d_nan;
+    DevBuf<uint32_t> d_idx, d_sidx;
+    DevBuf<char> d_temp;
+    const auto no_memory = [] { g_bsx_err = "no device memory for the q-values' sort"; return BSX_ERR_NOMEM; };
+    if (d_keys.reserve(n * 8) != hipSuccess || d_skeys.reserve(n * 8) != hipSuccess || d_idx.reserve(n * 4) != hipSuccess || d_sidx.reserve(n * 4) != hipSuccess ||
+        d_nan.reserve(8) != hipSuccess)
+        return no_memory();
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    HIP_TRY(hipMemsetAsync(d_nan.p, 0, 8, stream));
+    hipLaunchKernelGGL(k_bh_keys, dim3(grid), dim3(256), 0, stream, d_p, (u64)n, d_keys.p, d_idx.p, d_nan.p);
+    HIP_TRY(hipGetLastError());
+    size_t need_sort = 0, need_scan = 0;
+    double *const d_r = (double *)d_keys.p;  // the unsorted keys are done with after the sort: r and its running minimum take their place
+    HIP_TRY(rocprim::radix_sort_pairs(nullptr, need_sort, d_keys.p, d_skeys.p, d_idx.p, d_sidx.p, n, 0u, 64u, stream));
+    HIP_TRY(rocprim::inclusive_scan(nullptr, need_scan, d_r, d_r, n, MinDouble(), stream));
+    if (d_temp.reserve(std::max(need_sort, need_scan)) != hipSuccess) return no_memory();
+    HIP_TRY(rocprim::radix_sort_pairs(d_temp.p, need_sort, d_keys.p, d_skeys.p, d_idx.p, d_sidx.p, n, 0u, 64u, stream));
+    hipLaunchKernelGGL(k_bh_ratio, dim3(grid), dim3(256), 0, stream, (const u64 *)d_skeys.p, (u64)n, (const u64 *)d_nan.p, d_r);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(rocprim::inclusive_scan(d_temp.p, need_scan, d_r, d_r, n, MinDouble(), stream));
+    hipLaunchKernelGGL(k_bh_scatter, dim3(grid), dim3(256), 0, stream, (const double *)d_r, (const uint32_t *)d_sidx.p, (u64)n, (const u64 *)d_nan.p, d_q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));  // ahead of the workspace's release
+    return BSX_OK;
+}
+
+extern "C" int bsx_meth_bh(int device, const double *p, uint64_t n, double *q)
+{
+    if (n && (!p || !q)) return BSX_ERR_ARG;
+    if (!n) return BSX_OK;
+    if (n > BH_MAX_ROWS) { g_bsx_err = "bsx_meth_bh takes fewer than 2^32 values"; return BSX_ERR_LIMIT; }
+    for (uint64_t i = 0; i < n; i++)
+        if (!(p[i] >= 0.0 && p[i] <= 1.0) && p[i] == p[i]) { g_bsx_err = "bsx_meth_bh: a p-value outside 0 .. 1"; return BSX_ERR_ARG; }
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) { g_bsx_err = "no HIP device visible; libbsx has no CPU fallback"; return BSX_ERR_NODEVICE; }
+    if (device < 0 || device >= nd) return BSX_ERR_NODEVICE;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> d_p, d_q;
+    if (d_p.reserve(n * 8) != hipSuccess || d_q.reserve(n * 8) != hipSuccess) { g_bsx_err = "bsx_meth_bh: no device memory for the values"; return BSX_ERR_NOMEM; }
+    HIP_TRY(hipMemcpy(d_p.p, p, n * 8, hipMemcpyHostToDevice));
+    const int rc = meth_bh((hipStream_t)0, d_p.p, (size_t)n, d_q.p);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(q, d_q.p, n * 8, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// the writer's sequence order: sorted names, or the ids' own order for a handle without names
+static std::vector<uint32_t> diff_order(const bsx_meth *a)
+{
+    if (a->names.size() == a->n_chr) return sorted_chromosomes(a);
+    std::vector<uint32_t> o(a->n_chr);
+    for (uint32_t c = 0; c < a->n_chr; c++) o[c] = c;
+    return o;
+}
+
+// Fills the store.  The blocks of all sequences stand behind one another in d_blk, in the writer's order: one count launch per sequence, ONE scan over all
+// blocks, whose results are row numbers of the whole store, and one emit launch per sequence that writes at them; then p and q of all rows at once.
+static int diff_report_all(bsx_meth *a, bsx_meth *b, uint32_t min_depth, uint64_t *n_rows)
+{
+    a->store_valid = false;
+    const uint32_t n_chr = a->n_chr;
+    std::vector<uint32_t> order = diff_order(a), row_start((size_t)n_chr + 1, 0);
+    std::vector<size_t> blk_off((size_t)n_chr + 1, 0);
+    for (uint32_t k = 0; k < n_chr; k++) blk_off[k + 1] = blk_off[k] + (size_t)((a->chr_off[order[k] + 1] - a->chr_off[order[k]] + 1023) / 1024);
+    const size_t nblk = blk_off[n_chr];
+    const MethDev A = a->dev(), B = diff_dev_b(a, b);
+    const RowRule R{min_depth, a->ctx_mask, 1, 0};
+    size_t rows = 0;
+    if (nblk) {
+        HIP_TRY(a->d_blk.reserve((nblk + 1) * 4)); HIP_TRY(a->d_blk_start.reserve((nblk + 1) * 4));
+        HIP_TRY(hipMemsetAsync(a->d_blk.p + nblk, 0, 4, a->stream));
+        for (uint32_t k = 0; k < n_chr; k++) {
+            const unsigned blocks = (unsigned)(blk_off[k + 1] - blk_off[k]);
+            const u64 g0 = a->chr_off[order[k]];
+            if (blocks) hipLaunchKernelGGL(k_diff_count, dim3(blocks), dim3(256), 0, a->stream, A, B, g0, a->chr_off[order[k] + 1] - g0, R, 0u, a->d_blk.p + blk_off[k]);
+        }
+        HIP_TRY(hipGetLastError());
+        const int rc = meth_scan_u32(a, a->d_blk.p, a->d_blk_start.p, nblk + 1);
+        if (rc) return rc;
+        std::vector<uint32_t> starts(nblk + 1);
+        HIP_TRY(hipMemcpyAsync(starts.data(), a->d_blk_start.p, (nblk + 1) * 4, hipMemcpyDeviceToHost, a->stream));
+        HIP_TRY(hipStreamSynchronize(a->stream));
+        for (size_t i = 0; i < nblk; i++)  // a block holds at most 1 024 rows: a sum that has passed 2^32 shows as a step down
+            if (starts[i + 1] < starts[i]) { g_bsx_err = "bsx_meth_diff_report_all: the store takes fewer than 2^32 rows"; return BSX_ERR_NOMEM; }
+        for (uint32_t k = 0; k <= n_chr; k++) row_start[k] = starts[blk_off[k]];
+        rows = starts[nblk];
+    }
+    const auto no_memory = [] { g_bsx_err = "bsx_meth_diff_report_all: no device memory for the store"; return BSX_ERR_NOMEM; };
+    if (a->d_store_row_start.reserve(((size_t)n_chr + 1) * 4) != hipSuccess || a->d_store_order.reserve((size_t)n_chr * 4) != hipSuccess) return no_memory();
+    if (rows) {
+        if (a->d_store_pos.reserve(rows * 4) != hipSuccess || a->d_store_counts.reserve(rows * 16) != hipSuccess || a->d_store_cls.reserve(rows) != hipSuccess ||
+            a->d_store_p.reserve(rows * 8) != hipSuccess || a->d_store_q.reserve(rows * 8) != hipSuccess)
+            return no_memory();
+        for (uint32_t k = 0; k < n_chr; k++) {
+            if (row_start[k + 1] == row_start[k]) continue;
+            const u64 g0 = a->chr_off[order[k]];
+            hipLaunchKernelGGL(k_diff_emit, dim3((unsigned)(blk_off[k + 1] - blk_off[k])), dim3(256), 0, a->stream, A, B, g0, a->chr_off[order[k] + 1] - g0, R, 0u,
+                               (const uint32_t *)(a->d_blk_start.p + blk_off[k]), a->d_store_pos.p, a->d_store_counts.p, a->d_store_cls.p);
+        }
+        diff_fisher(a, a->d_store_counts.p, nullptr, rows, a->d_store_p.p);
+        HIP_TRY(hipGetLastError());
+        const int rc = meth_bh(a->stream, a->d_store_p.p, rows, a->d_store_q.p);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(a->d_store_row_start.p, row_start.data(), ((size_t)n_chr + 1) * 4, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(hipMemcpyAsync(a->d_store_order.p, order.data(), (size_t)n_chr * 4, hipMemcpyHostToDevice, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    a->store_row_start.swap(row_start); a->store_order.swap(order);
+    a->store_min_depth = min_depth; a->store_changes_a = a->changes; a->store_changes_b = b->changes;
+    a->store_valid = true;
+    *n_rows = rows;
+    return BSX_OK;
+}
+
+static bool diff_store_stands(const bsx_meth *a, const bsx_meth *b, uint32_t min_depth)
+{
+    return a->store_valid && a->store_min_depth == min_depth && a->store_changes_a == a->changes && a->store_changes_b == b->changes;
+}
+
+// the store for (b, min_depth): the one that stands, or a new one
+static int diff_store_ensure(bsx_meth *a, bsx_meth *b, uint32_t min_depth)
+{
+    uint64_t rows = 0;
+    return diff_store_stands(a, b, min_depth) ? BSX_OK : diff_report_all(a, b, min_depth, &rows);
+}
+
+extern "C" int bsx_meth_diff_report_all(bsx_meth *a, bsx_meth *b, uint32_t min_depth, uint64_t *n_rows)
+{
+    if (!a || !b || !n_rows) return BSX_ERR_ARG;
+    *n_rows = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    try {
+        return diff_report_all(a, b, min_depth, n_rows);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = "bsx_meth_diff_report_all: out of host memory"; return BSX_ERR_NOMEM;
+    }
+}
+
+extern "C" int bsx_meth_diff_fetch_all(bsx_meth *a, uint32_t *row_start, uint32_t *pos0, uint32_t *counts, uint8_t *cls, double *p, double *q)
+{
+    if (!a || !row_start || !pos0 || !counts || !cls || !p || !q) return BSX_ERR_ARG;
+    if (!a->store_valid) { g_bsx_err = "bsx_meth_diff_fetch_all without a store (bsx_meth_diff_report_all)"; return BSX_ERR_STATE; }
+    HIP_TRY(hipSetDevice(a->device));
+    memcpy(row_start, a->store_row_start.data(), a->store_row_start.size() * 4);
+    const size_t rows = a->store_row_start.back();
+    if (!rows) return BSX_OK;
+    HIP_TRY(hipMemcpy(pos0, a->d_store_pos.p, rows * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, a->d_store_counts.p, rows * 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cls, a->d_store_cls.p, rows, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(p, a->d_store_p.p, rows * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(q, a->d_store_q.p, rows * 8, hipMemcpyDeviceToHost));
+    return BSX_OK;
+}
+
+// The DMRs over the store that stands: candidates (CandRule), run heads among them (HeadRule), a thread per run; the host drops the runs below min_sites
+// and sends the spans through diff_regions for their sums and p.
+static int diff_dmrs(bsx_meth *a, bsx_meth *b, uint32_t min_depth, double max_q, uint32_t permille, uint32_t max_gap, uint32_t min_sites, uint32_t *n_dmr)
+{
+    a->dmr_runs.clear(); a->dmr_sums.clear(); a->dmr_p.clear();
+    *n_dmr = 0;
+    const u64 rows = a->store_row_start.back();
+    const StoreDev S{a->d_store_row_start.p, a->d_store_pos.p, a->d_store_counts.p, a->d_store_q.p, a->n_chr};
+    DevBuf<uint32_t> d_key, d_pos, d_head;
+    DevBuf<uint4> d_runs;
+    uint32_t n_cand = 0, n_runs = 0, last = 0;
+    int rc = meth_compact(a, rows, &n_cand, last,
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_cand_count, dim3(nblk), dim3(256), 0, a->stream, S, rows, max_q, permille, a->d_blk.p); },
+        [&](size_t n) -> int { HIP_TRY(d_key.reserve(n * 4)); HIP_TRY(d_pos.reserve(n * 4)); return BSX_OK; },
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_cand_emit, dim3(nblk), dim3(256), 0, a->stream, S, rows, max_q, permille, (const uint32_t *)a->d_blk_start.p, d_key.p, d_pos.p); });
+    if (rc) return rc;
+    rc = meth_compact(a, n_cand, &n_runs, last,
+        [&](unsigned nblk) { hipLaunchKernelGGL(k_head_count, dim3(nblk), dim3(256), 0, a->stream, (const uint32_t *)d_key.p, (const uint32_t *)d_pos.p, (u64)n_cand, max_gap, a->d_blk.p); },
+        [&](size_t n) -> int { HIP_TRY(d_head.reserve(n * 4)); HIP_TRY(d_runs.reserve(n * 16)); return BSX_OK; },
+        [&](unsigned nblk) {
+            hipLaunchKernelGGL(k_head_emit, dim3(nblk), dim3(256), 0, a->stream, (const uint32_t *)d_key.p, (const uint32_t *)d_pos.p, (u64)n_cand, max_gap,
+                               (const uint32_t *)a->d_blk_start.p, d_head.p);
+        });
+    if (rc || !n_runs) return rc;
+    hipLaunchKernelGGL(k_dmr_runs, dim3((n_runs + 255) / 256), dim3(256), 0, a->stream, (const uint32_t *)d_head.p, n_runs, n_cand, (const uint32_t *)d_key.p,
+                       (const uint32_t *)d_pos.p, (const uint32_t *)a->d_store_order.p, d_runs.p);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> runs((size_t)n_runs * 4);
+    HIP_TRY(hipMemcpyAsync(runs.data(), d_runs.p, (size_t)n_runs * 16, hipMemcpyDeviceToHost, a->stream));
+    HIP_TRY(hipStreamSynchronize(a->stream));
+    const size_t kept = bsx_meth_diff::keep_runs(runs.data(), n_runs, min_sites);
+    runs.resize(kept * 4);
+    if (!kept) return BSX_OK;
+    std::vector<uint32_t> chr(kept), start(kept), end(kept);
+    for (size_t i = 0; i < kept; i++) { chr[i] = runs[i * 4]; start[i] = runs[i * 4 + 1]; end[i] = runs[i * 4 + 2]; }
+    std::vector<uint64_t> sums(kept * 5);
+    std::vector<double> p(kept);
+    rc = diff_regions(a, b, (uint32_t)kept, chr.data(), start.data(), end.data(), min_depth, sums.data(), p.data());
+    if (rc) return rc;
+    a->dmr_runs.swap(runs); a->dmr_sums.swap(sums); a->dmr_p.swap(p);
+    *n_dmr = (uint32_t)kept;
+    return BSX_OK;
+}
+
+static const char *const NO_STORE = "no store of bsx_meth_diff_report_all stands for this pair and min_depth";
+
+extern "C" int bsx_meth_diff_dmrs(bsx_meth *a, bsx_meth *b, uint32_t min_depth, const double *max_q, uint32_t min_delta_permille, uint32_t max_gap, uint32_t min_sites,
+                                  uint32_t *n_dmr)
+{
+    if (!a || !b || !max_q || !n_dmr || min_delta_permille > 1000 || !min_sites || !(*max_q >= 0.0 && *max_q <= 1.0)) return BSX_ERR_ARG;
+    *n_dmr = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    if (!diff_store_stands(a, b, min_depth)) { g_bsx_err = NO_STORE; return BSX_ERR_STATE; }
+    try {
+        return diff_dmrs(a, b, min_depth, *max_q, min_delta_permille, max_gap, min_sites, n_dmr);
+    } catch (const std::bad_alloc &) {
+        g_bsx_err = "bsx_meth_diff_dmrs: out of host memory"; return BSX_ERR_NOMEM;
+    }
+}
+
+extern "C" int bsx_meth_diff_fetch_dmrs(bsx_meth *a, uint32_t *chr, uint32_t *start, uint32_t *end, uint32_t *n_sig, uint64_t *sums, double *p)
+{
+    if (!a) return BSX_ERR_ARG;
+    const size_t n = a->dmr_p.size();
+    if (n && (!chr || !start || !end || !n_sig || !sums || !p)) return BSX_ERR_ARG;
+    for (size_t i = 0; i < n; i++) { chr[i] = a->dmr_runs[i * 4]; start[i] = a->dmr_runs[i * 4 + 1]; end[i] = a->dmr_runs[i * 4 + 2]; n_sig[i] = a->dmr_runs[i * 4 + 3]; }
+    if (n) { memcpy(sums, a->dmr_sums.data(), n * 40); memcpy(p, a->dmr_p.data(), n * 8); }
+    return BSX_OK;
+}
+
 namespace {
 
 int write_diff(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, uint64_t *n_rows)
@@ -2088,7 +2483,8 @@ int write_diff(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, u
     return BSX_OK;
 }
 
-int write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
+// fdr: with the q column, Benjamini-Hochberg over the intervals with a common site (bsx_meth_bh)
+int write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, bool fdr, uint64_t *n_written, uint64_t *n_dropped)
 {
     bsx_meth_parse::BedRecords bed;
     const int rc_bed = read_bed(a, bed_path, bed);
@@ -2098,11 +2494,14 @@ int write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, const cha
     std::vector<double> p(n + 1);
     const int rc = bsx_meth_diff_regions(a, b, (uint32_t)n, bed.chr.data(), bed.start.data(), bed.end.data(), min_depth, sums.data(), p.data());
     if (rc) return rc;
+    std::vector<double> q(fdr ? n + 1 : 0);
+    if (fdr) { const int rc_q = bsx_meth_bh(a->device, p.data(), n, q.data()); if (rc_q) return rc_q; }
     OutFile out(out_path);
     if (!out.f) return out.cannot_write();
-    fputs(bsx_meth_diff::REGION_HEADER, out.f);
+    fputs(fdr ? bsx_meth_diff::REGION_FDR_HEADER : bsx_meth_diff::REGION_HEADER, out.f);
     format_rows(out.f, n, 80, [&](size_t i, std::string &o) {
         bsx_meth_diff::append_interval_row(o, a->names[bed.chr[i]].c_str(), bed.start[i], bed.end[i], &bed.label[i], &sums[i * 5], p[i]);
+        if (fdr) bsx_meth_diff::append_q(o, q[i]);
     });
     const int rc_close = out.finish();
     if (rc_close) return rc_close;
@@ -2140,6 +2539,68 @@ int write_diff_bins(bsx_meth *a, bsx_meth *b, const char *path, uint32_t bin, ui
     return BSX_OK;
 }
 
+// The position file with q: formatted from the store (every common site with its p and the q of the whole family), a sequence at a time; the delta rule,
+// max_p and max_q choose among the fetched rows what is written and change no printed value.
+int write_diff_fdr(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, const double *max_q, uint64_t *n_rows)
+{
+    const int rc_store = diff_store_ensure(a, b, min_depth);
+    if (rc_store) return rc_store;
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs(bsx_meth_diff::POS_FDR_HEADER, out.f);
+    std::vector<uint32_t> pos, counts;
+    std::vector<uint8_t> cls, listed;
+    std::vector<double> p, q;
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < a->n_chr; k++) {
+        const size_t lo = a->store_row_start[k], rows = a->store_row_start[k + 1] - lo;
+        if (!rows) continue;
+        pos.resize(rows); counts.resize(rows * 4); cls.resize(rows); p.resize(rows); q.resize(rows);
+        HIP_TRY(hipMemcpy(pos.data(), a->d_store_pos.p + lo, rows * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(counts.data(), a->d_store_counts.p + lo, rows * 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cls.data(), a->d_store_cls.p + lo, rows, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(p.data(), a->d_store_p.p + lo, rows * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(q.data(), a->d_store_q.p + lo, rows * 8, hipMemcpyDeviceToHost));
+        const char *name = a->names[a->store_order[k]].c_str();
+        listed.resize(rows);  // decided once per row: the count and the file cannot disagree
+        for (size_t i = 0; i < rows; i++) {
+            const uint32_t *c = &counts[i * 4];
+            listed[i] = bsx_meth_diff::delta_keeps(c[0], c[1], c[2], c[3], min_delta_permille) && (!max_p || p[i] <= *max_p) && (!max_q || q[i] <= *max_q);
+            total += listed[i];
+        }
+        format_rows(out.f, rows, 84, [&](size_t i, std::string &o) {
+            if (!listed[i]) return;
+            bsx_meth_diff::append_pos_row(o, name, pos[i], cls[i], &counts[i * 4], p[i]);
+            bsx_meth_diff::append_q(o, q[i]);
+        });
+    }
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
+    if (n_rows) *n_rows = total;
+    return BSX_OK;
+}
+
+int write_dmrs(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, double max_q, uint32_t min_delta_permille, uint32_t max_gap, uint32_t min_sites,
+               uint64_t *n_rows)
+{
+    int rc = diff_store_ensure(a, b, min_depth);
+    if (rc) return rc;
+    uint32_t n = 0;
+    rc = diff_dmrs(a, b, min_depth, max_q, min_delta_permille, max_gap, min_sites, &n);
+    if (rc) return rc;
+    OutFile out(path);
+    if (!out.f) return out.cannot_write();
+    fputs(bsx_meth_diff::DMR_HEADER, out.f);
+    format_rows(out.f, n, 96, [&](size_t i, std::string &o) {
+        const uint32_t *r = &a->dmr_runs[i * 4];
+        bsx_meth_diff::append_dmr_row(o, a->names[r[0]].c_str(), r[1], r[2], r[3], &a->dmr_sums[i * 5], a->dmr_p[i]);
+    });
+    const int rc_close = out.finish();
+    if (rc_close) return rc_close;
+    if (n_rows) *n_rows = n;
+    return BSX_OK;
+}
+
 }  // namespace
 
 extern "C" int bsx_meth_write_diff(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, uint64_t *n_rows)
@@ -2158,7 +2619,7 @@ extern "C" int bsx_meth_write_diff_regions(bsx_meth *a, bsx_meth *b, const char 
     if (n_dropped) *n_dropped = 0;
     const int rc_pair = diff_pair(a, b);
     if (rc_pair) return rc_pair;
-    return guarded(out_path, "writing", [&] { return write_diff_regions(a, b, bed_path, out_path, min_depth, n_written, n_dropped); });
+    return guarded(out_path, "writing", [&] { return write_diff_regions(a, b, bed_path, out_path, min_depth, false, n_written, n_dropped); });
 }
 
 extern "C" int bsx_meth_write_diff_bins(bsx_meth *a, bsx_meth *b, const char *path, uint32_t bin, uint32_t min_depth, uint64_t *n_rows)
@@ -2168,4 +2629,35 @@ extern "C" int bsx_meth_write_diff_bins(bsx_meth *a, bsx_meth *b, const char *pa
     const int rc_pair = diff_pair(a, b);
     if (rc_pair) return rc_pair;
     return guarded(path, "writing", [&] { return write_diff_bins(a, b, path, bin, min_depth, n_rows); });
+}
+
+extern "C" int bsx_meth_write_diff_fdr(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, const double *max_q,
+                                       uint64_t *n_rows)
+{
+    if (!a || !b || !path || !n_rows || min_delta_permille > 1000 || a->names.size() != a->n_chr) return BSX_ERR_ARG;
+    for (const double *limit : {max_p, max_q}) if (limit && !(*limit >= 0.0 && *limit <= 1.0)) return BSX_ERR_ARG;  // (a NaN fails both comparisons)
+    *n_rows = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    return guarded(path, "writing", [&] { return write_diff_fdr(a, b, path, min_depth, min_delta_permille, max_p, max_q, n_rows); });
+}
+
+extern "C" int bsx_meth_write_diff_regions_fdr(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped)
+{
+    if (!a || !b || !bed_path || !out_path || a->names.size() != a->n_chr) return BSX_ERR_ARG;
+    if (n_written) *n_written = 0;
+    if (n_dropped) *n_dropped = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    return guarded(out_path, "writing", [&] { return write_diff_regions(a, b, bed_path, out_path, min_depth, true, n_written, n_dropped); });
+}
+
+extern "C" int bsx_meth_write_dmrs(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, const double *max_q, uint32_t min_delta_permille, uint32_t max_gap,
+                                   uint32_t min_sites, uint64_t *n_rows)
+{
+    if (!a || !b || !path || !max_q || !n_rows || min_delta_permille > 1000 || !min_sites || !(*max_q >= 0.0 && *max_q <= 1.0) || a->names.size() != a->n_chr) return BSX_ERR_ARG;
+    *n_rows = 0;
+    const int rc_pair = diff_pair(a, b);
+    if (rc_pair) return rc_pair;
+    return guarded(path, "writing", [&] { return write_dmrs(a, b, path, min_depth, *max_q, min_delta_permille, max_gap, min_sites, n_rows); });
 }

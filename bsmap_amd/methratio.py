@@ -93,6 +93,14 @@ PROTOTYPES = {
     "bsx_meth_diff_regions": (_I32, [_VP, _VP, _U32, _VP, _VP, _VP, _U32, _VP, _VP]),
     "bsx_meth_write_diff_regions": (_I32, [_VP, _VP, _STR, _STR, _U32, _VP, _VP]),
     "bsx_meth_write_diff_bins": (_I32, [_VP, _VP, _STR, _U32, _U32, _VP]),
+    "bsx_meth_bh": (_I32, [_I32, _VP, _U64, _VP]),
+    "bsx_meth_diff_report_all": (_I32, [_VP, _VP, _U32, _VP]),
+    "bsx_meth_diff_fetch_all": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "bsx_meth_diff_dmrs": (_I32, [_VP, _VP, _U32, _VP, _U32, _U32, _U32, _VP]),
+    "bsx_meth_diff_fetch_dmrs": (_I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "bsx_meth_write_diff_fdr": (_I32, [_VP, _VP, _STR, _U32, _U32, _VP, _VP, _VP]),
+    "bsx_meth_write_diff_regions_fdr": (_I32, [_VP, _VP, _STR, _STR, _U32, _VP, _VP]),
+    "bsx_meth_write_dmrs": (_I32, [_VP, _VP, _STR, _U32, _VP, _U32, _U32, _U32, _VP]),
 }
 _path = os.fsencode  # str or os.PathLike -> the bytes of a const char *path
 
@@ -130,6 +138,17 @@ def epi_fetch(L, h, chr, min_reads=1):
     pos0, counts = np.zeros((nr[0], 4), np.uint32), np.zeros((nr[0], 16), np.uint32)
     _check(L.bsx_meth_epi_fetch_rows(h, pos0.ctypes.data, counts.ctypes.data))
     return pos0, counts
+
+
+def bh(p, device=0):
+    """Benjamini-Hochberg q-values of the p-values `p` (float64, within 0 .. 1; a NaN is outside the family and stays NaN), computed on the device
+    (bsx_meth_bh)"""
+    p = np.ascontiguousarray(p, np.float64)
+    if p.ndim != 1:
+        raise ValueError("p must be one-dimensional")
+    q = np.zeros(p.size, np.float64)
+    _check(_bind().bsx_meth_bh(device, p.ctypes.data, p.size, q.ctypes.data))
+    return q
 
 
 class Meth:
@@ -331,17 +350,58 @@ class Meth:
         _check(self.L.bsx_meth_diff_regions(h, hb, a[0].size, *[x.ctypes.data for x in a], min_depth, sums.ctypes.data, p.ctypes.data))
         return sums, p
 
-    def write_diff(self, other, path, min_depth=1, min_delta_permille=0, max_p=None):
-        """the rows of every sequence in sorted name order, with max_p those with p <= max_p; returns the rows written"""
+    def write_diff(self, other, path, min_depth=1, min_delta_permille=0, max_p=None, max_q=None, fdr=False):
+        """the rows of every sequence in sorted name order, with max_p those with p <= max_p; returns the rows written.  fdr (or a max_q): with the
+        Benjamini-Hochberg q of every row over all common sites as a 13th column, and with max_q only the rows with q <= max_q"""
         (h, hb), n = self._pair(other), C.c_uint64()
-        _check(self.L.bsx_meth_write_diff(h, hb, _path(path), min_depth, min_delta_permille, None if max_p is None else C.byref(C.c_double(max_p)), C.byref(n)))
+        ref = lambda x: None if x is None else C.byref(C.c_double(x))
+        if fdr or max_q is not None:
+            _check(self.L.bsx_meth_write_diff_fdr(h, hb, _path(path), min_depth, min_delta_permille, ref(max_p), ref(max_q), C.byref(n)))
+        else:
+            _check(self.L.bsx_meth_write_diff(h, hb, _path(path), min_depth, min_delta_permille, ref(max_p), C.byref(n)))
         return n.value
 
-    def write_diff_regions(self, other, bed_path, out_path, min_depth=1):
-        """one row per interval of a BED file; returns (intervals written, intervals dropped: on sequences that are not loaded)"""
+    def write_diff_regions(self, other, bed_path, out_path, min_depth=1, fdr=False):
+        """one row per interval of a BED file; returns (intervals written, intervals dropped: on sequences that are not loaded).  fdr: with the q of every
+        interval over the file's intervals that hold a common site"""
         (h, hb), nw, nd = self._pair(other), C.c_uint64(), C.c_uint64()
-        _check(self.L.bsx_meth_write_diff_regions(h, hb, _path(bed_path), _path(out_path), min_depth, C.byref(nw), C.byref(nd)))
+        write = self.L.bsx_meth_write_diff_regions_fdr if fdr else self.L.bsx_meth_write_diff_regions
+        _check(write(h, hb, _path(bed_path), _path(out_path), min_depth, C.byref(nw), C.byref(nd)))
         return nw.value, nd.value
+
+    # ---- q-values over all rows and de novo DMRs (DESIGN §3.13) ----
+    def write_order(self):
+        """the sequence ids in the order the diff files and the store list them: sorted names, the ids' own order without names"""
+        n = self.n_chr
+        names = [self.chr_name(c) for c in range(n)]
+        return sorted(range(n), key=lambda c: names[c].encode()) if all(names) else list(range(n))
+
+    def diff_report_all(self, other, min_depth=1):
+        """every common site of every sequence, in write_order() and ascending position: (row_start uint32 [n_chr + 1] by rank in that order, pos0 uint32,
+        counts uint32 [rows][4] = mA, dA, mB, dB, cls uint8, p float64, q float64: Benjamini-Hochberg over all rows).  The rows stay on the device as
+        the store diff_dmrs works on"""
+        (h, hb), n = self._pair(other), C.c_uint64()
+        _check(self.L.bsx_meth_diff_report_all(h, hb, min_depth, C.byref(n)))
+        rows = n.value
+        row_start, pos0, counts, cls = np.zeros(self.n_chr + 1, np.uint32), np.zeros(rows, np.uint32), np.zeros((rows, 4), np.uint32), np.zeros(rows, np.uint8)
+        p, q = np.zeros(rows, np.float64), np.zeros(rows, np.float64)
+        _check(self.L.bsx_meth_diff_fetch_all(h, *[x.ctypes.data for x in (row_start, pos0, counts, cls, p, q)]))
+        return row_start, pos0, counts, cls, p, q
+
+    def diff_dmrs(self, other, max_q, min_delta_permille=0, max_gap=300, min_sites=3, min_depth=1):
+        """the DMRs over the store of the last diff_report_all(other, min_depth): (chr uint32, start uint32, end uint32, n_sig uint32, sums uint64 [n][5] =
+        N, MA, DA, MB, DB over all common sites of [start, end), p float64: the test on the sums)"""
+        (h, hb), n = self._pair(other), C.c_uint32()
+        _check(self.L.bsx_meth_diff_dmrs(h, hb, min_depth, C.byref(C.c_double(max_q)), min_delta_permille, max_gap, min_sites, C.byref(n)))
+        cols = [np.zeros(n.value, np.uint32) for _ in range(4)] + [np.zeros((n.value, 5), np.uint64), np.zeros(n.value, np.float64)]
+        _check(self.L.bsx_meth_diff_fetch_dmrs(h, *[x.ctypes.data for x in cols]))
+        return tuple(cols)
+
+    def write_dmrs(self, other, path, max_q=0.05, min_delta_permille=0, max_gap=300, min_sites=3, min_depth=1):
+        """the DMRs as a file (the store is built unless one stands for other and min_depth); returns the DMRs written"""
+        (h, hb), n = self._pair(other), C.c_uint64()
+        _check(self.L.bsx_meth_write_dmrs(h, hb, _path(path), min_depth, C.byref(C.c_double(max_q)), min_delta_permille, max_gap, min_sites, C.byref(n)))
+        return n.value
 
     def write_diff_bins(self, other, path, width, min_depth=1):
         """one row per bin of `width` positions that holds a common site; returns the rows written"""

@@ -531,6 +531,55 @@ int bsx_meth_write_diff_regions(bsx_meth *a, bsx_meth *b, const char *bed_path, 
  * "name", and only the bins with N > 0; n_rows (may be NULL): the bins written.  bin == 0 is BSX_ERR_ARG. */
 int bsx_meth_write_diff_bins(bsx_meth *a, bsx_meth *b, const char *path, uint32_t bin, uint32_t min_depth, uint64_t *n_rows);
 
+/* Benjamini-Hochberg q-values over all rows, and de novo differentially methylated regions (an extension).
+ *
+ * The FAMILY is every common site (the definition above, under min_depth and the context mask) of every loaded sequence, listed in the writer's sequence
+ * order (sorted names as in bsx_meth_write_diff; the ids' order for a handle without names), ascending position within a sequence; n is its size.  No
+ * filter of a writer (min_delta_permille, max_p, max_q) shrinks it: filters choose what is written.
+ * q: with the family's p-values sorted ascending, p_(1) <= .. <= p_(n), r_k = (p_(k) (double)n) / (double)k (two separately rounded double operations,
+ * the product first) and q_(k) = min(1.0, min over j >= k of r_j); a row gets the q of its p, equal p get equal q.  A NaN p (an interval with N == 0) is
+ * outside the family: it does not count in n and its q is NaN ("NA" in the files).  Minima are exact in any order and a product followed by a quotient
+ * cannot be contracted, so q is bit-identical to the same formula in numpy on the same p, and two calls give the same bits (no floating-point atomics).
+ * A CANDIDATE is a row of the family with q <= max_q that passes the delta rule of bsx_meth_diff_report_chr under min_delta_permille and whose direction
+ * s = sign(mB dA - mA dB) (64-bit integers) is not 0.  A DMR is a maximal run of candidates that follow one another among the candidates, lie on one
+ * sequence, share s, and each lie at most max_gap nt behind the one before (pos[i] - pos[i - 1] <= max_gap).  Common sites that are no candidates do
+ * not break a run; strand is ignored (without bsx_meth_combine_cpg the C and the G of a CpG are neighbouring rows).  n_sig is the number of candidates,
+ * the span is [start, end) = [pos_first, pos_last + 1), 0-based and half-open; a run is reported when n_sig >= min_sites (min_sites >= 1).  Its sums
+ * N, MA, DA, MB, DB and p are what bsx_meth_diff_regions returns for the span under the same min_depth: over ALL common sites of the span (N >= n_sig),
+ * and the p is that pooled test, a description of the region and not a corrected value.
+ *
+ * The core on its own: q[n] of p[n], host arrays, computed on `device` (a radix sort of (bits of p, row index), r, a running minimum, a scatter).
+ * Every p is within 0 .. 1 or NaN (BSX_ERR_ARG otherwise); n == 0 is BSX_OK; n >= 2^32 is BSX_ERR_LIMIT. */
+int bsx_meth_bh(int device, const double *p, uint64_t n, double *q);
+/* Fills the genome-wide store of handle `a`: every row of the family with pos, counts, class byte, p and q (37 bytes a row on the device, in buffers
+ * apart from those of bsx_meth_diff_report_chr, whose rows stay fetchable).  n_rows: the family's size.  2^32 rows or more: BSX_ERR_NOMEM with a message.
+ * The store stands for (b, min_depth) until the next bsx_meth_diff_report_all on `a`, or until an add, bsx_meth_combine_cpg, bsx_meth_set_reference or
+ * bsx_meth_set_contexts on either handle; a handle created after `b` was destroyed is another sample B, also at the same address. */
+int bsx_meth_diff_report_all(bsx_meth *a, bsx_meth *b, uint32_t min_depth, uint64_t *n_rows);
+/* the store: row_start[n_chr + 1] by rank in the writer's sequence order (the rows of the k-th sequence of that order are [row_start[k], row_start[k + 1])),
+ * and per row the 0-based position, counts[4] = mA, dA, mB, dB, the class byte (bits 0-1: CG, CHG, CHH, CN; bit 2 set over a G), p and q.  BSX_ERR_STATE
+ * without a store */
+int bsx_meth_diff_fetch_all(bsx_meth *a, uint32_t *row_start, uint32_t *pos0, uint32_t *counts, uint8_t *cls, double *p, double *q);
+/* The DMRs over the store of the last bsx_meth_diff_report_all(a, b, min_depth): BSX_ERR_STATE when none stands for this b and min_depth.  *max_q within
+ * 0 .. 1, min_delta_permille <= 1000, min_sites >= 1, else BSX_ERR_ARG.  n_dmr: how many, in the store's order. */
+int bsx_meth_diff_dmrs(bsx_meth *a, bsx_meth *b, uint32_t min_depth, const double *max_q, uint32_t min_delta_permille, uint32_t max_gap, uint32_t min_sites,
+                       uint32_t *n_dmr);
+/* the DMRs of the last bsx_meth_diff_dmrs: sequence id, start, end, n_sig, sums[n_dmr][5] = N, MA, DA, MB, DB and p[n_dmr] */
+int bsx_meth_diff_fetch_dmrs(bsx_meth *a, uint32_t *chr, uint32_t *start, uint32_t *end, uint32_t *n_sig, uint64_t *sums, double *p);
+/* bsx_meth_write_diff with a 13th column q ("%.4e"; header "... p q"): formatted from the store (built here unless one stands for b and min_depth).  The
+ * rows that pass the delta rule, p <= *max_p and q <= *max_q are written (a NULL pointer: no such filter); the first 12 columns of a written row are what
+ * bsx_meth_write_diff writes for it, and no filter changes a printed q.  A limit outside 0 .. 1 (a NaN too) is BSX_ERR_ARG, as in bsx_meth_diff_dmrs.
+ * n_rows: the rows written (needed). */
+int bsx_meth_write_diff_fdr(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, uint32_t min_delta_permille, const double *max_p, const double *max_q,
+                            uint64_t *n_rows);
+/* bsx_meth_write_diff_regions with a column q behind p: Benjamini-Hochberg over the file's intervals with N > 0 (bsx_meth_bh), "NA" for the others.
+ * (The bin file has no q form: it is written in pieces of 2^22 bins and q needs all of them.) */
+int bsx_meth_write_diff_regions_fdr(bsx_meth *a, bsx_meth *b, const char *bed_path, const char *out_path, uint32_t min_depth, uint64_t *n_written, uint64_t *n_dropped);
+/* The DMRs as a file: header "chr start end n_sig n_C C_a CT_a ratio_a C_b CT_b ratio_b delta p", the numbers formatted as in bsx_meth_write_diff.  Uses
+ * the store that stands for (b, min_depth) or builds it.  Argument rules of bsx_meth_diff_dmrs; n_rows: the DMRs written (needed). */
+int bsx_meth_write_dmrs(bsx_meth *a, bsx_meth *b, const char *path, uint32_t min_depth, const double *max_q, uint32_t min_delta_permille, uint32_t max_gap,
+                        uint32_t min_sites, uint64_t *n_rows);
+
 #ifdef __cplusplus
 }
 #endif

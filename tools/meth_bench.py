@@ -13,8 +13,11 @@ the first add) and bsx_meth_epi_report_chr over all chromosomes; the JSON line t
 over the same reference, fed the same alignments converted under another seed (sample B), and times bsx_meth_diff_report_chr over all chromosomes (with
 `--diff-delta PERMILLE` as its filter) and, for every `--regions` entry, bsx_meth_diff_regions on the same intervals right behind bsx_meth_regions (DESIGN
 §3.12): in a kernel trace of the run k_diff_count / k_diff_emit / k_meth_fisher stand beside k_meth_count / k_meth_emit, and k_meth_diff_regions beside
-k_meth_regions; the JSON line carries the rows and the host-side times.  (Not with --ct-snp: a diff call needs the mode off.)
-usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--epi] [--diff] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
+k_meth_regions; the JSON line carries the rows and the host-side times.  (Not with --ct-snp: a diff call needs the mode off.)  With `--fdr` (needs --diff) it also
+times bsx_meth_diff_report_all (the genome-wide store with its q-values: the radix sort, k_bh_keys / k_bh_ratio / k_bh_scatter and the running minimum stand in
+the trace behind one k_diff_count / k_diff_emit per chromosome) and bsx_meth_diff_dmrs over it (k_cand_* / k_head_* / k_dmr_runs; `--dmr-max-q Q`, default 0.05,
+with the defaults of methdiff for the rest).
+usage: meth_bench.py [--aln 16777216] [--len 100] [--ct-snp MODE] [--nonconv-filter N] [--read-stats] [--pdr] [--epi] [--diff [--fdr]] [--wig-bin B,...] [--regions N,LEN;...] [--repeat R]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,7 +41,11 @@ def main():
     ap.add_argument("--epi", dest="epi", action="store_true")
     ap.add_argument("--diff", dest="diff", action="store_true")
     ap.add_argument("--diff-delta", dest="diff_delta", type=int, default=0)
+    ap.add_argument("--fdr", dest="fdr", action="store_true")
+    ap.add_argument("--dmr-max-q", dest="dmr_max_q", type=float, default=0.05)
     a = ap.parse_args()
+    if a.fdr and not a.diff:
+        ap.error("--fdr needs --diff")
     if a.diff and a.ct_snp != "no-action":
         ap.error("--diff needs the C/T-SNP mode off")
     rng = np.random.default_rng(1)
@@ -132,6 +139,12 @@ def main():
             B._check(L.bsx_meth_diff_report_chr(h, mb.h, c, 1, a.diff_delta, C.byref(nr)))
             diff_rows += nr.value
         extra.update(diff_delta_permille=a.diff_delta, diff_rows=diff_rows, diff_report_s_all_chromosomes=round(time.perf_counter() - t7, 3))
+    if a.fdr:
+        t9, n_all, n_dmr = time.perf_counter(), C.c_uint64(), C.c_uint32()
+        B._check(L.bsx_meth_diff_report_all(h, mb.h, 1, C.byref(n_all)))
+        t10 = time.perf_counter()
+        B._check(L.bsx_meth_diff_dmrs(h, mb.h, 1, C.byref(C.c_double(a.dmr_max_q)), a.diff_delta, 300, 3, C.byref(n_dmr)))
+        extra.update(store_rows=n_all.value, diff_report_all_s=round(t10 - t9, 3), dmr_max_q=a.dmr_max_q, dmrs=n_dmr.value, diff_dmrs_s=round(time.perf_counter() - t10, 3))
     for width in [int(x) for x in a.wig_bin.split(",") if x]:
         out = np.zeros((int(lens.max()) // width + 1, 5), np.uint64)
         nb, took = C.c_uint64(), []
