@@ -1891,15 +1891,13 @@ static int meth_tiled(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32
     }
     HIP_TRY(hipSetDevice(m->device));
     // launches: [a, b) of the intervals each
-    std::vector<uint32_t> cut_at(1, 0);
+    const auto clipped_len = [&](uint32_t i) { return ce[i] - cs[i]; };
+    const std::vector<uint32_t> cut_at = bsx_meth_tiles::launches(n, clipped_len, REGION_CHUNK);
     size_t max_iv = 0, max_tiles = 0;
-    for (uint32_t a = 0; a < n;) {
-        uint32_t b = a;
+    for (size_t q = 0; q + 1 < cut_at.size(); q++) {
         size_t nt = 0;
-        while (b < n && (size_t)(b - a) < REGION_CHUNK && nt < REGION_CHUNK) nt += (size_t)bsx_meth_tiles::n_tiles(ce[b] - cs[b]), b++;
-        max_iv = std::max<size_t>(max_iv, b - a); max_tiles = std::max(max_tiles, nt);
-        cut_at.push_back(b);
-        a = b;
+        for (uint32_t i = cut_at[q]; i < cut_at[q + 1]; i++) nt += (size_t)bsx_meth_tiles::n_tiles(clipped_len(i));
+        max_iv = std::max<size_t>(max_iv, cut_at[q + 1] - cut_at[q]); max_tiles = std::max(max_tiles, nt);
     }
     DevBuf<bsx_meth_tiles::Tile> d_tiles;
     DevBuf<uint32_t> d_chr, d_start;
@@ -1919,9 +1917,7 @@ static int meth_tiled(bsx_meth *m, uint32_t n, const uint32_t *chr, const uint32
             HIP_TRY(hipMemcpyAsync(d_chr.p, chr + a, (size_t)(b - a) * 4, hipMemcpyHostToDevice, m->stream));
             HIP_TRY(hipMemcpyAsync(d_start.p, cs.data() + a, (size_t)(b - a) * 4, hipMemcpyHostToDevice, m->stream));
             const uint32_t nt = (uint32_t)tiles.size();
-            size_t in_long = 0;  // tiles of intervals of 64 tiles and more
-            for (uint32_t i = a; i < b; i++) { const size_t k = (size_t)bsx_meth_tiles::n_tiles(ce[i] - cs[i]); if (k >= 64) in_long += k; }
-            launch(2 * in_long > nt, (const bsx_meth_tiles::Tile *)d_tiles.p, nt, (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, d_sums.p);
+            launch(bsx_meth_tiles::wide(a, b, clipped_len), (const bsx_meth_tiles::Tile *)d_tiles.p, nt, (const uint32_t *)d_chr.p, (const uint32_t *)d_start.p, d_sums.p);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipMemcpyAsync(sums + (size_t)a * 5, d_sums.p, (size_t)(b - a) * 40, hipMemcpyDeviceToHost, m->stream));

@@ -2,6 +2,7 @@
 lists of tuples the pure-Python models give."""
 import numpy as np
 
+import diff_model as D
 from bsmap_amd.methratio import Meth
 
 
@@ -73,6 +74,25 @@ def epi_rows(m, n_chr, min_reads=1):
         pos, counts = m.epi_report(c, min_reads)
         got += [(c, tuple(p), n) for p, n in zip(pos.tolist(), counts.tolist())]
     return got
+
+
+def joined(a, b, c, min_depth, permille=0):
+    """the model of the two-sample rows of sequence c: [(pos0, mA, dA, mB, dB)] from the pinned single-sample reports of a and b"""
+    pa, da, ma, _, _ = a.report(c, min_depth, True)
+    pb, db, mb, _, _ = b.report(c, min_depth, True)
+    sb = {int(p): (int(m), int(d)) for p, d, m in zip(pb, db, mb) if d > 0}
+    rows = [(int(p), int(m), int(d)) + sb[int(p)] for p, d, m in zip(pa, da, ma) if d > 0 and int(p) in sb]
+    return [r for r in rows if D.delta_keeps(*r[1:], permille)]
+
+
+def interval_sums(rows_by_chr, lens, ivs):
+    """[[N, MA, DA, MB, DB]] of the intervals [(chr id, start, end)] over the rows of joined(), the ends clipped to the sequences' lengths"""
+    out = []
+    for c, s, e in ivs:
+        e = min(e, lens[c])
+        inside = [r for r in rows_by_chr[c] if min(s, e) <= r[0] < e]
+        out.append([len(inside)] + [sum(r[k] for r in inside) for k in (1, 2, 3, 4)])
+    return out
 
 
 def read_text(path):

@@ -91,15 +91,6 @@ def both(world):
     b.close()
 
 
-def joined(a, b, c, min_depth, permille=0):
-    """the model of the rows: [(pos0, mA, dA, mB, dB)] from the pinned single-sample reports"""
-    pa, da, ma, _, _ = a.report(c, min_depth, True)
-    pb, db, mb, _, _ = b.report(c, min_depth, True)
-    sb = {int(p): (int(m), int(d)) for p, d, m in zip(pb, db, mb) if d > 0}
-    rows = [(int(p), int(m), int(d)) + sb[int(p)] for p, d, m in zip(pa, da, ma) if d > 0 and int(p) in sb]
-    return [r for r in rows if D.delta_keeps(*r[1:], permille)]
-
-
 def got_rows(a, b, c, min_depth=1, permille=0):
     pos, counts, p = a.diff_report(b, c, min_depth, permille)
     assert pos.dtype == np.uint32 and counts.shape == (len(pos), 4) and p.shape == (len(pos),) and p.dtype == np.float64
@@ -121,13 +112,13 @@ def test_rows_are_the_join_of_the_two_reports(world, mask, cpg):
         for md in (1, 3):
             for c in range(3):
                 for permille in (0, 250, 1000):
-                    want = joined(a, b, c, md, permille)
+                    want = U.joined(a, b, c, md, permille)
                     got, p = got_rows(a, b, c, md, permille)
                     assert got == want, (md, c, permille)
                     assert np.all((p >= 0) & (p <= 1))
-            assert len(joined(a, b, 1, md)) > 50 and joined(a, b, 2, md) == [] and 0 < len(joined(a, b, 1, md, 250)) < len(joined(a, b, 1, md))
+            assert len(U.joined(a, b, 1, md)) > 50 and U.joined(a, b, 2, md) == [] and 0 < len(U.joined(a, b, 1, md, 250)) < len(U.joined(a, b, 1, md))
         if mask == 0 and not cpg:   # the planted rows: block and tile borders, the last position of a sequence and the first of the next
-            pos0, pos1 = ({r[0] for r in joined(a, b, c, 1)} for c in (0, 1))
+            pos0, pos1 = ({r[0] for r in U.joined(a, b, c, 1)} for c in (0, 1))
             assert {255, 256, 1023, 1024, 1099} <= pos0 and {0, 255, 256, 1023, 1024, 2047, 2048, 4999} <= pos1
             assert not any(300 <= x < 420 for x in pos1) and any(300 <= x < 420 for x in a.report(1)[0].tolist())   # covered in A only
     finally:
@@ -200,15 +191,6 @@ def test_two_calls_give_the_same_bytes(both):
 
 
 # ---- 4. regions ----------------------------------------------------------------------------------------------------------------------------------
-def interval_sums(rows_by_chr, lens, ivs):
-    out = []
-    for c, s, e in ivs:
-        e = min(e, lens[c])
-        inside = [r for r in rows_by_chr[c] if min(s, e) <= r[0] < e]
-        out.append([len(inside)] + [sum(r[k] for r in inside) for k in (1, 2, 3, 4)])
-    return out
-
-
 def check_interval_p(sums, p):
     for s, x in zip(sums, p.tolist()):
         assert math.isnan(x) if not s[0] else 0.0 <= x <= 1.0, (s, x)
@@ -220,9 +202,9 @@ def check_interval_p(sums, p):
 def test_region_sums_and_p(world, both, md):
     a, b = both
     assert a.L.bsx_meth_region_tile() == 2048
-    rows = [joined(a, b, c, md) for c in range(3)]
+    rows = [U.joined(a, b, c, md) for c in range(3)]
     sums, p = a.diff_regions(b, *[[v[k] for v in INTERVALS] for k in range(3)], md)
-    want = interval_sums(rows, world.lens, INTERVALS)
+    want = U.interval_sums(rows, world.lens, INTERVALS)
     assert sums.dtype == np.uint64 and sums.tolist() == want
     assert want[0] == want[5] and want[3] == want[7] == want[8] == [0] * 5 and want[2][0] > 500 and want[9][0] == len(rows[0]) and want[11][0] == want[13][0] == 1
     check_interval_p(want, p)

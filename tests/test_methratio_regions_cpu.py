@@ -4,6 +4,7 @@ interval into tiles (bsmap_amd/csrc/bsx_meth_tiles.h through tests/harness/tiles
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 import ctsnp_model as M
@@ -132,3 +133,73 @@ def test_tile_cutting_rule(tiles):
             assert single == (1 if ntile == 1 else 0)
         assert pos == n
     assert at == len(out)
+
+
+# ---- the launches of a call and their block width --------------------------------------------------------------------------------------
+def launch_lists(T):
+    """directed lists of interval lengths (in positions), then seeded ones: empty intervals in runs, single tiles, intervals of more tiles than any chunk"""
+    directed = [[], [0], [1], [0, 0, 0], [9 * T], [9 * T, 9 * T], [T] * 17, [0] * 17, [1, 9 * T, 1],
+                [0, T, 0, 0, 5 * T, 0, 0, 0, T + 1, 0],                        # empty ones at the first and last place of a launch, and alone
+                [T, T, 0, 0, 0, 0, 0, 0, 0, 0, 0, T, T, 0], [0, 0, 2 * T, 0, 0, 3 * T + 1, 0, 0, 0, 0, 0, 4 * T, 4 * T + 1],
+                [2 * T, 3 * T, T, 0, 8 * T, 8 * T + 1, 7 * T, 1, 1, 1, 1, 1, 1, 1, 1, 1, 40 * T]]
+    rng = np.random.default_rng(11)
+    seeded = []
+    for n in (1, 2, 3, 7, 8, 9, 40, 200):
+        for _ in range(3):
+            kind = rng.integers(0, 4, n)   # 0: empty, 1: one tile, 2: a few tiles, 3: more than 8
+            tiles = np.where(kind == 0, 0, np.where(kind == 1, 1, np.where(kind == 2, rng.integers(2, 6, n), rng.integers(9, 30, n))))
+            seeded.append([int(t) * T - (int(rng.integers(0, T)) if t else 0) for t in tiles])
+    return directed, seeded
+
+
+def model_launches(ntiles, chunk):
+    """the rule restated: a launch takes intervals while it holds fewer than `chunk` of them and fewer than `chunk` tiles"""
+    cuts, a = [0], 0
+    while a < len(ntiles):
+        b, nt = a, 0
+        while b < len(ntiles) and b - a < chunk and nt < chunk:
+            nt += ntiles[b]
+            b += 1
+        cuts.append(b)
+        a = b
+    return cuts
+
+
+@pytest.mark.parametrize("chunk", [1, 2, 5, 8])
+def test_launch_cut_rule(tiles, chunk):
+    T = int(tiles()[0].split()[1])
+    directed, seeded = launch_lists(T)
+    seen = set()
+    for lens in directed + seeded:
+        ntiles = [(n + T - 1) // T for n in lens]
+        out = tiles("launches", chunk, *lens)
+        assert len(out) == 1 and out[0].split()[0] == "launches"
+        cuts = [int(x) for x in out[0].split()[1:]]
+        assert cuts[0] == 0 and cuts[-1] == len(lens) and all(x < y for x, y in zip(cuts, cuts[1:])), (lens, cuts)   # a partition of [0, n) in order, none empty
+        assert cuts == model_launches(ntiles, chunk), lens
+        for a, b in zip(cuts, cuts[1:]):
+            assert b - a <= chunk and sum(ntiles[a:b - 1]) < chunk, (lens, a, b)
+            if b < len(lens):                                     # a launch ends early only where it is full
+                assert b - a == chunk or sum(ntiles[a:b]) >= chunk, (lens, a, b)
+            if ntiles[b - 1] > chunk:
+                seen.add("alone" if b - a == 1 else "last")       # an interval of more tiles than the chunk is placed
+            if b - a > 1 and any(ntiles[a:b]):
+                seen |= {"empty first"} if not ntiles[a] else set()
+                seen |= {"empty last"} if not ntiles[b - 1] else set()
+            if not any(ntiles[a:b]):
+                seen.add("all empty")
+        assert all(t <= chunk or any(b - 1 == i for b in cuts[1:]) for i, t in enumerate(ntiles)), lens   # .. as its launch's last interval
+    assert seen >= ({"alone", "all empty"} if chunk == 1 else {"alone", "last", "empty first", "empty last", "all empty"}), seen
+
+
+def test_wide_rule(tiles):
+    T = int(tiles()[0].split()[1])
+    wide = lambda *lens: tiles("wide", *lens) == ["wide 1"]
+    narrow = lambda *lens: tiles("wide", *lens) == ["wide 0"]
+    assert narrow() and narrow(0) and narrow(1) and narrow(T, T, T)
+    assert narrow(63 * T) and narrow(62 * T + 1) and wide(63 * T + 1) and wide(64 * T) and wide(200 * T + 5)   # 63 tiles against 64
+    assert narrow(*[63 * T] * 10) and wide(*[64 * T] * 10)
+    assert narrow(64 * T, *[1] * 64) and wide(64 * T, *[1] * 63) and narrow(64 * T, *[1] * 65)                   # exactly half is not wide
+    assert wide(64 * T + 1, *[T] * 64) and narrow(64 * T + 1, *[T] * 65)                                         # 65 of 129: one tile over half
+    assert narrow(64 * T, 32 * T, 32 * T) and wide(64 * T, 32 * T, 31 * T) and wide(64 * T, 0, 0, 63 * T, 0)     # shorter intervals of many tiles count as short
+    assert wide(0, 64 * T, 0) and wide(32 * T, 64 * T, 31 * T + 1, 65 * T) and narrow(*[63 * T, 64 * T] * 3, T, T, T)
