@@ -20,6 +20,7 @@
 #include <csignal>
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -38,6 +39,7 @@
 #include "bsx_bam_out.h"
 #include "bsx_textout.h"
 #include "bsx_lanes.h"
+#include "bsx_ring.h"
 #include <sys/wait.h>
 
 using namespace std;
@@ -554,13 +556,33 @@ void die(int rc, const char *what)
     fatal_exit();
 }
 
+double now_s() { return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// ---- environment knobs: each read once, when main() makes its Knobs (DESIGN.md §3.5 has the table) -----------------------------
+int env_int(const char *name, int dflt, int lo, int hi) { const char *e = getenv(name); return e ? max(lo, min(hi, atoi(e))) : dflt; }
+struct Knobs {
+    // units per batch, >= 1; 0 = not set (being set also switches off the smaller batches of lanes that share a GPU)
+    const int batch = env_int("BSX_BATCH", 0, 1, INT_MAX);
+    // device batches per GPU, 1..8, and how many of them may be in their kernels at once, >= 1 (at most the device batches); 0 = not set
+    const int gpu_batches = env_int("BSX_GPU_BATCHES", 0, 1, 8), gpu_compute = env_int("BSX_GPU_COMPUTE", 0, 1, INT_MAX);
+    const bool pin = env_int("BSX_PIN", 1, INT_MIN, INT_MAX) != 0;          // unset or non-zero = pin to the GPU's NUMA node
+    const bool timing = getenv("BSX_TIMING") != nullptr;                    // set = the JSON line and the pin messages on stderr ...
+    const bool events = env_int("BSX_TIMING", 0, INT_MIN, INT_MAX) >= 2;    // ... >= 2 = the events line too
+    const char *const write = getenv("BSX_WRITE");                          // mmap | anything else = pwrite; null = by the output's file system
+    const int write_threads = env_int("BSX_WRITE_THREADS", 0, 1, INT_MAX);  // threads of the mapped writer, >= 1; 0 = not set
+    const bool work_counters = getenv("BSX_WORK_COUNTERS") != nullptr;      // set = the batches keep their work counters
+    // starting pool of --all-hits in words, >= 1; 0 = not set
+    const long long all_hits_pool = getenv("BSX_ALL_HITS_POOL") ? max(1ll, atoll(getenv("BSX_ALL_HITS_POOL"))) : 0;
+    const bool p1_exact = env_int("BSX_P1_EXACT", 0, INT_MIN, INT_MAX) != 0;  // non-zero = the single-threaded reference's planner state for every read
+};
+
 // ---- the mapping pipeline ---------------------------------------------------------------------------------------------
-// Four stages run concurrently on a ring of batches, each stage taking the batches in input order:
+// Four stages run concurrently on a ring of batches (bsx_ring.h), each stage taking the batches in input order:
 //   parse (one thread per read file)  ->  GPU (upload, Do_Batch, results)  ->  format (-p worker threads)  ->  write
 // so the output stays in input order whatever the thread count (the reference's order is only defined for -p 1).
-// The GPU stage has two device batches driven by two threads: while one batch is in its scan passes (VALU-bound) the
+// The GPU stage has several device batches per GPU, each driven by a thread: while one batch is in its scan passes (VALU-bound) the
 // other one's reads go up, its latency-bound main kernel runs, and its records come down.
-struct Slot {
+struct Slot : bsx_ring::SlotState {  // stage: 0 free, 1 parsed, 2 aligned, 3 formatted
     ReadSet A, B;
     size_t n = 0;
     unsigned total_after = 0;
@@ -571,32 +593,75 @@ struct Slot {
     vector<bsx_span> spans;      // --all-hits: [n][3], the words they point into, the side file's lines by format worker
     vector<uint32_t> ah_words;
     vector<Text> out_all;
-    int stage = 0;  // 0 free, 1 parsed, 2 aligned, 3 formatted
-    long batch = -1;  // ordinal of the batch the slot holds while stage != 0
 };
 
-struct Ring {
-    const int NS;
-    vector<Slot> slot;
-    explicit Ring(int ns) : NS(ns), slot(ns) {}
-    mutex mu;
-    condition_variable cv;
-    long n_batches = -1;  // known once the parser reaches the end of the input
-    Slot &at(long k) { return slot[k % NS]; }
-    // wait until batch k is in `stage`; false when the input ended before batch k.  A slot is shared by the batches
-    // k, k+NS, ...: a consumer must not mistake an older batch that is still in the same stage for its own, so the slot
-    // carries the ordinal of the batch it holds (stage 0 = free: the parser takes it for whatever batch comes next).
-    bool acquire(long k, int stage)
+// what is fixed before the stages start
+struct RunShape {
+    int ND, NB, NC, NG;   // GPUs, device batches per GPU, how many of them may be in their kernels at once, GPU-stage threads (ND * NB)
+    int workers;          // format workers
+    unsigned ncpu;        // CPUs this process may use (a lane: its share)
+    bool pe, bam_out;
+    bool map_out;         // the output goes through a shared mapping of the file (known once it is open)
+    int map_threads;
+    bool all_on, p1_exact, ev_on;
+};
+
+// the output files; once the headers are written, only the write stage (main thread) and the writer threads it joins per batch touch them
+struct Outputs {
+    int fout = -1, fout_unpair = -1, fout_all = -1;
+    off_t off_out = 0, off_unpair = 0, off_all = 0;   // where the next batch's text goes
+    bsx_bam::Sink bam;
+};
+
+struct StageStats {
+    struct Ev { long k; int stage; double t0, t1; };   // BSX_TIMING=2: when which batch was in which stage (0 parse, 1 upload, 2 align, 3 read-back, 4 format, 5 write)
+    const bool ev_on;
+    mutex mu;                          // guards what more than one thread writes: busy[1], gpu_part, events
+    double busy[4] = {0, 0, 0, 0};     // wall time of the stages: [0] parse thread, [1] the GPU threads (under mu), [2] format thread, [3] write stage (main thread)
+    double gpu_part[3] = {0, 0, 0};    // upload, align, read-back: the GPU threads (under mu)
+    std::atomic<long long> cpu_ns[4];  // CPU time of the stages' threads — parse and mate parser, GPU drivers, format workers, writer threads: each adds its own
+    vector<Ev> events;                 // every stage's thread (under mu); empty unless ev_on
+    explicit StageStats(bool ev) : ev_on(ev) { for (auto &c : cpu_ns) c = 0; }
+    void add_cpu(int st, double c0) { cpu_ns[st] += (long long)((thread_cpu_s() - c0) * 1e9); }
+    void log_ev(long k, int stage, double a, double b) { if (ev_on) { lock_guard<mutex> lk(mu); events.push_back({k, stage, a, b}); } }
+    void add_gpu(long k, double t, double t1, double t2, double t3)   // one batch of a GPU thread: upload until t1, align until t2, read-back until t3
     {
-        unique_lock<mutex> lk(mu);
-        cv.wait(lk, [&] { return (n_batches >= 0 && k >= n_batches) || (at(k).stage == stage && (stage == 0 || at(k).batch == k)); });
-        return !(n_batches >= 0 && k >= n_batches);
+        lock_guard<mutex> lk(mu);
+        busy[1] += t3 - t; gpu_part[0] += t1 - t; gpu_part[1] += t2 - t1; gpu_part[2] += t3 - t2;
+        if (ev_on) { events.push_back({k, 1, t, t1}); events.push_back({k, 2, t1, t2}); events.push_back({k, 3, t2, t3}); }
     }
-    void release(long k, int stage) { { lock_guard<mutex> lk(mu); at(k).stage = stage; at(k).batch = stage ? k : -1; } cv.notify_all(); }
-    void finish(long n) { { lock_guard<mutex> lk(mu); n_batches = n; } cv.notify_all(); }
 };
 
-double now_s() { return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count(); }
+// ---- what a run reports: one LaneStats, filled by the single pipeline, by a lane, or summed over the lanes by their parent -----
+void print_summary(bool pe, const LaneStats &s, time_t t_begin)
+{
+    char pct[64];
+    const double total = (double)s.total;
+    if (pe) {
+        cout << "Total number of aligned reads: \n";
+        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * s.n_pairs / total : 0.0); cout << "pairs:       " << s.n_pairs << " (" << pct << "%)\n";
+        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * s.n_a / total : 0.0); cout << "single a:    " << s.n_a << " (" << pct << "%)\n";
+        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * s.n_b / total : 0.0); cout << "single b:    " << s.n_b << " (" << pct << "%)\n";
+    } else {
+        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * s.n_aligned / total : 0.0);
+        cout << "Total number of aligned reads: " << s.n_aligned << " (" << pct << "%)\n";
+    }
+    cout << "Done.\n";
+    time_t t_end = time(NULL);
+    cout << "Finished at " << ctime(&t_end);
+    cout << "Total time consumed:  " << t_end - t_begin << " secs\n";
+}
+// BSX_TIMING: machine-readable phase times (extension; stderr so that stdout keeps the reference's lines).  lanes > 0: the parent's line for the whole run
+void print_timing_json(bool pe, const LaneStats &s, unsigned ncpu, int lanes = 0, double join_s = 0)
+{
+    char head[64] = "", join[64] = "";
+    if (lanes) { snprintf(head, sizeof head, "\"lanes\": %d, ", lanes); snprintf(join, sizeof join, "\"join_s\": %.3f, ", join_s); }
+    fprintf(stderr, "{%s\"load_reference_s\": %.3f, \"index_build_s\": %.3f, \"mapping_s\": %.3f, %s\"units\": %llu, \"reads\": %llu, \"workers\": %d, \"usable_cpus\": %u, "
+                    "\"mapping_cpu_s\": {\"user\": %.2f, \"sys\": %.2f, \"parse_threads\": %.2f, \"gpu_driver_threads\": %.2f, \"format_workers\": %.2f, \"write_threads\": %.2f}, "
+                    "\"stage_busy_s\": {\"parse\": %.3f, \"gpu\": %.3f, \"format\": %.3f, \"write\": %.3f, \"gpu_upload\": %.3f, \"gpu_align\": %.3f, \"gpu_readback\": %.3f}}\n",
+            head, s.load_s, s.index_s, s.mapping_s, join, s.total, pe ? 2 * s.total : s.total, s.workers, ncpu, s.cpu_user, s.cpu_sys,
+            s.stage_cpu[0], s.stage_cpu[1], s.stage_cpu[2], s.stage_cpu[3], s.busy[0], s.busy[1], s.busy[2], s.busy[3], s.gpu_part[0], s.gpu_part[1], s.gpu_part[2]);
+}
 
 // ---- lanes ----------------------------------------------------------------------------------------------------------------
 // `--lanes`: the run is cut into ranges of reads and every range is mapped by a process of its own with its own GPU, reader,
@@ -653,41 +718,53 @@ bool join_files(const string &dst, const vector<string> &parts, int nthreads)
     return ok;
 }
 
-// Returns -1 when the run is not cut (no --lanes, or the input cannot be cut: the caller goes on as the single pipeline), the lane
-// index in a lane process (LaneInfo filled in, Opts narrowed to the lane's range, device and output file), and does not return in
-// the parent, which exits with the run's status once every lane is done.
-int fork_lanes(Opts &o, LaneInfo &lane, time_t t_begin)
+// the parent's view of its lanes
+struct LaneRun {
+    bsx_lanes::Plan plan;
+    int L = 0;
+    unsigned ncpu = 0;
+    vector<pid_t> pids;
+    vector<int> stats_fd, state_fd;   // per lane: where its LaneStats come from; where its planner state goes (BSX_P1_EXACT)
+    int ready_fd = -1, go_fd = -1;    // the lanes say when they are ready to map; the parent releases all of them together
+    string out0, unpair0, all0;       // the names the user asked for (lane l writes <name>.<l>)
+};
+
+// plan: false (and the reason on stderr) when the run is not cut
+bool plan_lanes(Opts &o, bool pe, LaneRun &R)
 {
-    if (!o.lanes) return -1;
-    const bool pe = !o.a_file.empty() && !o.b_file.empty();
     const char *why = nullptr;
     if (o.out_sam == 2) why = "BAM output is sorted over the whole run";
-    const bool p1_exact = getenv("BSX_P1_EXACT") && atoi(getenv("BSX_P1_EXACT")) != 0;   // (round 6: composes with lanes, see the parent's loop below)
     if (o.devices_all) { o.devices.clear(); const int n = count_devices_in_a_child(); for (int d = 0; d < n; d++) o.devices.push_back(d); o.devices_all = false; }
     if (o.devices.empty()) o.devices.push_back(0);
     const int want = o.lanes > 0 ? o.lanes : (int)o.devices.size();
     bsx_lanes::LineIndex ia, ib;
-    bsx_lanes::Plan plan;
     if (!why) {
         const unsigned nthreads = bsx_usable_cpus();
         thread tb;
         if (pe) tb = thread([&] { bsx_lanes::index_lines(o.b_file, (int)max(1u, nthreads / 2), ib); });
         bsx_lanes::index_lines(o.a_file, (int)max(1u, pe ? nthreads / 2 : nthreads), ia);
         if (pe) tb.join();
-        plan = bsx_lanes::plan_lanes(ia, pe ? &ib : nullptr, want, o.read_start, o.read_end);
-        if (plan.lanes.empty()) why = plan.why_not.c_str();
+        R.plan = bsx_lanes::plan_lanes(ia, pe ? &ib : nullptr, want, o.read_start, o.read_end);
+        if (R.plan.lanes.empty()) why = R.plan.why_not.c_str();
     }
-    if (why) { cerr << "bsx: --lanes: the run is not cut (" << why << "); one pipeline\n"; o.lanes = 0; return -1; }
-    if (plan.mates_differ)
-        cerr << "warning: mate files differ in length (" << plan.n_a << " vs " << plan.n_b << " reads); like the reference, mapping stops after pair "
-             << (o.read_start - 1) + plan.total << endl;
-    const int L = (int)plan.lanes.size();
-    const unsigned ncpu = bsx_usable_cpus(), share = max(2u, ncpu / (unsigned)L);
-    vector<pid_t> pids(L, -1);
-    vector<int> fds(L, -1), sfds(L, -1);
+    if (why) { cerr << "bsx: --lanes: the run is not cut (" << why << "); one pipeline\n"; o.lanes = 0; return false; }
+    if (R.plan.mates_differ)
+        cerr << "warning: mate files differ in length (" << R.plan.n_a << " vs " << R.plan.n_b << " reads); like the reference, mapping stops after pair "
+             << (o.read_start - 1) + R.plan.total << endl;
+    R.L = (int)R.plan.lanes.size();
+    R.ncpu = bsx_usable_cpus();
+    R.out0 = o.out_file; R.unpair0 = o.out_unpair; R.all0 = o.all_hits;
+    return true;
+}
+
+// spawn: the lane index in a lane process (LaneInfo filled in, Opts narrowed to the lane's range, device and output file), -1 in the parent
+int spawn_lanes(Opts &o, LaneInfo &lane, bool p1_exact, LaneRun &R)
+{
+    const int L = R.L;
+    const unsigned share = max(2u, R.ncpu / (unsigned)L);
+    R.pids.assign(L, -1); R.stats_fd.assign(L, -1); R.state_fd.assign(L, -1);
     int ready[2], go[2];
     if (pipe(ready) != 0 || pipe(go) != 0) { cerr << "bsx: pipe failed\n"; exit(1); }
-    const string out0 = o.out_file, unpair0 = o.out_unpair, all0 = o.all_hits;
     const vector<int> devs = o.devices;
     const unsigned end0 = o.read_end;
     cout.flush(); cerr.flush();
@@ -697,123 +774,156 @@ int fork_lanes(Opts &o, LaneInfo &lane, time_t t_begin)
         const pid_t pid = fork();
         if (pid < 0) { cerr << "bsx: fork failed\n"; exit(1); }
         if (pid == 0) {
-            for (int k = 0; k < l; k++) { ::close(fds[k]); if (sfds[k] >= 0) ::close(sfds[k]); }
+            for (int k = 0; k < l; k++) { ::close(R.stats_fd[k]); if (R.state_fd[k] >= 0) ::close(R.state_fd[k]); }
             ::close(fd[0]); ::close(ready[0]); ::close(go[1]);
             if (p1_exact) ::close(sfd[1]);
             lane.ready_fd = ready[1]; lane.go_fd = go[0]; lane.state_fd = sfd[0];
-            const bsx_lanes::Lane &R = plan.lanes[l];
-            lane.index = l; lane.n = L; lane.stats_fd = fd[1]; lane.off_a = R.off_a; lane.off_b = R.off_b;
-            lane.cpus = share; lane.final_out = out0; lane.final_unpair = unpair0;
+            const bsx_lanes::Lane &r = R.plan.lanes[l];
+            lane.index = l; lane.n = L; lane.stats_fd = fd[1]; lane.off_a = r.off_a; lane.off_b = r.off_b;
+            lane.cpus = share; lane.final_out = R.out0; lane.final_unpair = R.unpair0;
             for (int k = 0; k < L; k++) lane.lane_devices.push_back(devs[(size_t)k % devs.size()]);
-            o.read_start = (unsigned)(R.first + 1);
+            o.read_start = (unsigned)(r.first + 1);
             // the last lane keeps the user's -E when nothing was cut off: a ragged tail of the file is then parsed exactly as one pipeline would
-            o.read_end = (l == L - 1 && !plan.mates_differ) ? end0 : (unsigned)(R.first + R.count);
+            o.read_end = (l == L - 1 && !R.plan.mates_differ) ? end0 : (unsigned)(r.first + r.count);
             o.devices.assign(1, devs[(size_t)l % devs.size()]);
-            o.out_file = out0 + "." + to_string(l);
-            if (!unpair0.empty()) o.out_unpair = unpair0 + "." + to_string(l);
-            if (!all0.empty()) o.all_hits = all0 + "." + to_string(l);
+            o.out_file = R.out0 + "." + to_string(l);
+            if (!R.unpair0.empty()) o.out_unpair = R.unpair0 + "." + to_string(l);
+            if (!R.all0.empty()) o.all_hits = R.all0 + "." + to_string(l);
             if (l > 0) { if (!freopen("/dev/null", "w", stdout)) {} }   // lane 0 keeps the reference's progress lines
             return l;
         }
         ::close(fd[1]);
         if (p1_exact) ::close(sfd[0]);
-        pids[l] = pid; fds[l] = fd[0]; sfds[l] = sfd[1];
+        R.pids[l] = pid; R.stats_fd[l] = fd[0]; R.state_fd[l] = sfd[1];
     }
-    // parent: once every lane has its reference and index (or has died: its end of the pipe closes), all start mapping
     ::close(ready[1]); ::close(go[0]);
-    if (!p1_exact) { for (int got = 0; got < L;) { char c[64]; const ssize_t r = read(ready[0], c, sizeof c); if (r <= 0) break; got += (int)r; } }
-    else {
-        // BSX_P1_EXACT across lanes.  What the reads of a range do to the reference's never-reset planner state (align.h:82-91) does not depend on the state they
-        // find: a read either writes a slot — start offset, seed_array entry — with a value of its own, or leaves it.  Every lane first sweeps its range with the
-        // pre-pass alone (upload, k_leak_meta, k_leak_final; no alignment) from a state of MARKER words and sends what comes out: its range's effect, marker = "left
-        // alone".  The state at lane j's first read is then, slot by slot, the effect of the nearest earlier lane that wrote the slot, zero (a fresh aligner
-        // object) if none did — composed here, where no GPU is touched, and handed back before the lanes start mapping.  One message per lane (lane index + state:
-        // under PIPE_BUF, so the writes of different lanes never interleave).
-        signal(SIGPIPE, SIG_IGN);   // (a lane that died before it could listen: its stats pipe reports it below)
-        const size_t W = BSX_LEAK_STATE_BYTES / 4, MSG = 1 + BSX_LEAK_STATE_BYTES;
-        vector<vector<uint32_t>> eff((size_t)L, vector<uint32_t>(W, 0xFFFFFFFFu));
-        vector<char> have((size_t)L, 0);
-        vector<unsigned char> msg(MSG);
-        for (int got = 0; got < L; got++) {
-            size_t n = 0;
-            while (n < MSG) { const ssize_t r = read(ready[0], msg.data() + n, MSG - n); if (r <= 0) break; n += (size_t)r; }
-            if (n < MSG || msg[0] >= (unsigned)L) break;   // (a lane died: its stats pipe will say so)
-            memcpy(eff[msg[0]].data(), msg.data() + 1, BSX_LEAK_STATE_BYTES); have[msg[0]] = 1;
-        }
-        const vector<vector<uint32_t>> start = bsx_lanes::compose_lane_states(eff, have, W);   // (lane 0: a fresh object; tests/test_lanes_cpu.py)
-        for (int l = 0; l < L; l++) {
-            const ssize_t w = write(sfds[l], start[(size_t)l].data(), BSX_LEAK_STATE_BYTES); (void)w;
-            ::close(sfds[l]);
-        }
+    R.ready_fd = ready[0]; R.go_fd = go[1];
+    return -1;
+}
+
+// BSX_P1_EXACT across lanes.  What the reads of a range do to the reference's never-reset planner state (align.h:82-91) does not depend on the state they
+// find: a read either writes a slot — start offset, seed_array entry — with a value of its own, or leaves it.  Every lane first sweeps its range with the
+// pre-pass alone (upload, k_leak_meta, k_leak_final; no alignment) from a state of MARKER words and sends what comes out: its range's effect, marker = "left
+// alone".  The state at lane j's first read is then, slot by slot, the effect of the nearest earlier lane that wrote the slot, zero (a fresh aligner
+// object) if none did — composed here, where no GPU is touched, and handed back before the lanes start mapping.  One message per lane (lane index + state:
+// under PIPE_BUF, so the writes of different lanes never interleave).
+void compose_lane_states(const LaneRun &R)
+{
+    const int L = R.L;
+    signal(SIGPIPE, SIG_IGN);   // (a lane that died before it could listen: its stats pipe reports it later)
+    const size_t W = BSX_LEAK_STATE_BYTES / 4, MSG = 1 + BSX_LEAK_STATE_BYTES;
+    vector<vector<uint32_t>> eff((size_t)L, vector<uint32_t>(W, 0xFFFFFFFFu));
+    vector<char> have((size_t)L, 0);
+    vector<unsigned char> msg(MSG);
+    for (int got = 0; got < L; got++) {
+        size_t n = 0;
+        while (n < MSG) { const ssize_t r = read(R.ready_fd, msg.data() + n, MSG - n); if (r <= 0) break; n += (size_t)r; }
+        if (n < MSG || msg[0] >= (unsigned)L) break;   // (a lane died: its stats pipe will say so)
+        memcpy(eff[msg[0]].data(), msg.data() + 1, BSX_LEAK_STATE_BYTES); have[msg[0]] = 1;
     }
-    { const string all((size_t)L, 'g'); const ssize_t w = write(go[1], all.data(), all.size()); (void)w; }
-    ::close(ready[0]); ::close(go[1]);
-    LaneStats tot; memset(&tot, 0, sizeof tot);
-    bool ok = true;
-    double map_max = 0, load_max = 0, index_max = 0, first_start = 1e300, last_end = 0;
+    const vector<vector<uint32_t>> start = bsx_lanes::compose_lane_states(eff, have, W);   // (lane 0: a fresh object; tests/test_lanes_cpu.py)
     for (int l = 0; l < L; l++) {
+        const ssize_t w = write(R.state_fd[l], start[(size_t)l].data(), BSX_LEAK_STATE_BYTES); (void)w;
+        ::close(R.state_fd[l]);
+    }
+}
+
+// rendezvous: once every lane has its reference and index (or has died: its end of the pipe closes), all start mapping
+void release_lanes(const LaneRun &R, bool p1_exact)
+{
+    if (!p1_exact) { for (int got = 0; got < R.L;) { char c[64]; const ssize_t r = read(R.ready_fd, c, sizeof c); if (r <= 0) break; got += (int)r; } }
+    else compose_lane_states(R);
+    { const string all((size_t)R.L, 'g'); const ssize_t w = write(R.go_fd, all.data(), all.size()); (void)w; }
+    ::close(R.ready_fd); ::close(R.go_fd);
+}
+
+// collect: the run's LaneStats from the lanes' — counters, CPU times and GPU parts added up, phase and stage times the slowest lane's, t_map0 / t_map1 the
+// first start and the last end of a mapping phase; false when a lane failed
+bool collect_lanes(const LaneRun &R, LaneStats &tot)
+{
+    memset(&tot, 0, sizeof tot);
+    tot.t_map0 = 1e300;
+    bool ok = true;
+    for (int l = 0; l < R.L; l++) {
         LaneStats st; memset(&st, 0, sizeof st);
         size_t got = 0;
-        while (got < sizeof st) { const ssize_t r = read(fds[l], (char *)&st + got, sizeof st - got); if (r <= 0) break; got += (size_t)r; }
-        ::close(fds[l]);
+        while (got < sizeof st) { const ssize_t r = read(R.stats_fd[l], (char *)&st + got, sizeof st - got); if (r <= 0) break; got += (size_t)r; }
+        ::close(R.stats_fd[l]);
         int status = 0;
-        waitpid(pids[l], &status, 0);
+        waitpid(R.pids[l], &status, 0);
         if (got != sizeof st || !WIFEXITED(status) || WEXITSTATUS(status) != 0) { cerr << "bsx: lane " << l << " failed\n"; ok = false; continue; }
         tot.total += st.total; tot.n_aligned += st.n_aligned; tot.n_pairs += st.n_pairs; tot.n_a += st.n_a; tot.n_b += st.n_b;
         tot.cpu_user += st.cpu_user; tot.cpu_sys += st.cpu_sys; tot.workers += st.workers;
         for (int k = 0; k < 4; k++) { tot.stage_cpu[k] += st.stage_cpu[k]; tot.busy[k] = max(tot.busy[k], st.busy[k]); }
         for (int k = 0; k < 3; k++) tot.gpu_part[k] += st.gpu_part[k];
-        map_max = max(map_max, st.mapping_s); load_max = max(load_max, st.load_s); index_max = max(index_max, st.index_s);
-        first_start = min(first_start, st.t_map0); last_end = max(last_end, st.t_map1);
+        tot.load_s = max(tot.load_s, st.load_s); tot.index_s = max(tot.index_s, st.index_s);
+        tot.t_map0 = min(tot.t_map0, st.t_map0); tot.t_map1 = max(tot.t_map1, st.t_map1);
     }
-    if (!ok) exit(1);
+    return ok;
+}
+
+// join: the lane files into the files the user asked for, in lane order
+void join_lane_files(const Opts &o, bool pe, const LaneRun &R)
+{
+    vector<string> parts, parts2;
+    for (int l = 0; l < R.L; l++) { parts.push_back(R.out0 + "." + to_string(l)); if (!R.unpair0.empty() && !o.out_sam && pe) parts2.push_back(R.unpair0 + "." + to_string(l)); }
+    bsx_textout::install_sigbus_handler();   // (the join writes through shared mappings of a sparsely extended file: a full tmpfs is a SIGBUS here, too)
+    if (!join_files(R.out0, parts, (int)R.ncpu) || (!parts2.empty() && !join_files(R.unpair0, parts2, (int)R.ncpu))) { cerr << "write error on the output file (joining the lanes)\n"; exit(1); }
+    if (!R.all0.empty()) {   // (lane 0's file carries the header line)
+        vector<string> parts3;
+        for (int l = 0; l < R.L; l++) parts3.push_back(R.all0 + "." + to_string(l));
+        if (!join_files(R.all0, parts3, (int)R.ncpu)) { cerr << "write error on the --all-hits file (joining the lanes)\n"; exit(1); }
+    }
+}
+
+// Returns -1 when the run is not cut (no --lanes, or the input cannot be cut: the caller goes on as the single pipeline), the lane
+// index in a lane process (LaneInfo filled in, Opts narrowed to the lane's range, device and output file), and does not return in
+// the parent, which exits with the run's status once every lane is done.
+int fork_lanes(Opts &o, LaneInfo &lane, const Knobs &kn, time_t t_begin)
+{
+    if (!o.lanes) return -1;
+    const bool pe = !o.a_file.empty() && !o.b_file.empty();
+    LaneRun R;
+    if (!plan_lanes(o, pe, R)) return -1;
+    const int l = spawn_lanes(o, lane, kn.p1_exact, R);
+    if (l >= 0) return l;
+    release_lanes(R, kn.p1_exact);
+    LaneStats tot;
+    if (!collect_lanes(R, tot)) exit(1);
     const double t_join0 = now_s();
-    if (!o.lane_files) {
-        vector<string> parts, parts2;
-        for (int l = 0; l < L; l++) { parts.push_back(out0 + "." + to_string(l)); if (!unpair0.empty() && !o.out_sam && pe) parts2.push_back(unpair0 + "." + to_string(l)); }
-        bsx_textout::install_sigbus_handler();   // (the join writes through shared mappings of a sparsely extended file: a full tmpfs is a SIGBUS here, too)
-        if (!join_files(out0, parts, (int)ncpu) || (!parts2.empty() && !join_files(unpair0, parts2, (int)ncpu))) { cerr << "write error on the output file (joining the lanes)\n"; exit(1); }
-        if (!all0.empty()) {   // (lane 0's file carries the header line)
-            vector<string> parts3;
-            for (int l = 0; l < L; l++) parts3.push_back(all0 + "." + to_string(l));
-            if (!join_files(all0, parts3, (int)ncpu)) { cerr << "write error on the --all-hits file (joining the lanes)\n"; exit(1); }
-        }
-    }
+    if (!o.lane_files) join_lane_files(o, pe, R);
     const double join_s = now_s() - t_join0;
-    char pct[64];
-    const double total = (double)tot.total;
-    if (pe) {
-        cout << "Total number of aligned reads: \n";
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * tot.n_pairs / total : 0.0); cout << "pairs:       " << tot.n_pairs << " (" << pct << "%)\n";
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * tot.n_a / total : 0.0); cout << "single a:    " << tot.n_a << " (" << pct << "%)\n";
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * tot.n_b / total : 0.0); cout << "single b:    " << tot.n_b << " (" << pct << "%)\n";
-    } else {
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * tot.n_aligned / total : 0.0);
-        cout << "Total number of aligned reads: " << tot.n_aligned << " (" << pct << "%)\n";
-    }
-    cout << "Done.\n";
-    time_t t_end = time(NULL);
-    cout << "Finished at " << ctime(&t_end);
-    cout << "Total time consumed:  " << t_end - t_begin << " secs\n";
-    if (getenv("BSX_TIMING"))
-        fprintf(stderr, "{\"lanes\": %d, \"load_reference_s\": %.3f, \"index_build_s\": %.3f, \"mapping_s\": %.3f, \"join_s\": %.3f, \"units\": %llu, \"reads\": %llu, \"workers\": %d, \"usable_cpus\": %u, "
-                        "\"mapping_cpu_s\": {\"user\": %.2f, \"sys\": %.2f, \"parse_threads\": %.2f, \"gpu_driver_threads\": %.2f, \"format_workers\": %.2f, \"write_threads\": %.2f}, "
-                        "\"stage_busy_s\": {\"parse\": %.3f, \"gpu\": %.3f, \"format\": %.3f, \"write\": %.3f, \"gpu_upload\": %.3f, \"gpu_align\": %.3f, \"gpu_readback\": %.3f}}\n",
-                L, load_max, index_max, (last_end - first_start) + join_s, join_s, tot.total, pe ? 2 * tot.total : tot.total, tot.workers, ncpu, tot.cpu_user, tot.cpu_sys,
-                tot.stage_cpu[0], tot.stage_cpu[1], tot.stage_cpu[2], tot.stage_cpu[3], tot.busy[0], tot.busy[1], tot.busy[2], tot.busy[3], tot.gpu_part[0], tot.gpu_part[1], tot.gpu_part[2]);
+    tot.mapping_s = (tot.t_map1 - tot.t_map0) + join_s;
+    print_summary(pe, tot, t_begin);
+    if (kn.timing) print_timing_json(pe, tot, R.ncpu, R.L, join_s);
     exit(0);
 }
 
-}  // namespace
+// ---- the single pipeline (also what a lane runs) ---------------------------------------------------------------------------
+// The ring's upload / download buffers are page-locked (the transfers are then plain DMA).
+const RawAlloc pinned_alloc = {bsx_pinned_alloc, bsx_pinned_free};
 
-int main(int argc, char **argv)
+void write_all(int fd, const char *p_, size_t n_, off_t at)
 {
-    cout << "\nBSMAP v" << version << endl;
-    if (argc == 1) usage();
-    time_t t_begin = time(NULL);
-    const double t0 = now_s();
-    cout << "Start at:  " << ctime(&t_begin) << endl;
-    Opts o;
+    while (n_) {
+        const ssize_t w = pwrite(fd, p_, n_, at);
+        if (w <= 0) { cerr << "write error on the output file\n"; fatal_exit(); }
+        p_ += w; n_ -= (size_t)w; at += w;
+    }
+}
+// Output on tmpfs (/dev/shm) goes through a shared mapping of the file instead of pwrite: buffered writes into ONE file hold the inode's
+// lock, so 1 or 14 threads move the same 5-6 GB/s (tools/microbench/shm_write.cpp), while page faults on a mapping run in parallel
+// (8 threads: 8 GB/s).  BSX_WRITE=pwrite|mmap overrides the choice.  A full file system then shows up as SIGBUS, reported like a write error.
+bool use_map(int fd, const Knobs &kn)
+{
+    if (kn.write) return strcmp(kn.write, "mmap") == 0;
+    struct statfs sf;
+    return fstatfs(fd, &sf) == 0 && (unsigned long)sf.f_type == 0x01021994ul;  // TMPFS_MAGIC
+}
+
+// 1. the options as the run uses them; every error of the command line that needs no GPU is reported here
+void finish_options(int argc, char **argv, Opts &o, const Knobs &kn)
+{
     bsx_params_default(&o.p);
     if (int bad = parse_options(argc, argv, o)) { cout << "unknown option: " << argv[bad] << endl; exit(bad); }
     if (o.out_file.size() > 4) {
@@ -821,24 +931,24 @@ int main(int argc, char **argv)
         else if (o.out_file.compare(o.out_file.size() - 4, 4, ".bam") == 0) o.out_sam = 2;  // SAM records, delivered as sorted BAM + index (main.cpp:295,466-473)
     }
     o.p.out_sam = o.out_sam;
-    if (const char *e = getenv("BSX_BATCH")) o.batch = (unsigned)max(1, atoi(e));  // units per batch (default 2^20)
-    int rc = bsx_params_finish(&o.p);
+    if (kn.batch) o.batch = (unsigned)kn.batch;  // units per batch
+    const int rc = bsx_params_finish(&o.p);
     if (rc) die(rc, "bad option value");
-    const bsx_params &p = o.p;
-    if (!o.all_hits.empty() && p.report_repeat_hits != 1) {
+    if (!o.all_hits.empty() && o.p.report_repeat_hits != 1) {
         cerr << "--all-hits needs -r 1: with -r 0 a scan stops at the second hit of the best class and the lists are cut short\n";
         exit(1);
     }
-    { ifstream t(o.ref_file.c_str()); if (!t) { cerr << "fatal error: failed to open ref file\n"; exit(1); } }
-    // --lanes: from here on a lane process sees its own range of reads, its GPU and its output file; the parent does not come back
-    LaneInfo lane;
-    fork_lanes(o, lane, t_begin);
+    ifstream t(o.ref_file.c_str());
+    if (!t) { cerr << "fatal error: failed to open ref file\n"; exit(1); }
+}
+
+// 3. the run shape: GPUs, device batches, threads (o.devices resolved, o.batch cut down for lanes that share a GPU)
+RunShape choose_shape(Opts &o, const LaneInfo &lane, const Knobs &kn)
+{
+    RunShape sh;
     if (o.devices_all) { o.devices.clear(); const int n = bsx_device_count(); for (int d = 0; d < n; d++) o.devices.push_back(d); }
-    // The ring's upload / download buffers are page-locked (the transfers are then plain DMA).  Locking gigabytes of pages
-    // takes seconds, so it happens on a side thread while the reference is loaded and indexed.
-    static const RawAlloc pinned = {bsx_pinned_alloc, bsx_pinned_free};
     if (o.devices.empty()) o.devices.push_back(0);
-    const int ND = (int)o.devices.size();
+    sh.ND = (int)o.devices.size();
     // device batches per GPU.  Runs that start together end together (equal work, the GPU shared evenly), so with two batches per GPU
     // every upload and read-back happened beside an idle GPU; with three the runs no longer line up and one batch's transfers fall under
     // the others' kernels (12.6 -> 13.1 M reads/s end to end at hg38 size).  BSX_GPU_COMPUTE < BSX_GPU_BATCHES additionally limits how
@@ -847,42 +957,89 @@ int main(int argc, char **argv)
     // (lanes that share one GPU share its memory too: fewer device batches each, and smaller ones)
     int lanes_on_gpu = 1;
     if (lane.index >= 0) { lanes_on_gpu = 0; for (int d : lane.lane_devices) lanes_on_gpu += d == o.devices[0]; }
-    if (lanes_on_gpu > 1 && !getenv("BSX_BATCH")) o.batch = max(50000u, (o.batch / (unsigned)lanes_on_gpu + 49999u) / 50000u * 50000u);
-    const int NB = getenv("BSX_GPU_BATCHES") ? max(1, min(8, atoi(getenv("BSX_GPU_BATCHES")))) : max(1, (p.rrbs ? 2 : 3) / (lanes_on_gpu > 2 ? lanes_on_gpu - 1 : 1));
-    const int NC = getenv("BSX_GPU_COMPUTE") ? max(1, min(NB, atoi(getenv("BSX_GPU_COMPUTE")))) : NB;
-    const int NG = ND * NB;                                                                          // GPU-stage threads
-    Ring &ring = *new Ring(max(6, NG + 4));  // never freed: error paths exit() while side threads may still touch it
-    const bool pe = !o.a_file.empty() && !o.b_file.empty();
+    if (lanes_on_gpu > 1 && !kn.batch) o.batch = max(50000u, (o.batch / (unsigned)lanes_on_gpu + 49999u) / 50000u * 50000u);
+    sh.NB = kn.gpu_batches ? kn.gpu_batches : max(1, (o.p.rrbs ? 2 : 3) / (lanes_on_gpu > 2 ? lanes_on_gpu - 1 : 1));
+    sh.NC = kn.gpu_compute ? min(sh.NB, kn.gpu_compute) : sh.NB;
+    sh.NG = sh.ND * sh.NB;
+    sh.pe = !o.a_file.empty() && !o.b_file.empty();
     // format workers: the CPUs this process may use (affinity mask and cgroup quota, not the hardware thread count) less the
     // parse, GPU-driver and write threads; oversubscribing a quota throttles every thread, the ones feeding the GPU included
-    const unsigned ncpu = lane.index >= 0 ? lane.cpus : bsx_usable_cpus();   // (a lane: its share of the run's CPUs)
-    // under a quota: keep the whole process on as many CPUs of the GPU's NUMA node as the quota is worth (BSX_PIN=0: leave the mask alone)
+    sh.ncpu = lane.index >= 0 ? lane.cpus : bsx_usable_cpus();   // (a lane: its share of the run's CPUs)
+    // (measured on the 16-CPU quota of the GPU boxes with the GPU stage nearly free, tools/host_threads.sh: 10 workers 10.0 M reads/s, 12: 10.6,
+    //  14: 12.8 — the driver threads of the device batches sleep on events and the two parse threads are light)
+    sh.workers = o.num_procs > 0 ? o.num_procs : (int)min(64u, max(1u, sh.ncpu > 4 ? sh.ncpu - 2 : sh.ncpu));
+    sh.bam_out = o.out_sam == 2;
+    sh.map_out = false;
+    sh.map_threads = kn.write_threads ? kn.write_threads : (int)max(1u, min(12u, sh.ncpu));  // (4 / 8 / 14 threads: 18 / 21 / 22 M reads/s with the GPU stage nearly free; pwrite 16)
+    sh.all_on = !o.all_hits.empty();
+    sh.p1_exact = kn.p1_exact;
+    sh.ev_on = kn.events;
+    return sh;
+}
+
+struct Pipeline {
+    // fixed by main() before any stage runs
+    Opts &o;
+    const Knobs &kn;
+    const LaneInfo &lane;
+    RunShape sh;
+    const time_t t_begin;
+    RefView rv;
+    // resources: created by main(); the stages use the batch and ring slot the ring's protocol gives them
+    vector<bsx_ref *> refs;        // one replica of reference + index per GPU
+    vector<bsx_batch *> batches;   // GPU-stage thread g drives batches[g]
+    bsx_ring::Ring<Slot> ring;
+    ReadOpts ro;
+    Reader ra, rb;                 // the parse thread (rb: its helper thread for mate B)
+    Outputs out;
+    // exact mode: the planner state behind the last batch that has uploaded; compute slots per GPU (gates[d]: the batches k with (k % NG) % ND == d)
+    bsx_ring::LeakChain<vector<unsigned char>> chain;
+    vector<bsx_ring::Gate> gates;
+    // statistics
+    StageStats stats;
+    Formatter totals;              // format thread
+    LaneStats run;                 // total: write stage; everything else: main() before and after the stages
+    struct rusage ru0;
+
+    Pipeline(Opts &o_, const Knobs &k, const LaneInfo &l, const RunShape &s, time_t tb)
+        : o(o_), kn(k), lane(l), sh(s), t_begin(tb), refs(s.ND, nullptr), batches(s.NG, nullptr), ring(max(6, s.NG + 4)), gates(s.ND), stats(s.ev_on), totals(o_, rv)
+    {
+        memset(&run, 0, sizeof run);
+        run.workers = sh.workers;
+    }
+
+    // 4. under a quota: keep the whole process on as many CPUs of the GPU's NUMA node as the quota is worth (BSX_PIN=0: leave the mask alone)
     // (only when every GPU of the run hangs on the same node: pinned to one socket, the threads that drive and feed GPUs of the other
     //  socket would run cross-node)
-    if (!getenv("BSX_PIN") || atoi(getenv("BSX_PIN")) != 0) {
+    void pin_cpus()
+    {
+        if (!kn.pin) return;
         const int node0 = bsx_device_numa_node(o.devices[0]);
         bool one_node = true;
-        for (int d = 1; d < ND; d++) one_node = one_node && bsx_device_numa_node(o.devices[d]) == node0;
+        for (int d = 1; d < sh.ND; d++) one_node = one_node && bsx_device_numa_node(o.devices[d]) == node0;
         unsigned skip = 0;   // a lane: behind the CPU ranges of the earlier lanes whose GPUs hang on the same node
-        for (int k = 0; k < lane.index; k++) if (bsx_device_numa_node(lane.lane_devices[(size_t)k]) == node0) skip += ncpu;
-        const unsigned pinned = one_node ? bsx_pin_to_node(node0, ncpu, skip) : 0u;
-        if (getenv("BSX_TIMING")) {
+        for (int k = 0; k < lane.index; k++) if (bsx_device_numa_node(lane.lane_devices[(size_t)k]) == node0) skip += sh.ncpu;
+        const unsigned pinned = one_node ? bsx_pin_to_node(node0, sh.ncpu, skip) : 0u;
+        if (kn.timing) {
             if (pinned) cerr << "bsx: pinned to " << pinned << " CPUs of NUMA node " << node0 << endl;
             else if (!one_node) cerr << "bsx: GPUs on several NUMA nodes, CPU mask left alone" << endl;
         }
     }
-    // (measured on the 16-CPU quota of the GPU boxes with the GPU stage nearly free, tools/host_threads.sh: 10 workers 10.0 M reads/s, 12: 10.6,
-    //  14: 12.8 — the driver threads of the device batches sleep on events and the two parse threads are light)
-    const int workers = o.num_procs > 0 ? o.num_procs : (int)min(64u, max(1u, ncpu > 4 ? ncpu - 2 : ncpu));
-    thread t_pin([&] {
+
+    // 5. Locking gigabytes of pages takes seconds, so it happens on a side thread while the reference is loaded and indexed.
+    void pretouch_buffers()
+    {
+        const bsx_params &p = o.p;
+        const bool pe = sh.pe;
+        const int workers = sh.workers;
         bsx_thread_device(o.devices[0]);  // the page-locked ring belongs to a context: not implicitly device 0's
         auto fsize = [](const string &f) { struct stat st; return (!f.empty() && stat(f.c_str(), &st) == 0) ? (size_t)st.st_size : (size_t)0; };
         const size_t fa = fsize(o.a_file), fb = fsize(o.b_file);
         const size_t units = min<size_t>(o.batch, max(fa, fb) / 2 + 1);
         for (int k = 0; k < ring.NS; k++) {
             Slot &s = ring.slot[k];
-            s.A.set_alloc(&pinned); s.B.set_alloc(&pinned);
-            s.hits.set_alloc(&pinned); s.pairs.set_alloc(&pinned); s.cca.set_alloc(&pinned); s.ccb.set_alloc(&pinned);
+            s.A.set_alloc(&pinned_alloc); s.B.set_alloc(&pinned_alloc);
+            s.hits.set_alloc(&pinned_alloc); s.pairs.set_alloc(&pinned_alloc); s.cca.set_alloc(&pinned_alloc); s.ccb.set_alloc(&pinned_alloc);
             if ((size_t)k * o.batch * 100 > max(fa, fb)) continue;  // short input: the later slots are never used
             const size_t ca = min<size_t>(units * (size_t)p.max_readlen, fa), cb = min<size_t>(units * (size_t)p.max_readlen, fb);
             s.A.seq.reserve(ca); s.A.qual.reserve(ca); s.A.soff.reserve(units + 1); s.cca.reserve(units);
@@ -899,205 +1056,190 @@ int main(int argc, char **argv)
                 }
             }
         }
-    });
-    // One replica of reference + index per GPU (7.8 GB of 288 at hg38 size); the replicas load and index concurrently.
-    RefView rv;
-    vector<bsx_ref *> refs(ND, nullptr);
-    vector<double> t_loaded_d(ND, 0.0);
+    }
+
+    // 6. One replica of reference + index per GPU (7.8 GB of 288 at hg38 size); the replicas load and index concurrently, device 0's index is
+    // built here behind the lines its reference prints.  t0: when the process started
+    void load_replicas(double t0)
     {
+        const int ND = sh.ND;
         vector<int> rcs(ND, 0), rci(ND, 0);
         vector<thread> tl;
         for (int d = 1; d < ND; d++)
-            tl.emplace_back([&, d] {
+            tl.emplace_back([this, &rcs, &rci, d] {
                 rcs[d] = bsx_ref_create_from_file(&o.p, o.ref_file.c_str(), o.devices[d], &refs[d]);
                 if (!rcs[d]) rci[d] = bsx_index_build(refs[d]);
             });
         rcs[0] = bsx_ref_create_from_file(&o.p, o.ref_file.c_str(), o.devices[0], &refs[0]);
-        t_loaded_d[0] = now_s();
+        const double t_loaded = now_s();
         if (rcs[0]) die(rcs[0], "loading the reference");
         rv.ref = refs[0];
-        // (the replicas keep loading while device 0 goes on to print its lines and build its index below)
         for (thread &t : tl) t.join();
         for (int d = 1; d < ND; d++) { if (rcs[d]) die(rcs[d], "loading the reference"); if (rci[d]) die(rci[d], "building the seed index"); }
+        const uint32_t n_chr = bsx_ref_n_chr(rv.ref);
+        rv.anchor.resize(n_chr + 1); rv.chr_size.resize(n_chr); rv.rc_offset.resize(n_chr);
+        bsx_ref_info(rv.ref, rv.anchor.data(), rv.chr_size.data(), rv.rc_offset.data());
+        uint64_t sum_len = 0;
+        size_t longest_name = 0;
+        for (uint32_t c = 0; c < n_chr; c++) { rv.names.push_back(bsx_ref_chr_name(rv.ref, c)); sum_len += rv.chr_size[c]; longest_name = max(longest_name, rv.names.back().size()); }
+        g_rec_max = BSX_REC_FIXED + 4 * longest_name;
+        cout << "Load in " << n_chr << " db seqs, total size " << sum_len << " bp. " << time(NULL) - t_begin << " secs passed" << endl;
+        cout << "total_kmers: " << o.p.total_kmers << endl;
+        const int rc = bsx_index_build(rv.ref);
+        if (rc) die(rc, "building the seed index");
+        run.load_s = t_loaded - t0; run.index_s = now_s() - t_loaded;
+        cout << "Create seed table. " << time(NULL) - t_begin << " secs passed\n";
     }
-    const double t_loaded = t_loaded_d[0];
-    const uint32_t n_chr = bsx_ref_n_chr(rv.ref);
-    rv.anchor.resize(n_chr + 1); rv.chr_size.resize(n_chr); rv.rc_offset.resize(n_chr);
-    bsx_ref_info(rv.ref, rv.anchor.data(), rv.chr_size.data(), rv.rc_offset.data());
-    uint64_t sum_len = 0;
-    size_t longest_name = 0;
-    for (uint32_t c = 0; c < n_chr; c++) { rv.names.push_back(bsx_ref_chr_name(rv.ref, c)); sum_len += rv.chr_size[c]; longest_name = max(longest_name, rv.names.back().size()); }
-    g_rec_max = BSX_REC_FIXED + 4 * longest_name;
-    cout << "Load in " << n_chr << " db seqs, total size " << sum_len << " bp. " << time(NULL) - t_begin << " secs passed" << endl;
-    cout << "total_kmers: " << p.total_kmers << endl;
-    rc = bsx_index_build(rv.ref);
-    if (rc) die(rc, "building the seed index");
-    const double t_indexed = now_s();
-    cout << "Create seed table. " << time(NULL) - t_begin << " secs passed\n";
-    rv.refcat.resize(bsx_ref_n_words(rv.ref) + 64, 0);
-    bsx_ref_download_words(rv.ref, rv.refcat.data(), nullptr);
-    for (int i = 0; i < 4; i++) rv.useful_nt[p.bit_nt[i]] = "ACGT"[i];
-    rv.digest_len = (int)strlen(p.digest_site); rv.digest_pos = p.digest_pos;
-    if (p.rrbs) for (uint32_t c = 0; c < n_chr; c++) { vector<uint32_t> s(bsx_ref_n_sites(rv.ref, c)); if (!s.empty()) bsx_ref_sites(rv.ref, c, s.data()); rv.sites.push_back(s); }
 
-    cout << "max mismatches: " << p.max_snp_num << "\tmax multi-hits: " << p.max_num_hits << "\tmax Ns: " << p.max_ns << "\tseed size: " << p.seed_size
-         << "\tindex interval: " << p.index_interval << endl;
-    cout << "quality cutoff: " << p.qual_threshold << "\tbase quality char: '" << (char)p.zero_qual << "'" << endl;
-    cout << "min fragment size:" << p.min_insert << "\tmax fragemt size:" << p.max_insert << endl;
-    cout << "start from read #" << o.read_start << "\tend at read #" << o.read_end << endl;
-    cout << "additional alignment: " << (char)toupper(p.read_nt) << " in reads => " << (char)toupper(p.ref_nt) << " in reference" << endl;
-    if (o.a_file.empty()) { cerr << "missing query file(s)\n"; exit(1); }
-    // output files are written with pwrite at running offsets: the chunks of a batch go out in parallel
-    const bool bam_out = o.out_sam == 2;
-    bsx_bam::Sink bam;
-    int fout = ::open(o.out_file.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);   // (read access: a shared mapping of the file needs it)
-    if (fout < 0) fout = ::open(o.out_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    if (fout < 0) { cerr << "failed to open output file (check -o option): " << o.out_file << endl; exit(1); }
-    int fout_unpair = -1;
-    off_t off_out = 0, off_unpair = 0;
-    // Output on tmpfs (/dev/shm) goes through a shared mapping of the file instead of pwrite: buffered writes into ONE file hold the inode's
-    // lock, so 1 or 14 threads move the same 5-6 GB/s (tools/microbench/shm_write.cpp), while page faults on a mapping run in parallel
-    // (8 threads: 8 GB/s).  BSX_WRITE=pwrite|mmap overrides the choice.  A full file system then shows up as SIGBUS, reported like a write error.
-    auto use_map = [](int fd) {
-        if (const char *e = getenv("BSX_WRITE")) return strcmp(e, "mmap") == 0;
-        struct statfs sf;
-        return fstatfs(fd, &sf) == 0 && (unsigned long)sf.f_type == 0x01021994ul;  // TMPFS_MAGIC
-    };
-    const bool map_out = use_map(fout);
-    const int map_threads = getenv("BSX_WRITE_THREADS") ? max(1, atoi(getenv("BSX_WRITE_THREADS"))) : (int)max(1u, min(12u, ncpu));  // (4 / 8 / 14 threads: 18 / 21 / 22 M reads/s with the GPU stage nearly free; pwrite 16)
-    if (map_out) {
-        // the input files are memory-mapped too (bsx_reads.h): only a fault inside a range map_write has mapped is the output's
-        bsx_textout::install_sigbus_handler();
-    }
-    auto map_write = bsx_textout::map_write;
-    auto write_all = [](int fd, const char *p_, size_t n_, off_t at) {
-        while (n_) {
-            const ssize_t w = pwrite(fd, p_, n_, at);
-            if (w <= 0) { cerr << "write error on the output file\n"; fatal_exit(); }
-            p_ += w; n_ -= (size_t)w; at += w;
-        }
-    };
-    if (o.out_sam) {
-        Text h;
-        h.put("@HD\tVN:1.0\n");
-        for (uint32_t c = 0; c < n_chr; c++) { h.put("@SQ\tSN:"); h.put(rv.names[c]); h.put("\tLN:"); h.put_u(rv.chr_size[c]); h.put('\n'); }
-        h.put("@PG\tID:BSMAP_"); h.put(version); h.put('\n');
-        if (bam_out) bam.open(o.out_file, string(h.s.data(), h.s.size()), rv.names, rv.chr_size);
-        else if (lane.index <= 0 || o.lane_files) {   // (lanes behind the first: the joined file has one header)
-            write_all(fout, h.s.data(), h.s.size(), 0);
-            off_out = (off_t)h.s.size();
-        }
-    } else if (pe) {
-        fout_unpair = ::open(o.out_unpair.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fout_unpair < 0) { cerr << "failed to open output file for unpaired hits (check -2 option): " << o.out_unpair << endl; exit(1); }
-    }
-    const bool all_on = !o.all_hits.empty();
-    int fout_all = -1;
-    off_t off_all = 0;
-    if (all_on) {
-        fout_all = ::open(o.all_hits.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        if (fout_all < 0) { cerr << "failed to open the --all-hits file: " << o.all_hits << endl; exit(1); }
-        if (lane.index <= 0 || o.lane_files) { static const char hd[] = BSX_ALL_HITS_HEADER; write_all(fout_all, hd, sizeof hd - 1, 0); off_all = (off_t)(sizeof hd - 1); }
-    }
-    // GPU-stage thread g drives device batch g: batches k = g, g+NG, ... of the input; thread g works on GPU g % ND, so
-    // consecutive batches go to different GPUs (the reference's worker pool, main.cpp:74-84,116-131, with GPUs for threads)
-    vector<bsx_batch *> batches(NG, nullptr);
-    for (int g = 0; g < NG; g++) {
-        rc = bsx_batch_create(refs[g % ND], o.batch, pe ? 1 : 0, &batches[g]);
-        if (rc) die(rc, "creating the batch");
-        // nothing the command line prints depends on the work counters (the reference has none): the scan kernels skip the classification
-        // that only they need (include/bsx.h; BSX_WORK_COUNTERS=1 keeps them, for diagnostics)
-        if (!getenv("BSX_WORK_COUNTERS")) bsx_batch_set_work_counters(batches[g], 0);
-        if (all_on) {   // (BSX_ALL_HITS_POOL: starting pool in words — test hook for the grow-and-run-again path)
-            const uint64_t words = getenv("BSX_ALL_HITS_POOL") ? (uint64_t)max(1ll, atoll(getenv("BSX_ALL_HITS_POOL"))) : max<uint64_t>(16384, (uint64_t)o.batch * BSX_ALL_HITS_WORDS_X100 / 100);
-            if ((rc = bsx_batch_set_all_hits(batches[g], words))) die(rc, "attaching the all-hits pool");
-        }
-    }
-    ReadOpts ro;
-    ro.read_start = o.read_start; ro.read_end = o.read_end; ro.max_readlen = p.max_readlen; ro.zero_qual = p.zero_qual;
-    Reader ra, rb;
-    { ReadOpts roa = ro, rob = ro; roa.start_offset = lane.off_a; rob.start_offset = lane.off_b;   // a lane starts at the byte its first read begins at
-      ra.open(o.a_file, roa);
-      if (pe) rb.open(o.b_file, rob); }
+    // 7. what the formatters read of the reference: its words, the digestion sites
+    void fill_ref_view()
     {
-        string dl;
-        for (int d = 0; d < ND; d++) dl += (d ? "," : "") + to_string(o.devices[d]);
-        if (pe) cout << "Pair-end alignment(GPU " << dl << ")\n"; else cout << "Single read alignment(GPU " << dl << ")\n";
+        const bsx_params &p = o.p;
+        rv.refcat.resize(bsx_ref_n_words(rv.ref) + 64, 0);
+        bsx_ref_download_words(rv.ref, rv.refcat.data(), nullptr);
+        for (int i = 0; i < 4; i++) rv.useful_nt[p.bit_nt[i]] = "ACGT"[i];
+        rv.digest_len = (int)strlen(p.digest_site); rv.digest_pos = p.digest_pos;
+        if (p.rrbs) for (uint32_t c = 0; c < rv.names.size(); c++) { vector<uint32_t> s(bsx_ref_n_sites(rv.ref, c)); if (!s.empty()) bsx_ref_sites(rv.ref, c, s.data()); rv.sites.push_back(s); }
     }
-    Formatter totals(o, rv);
-    unsigned total = 0;
-    double busy[4] = {0, 0, 0, 0}, gpu_part[3] = {0, 0, 0};  // gpu_part: upload, align, read-back
-    // BSX_TIMING=2: when which batch was in which stage (0 parse, 1 upload, 2 align, 3 read-back, 4 format, 5 write)
-    struct Ev { long k; int stage; double t0, t1; };
-    vector<Ev> events;
-    mutex mu_ev;
-    const bool ev_on = getenv("BSX_TIMING") && atoi(getenv("BSX_TIMING")) >= 2;
-    auto log_ev = [&](long k, int stage, double a, double b) { if (ev_on) { lock_guard<mutex> lk(mu_ev); events.push_back({k, stage, a, b}); } };
-    std::atomic<long long> cpu_ns[4];  // CPU time of the stages' threads: parse, gpu drivers, format workers, write threads
-    for (auto &c : cpu_ns) c = 0;
-    auto add_cpu = [&](int st, double t0) { cpu_ns[st] += (long long)((thread_cpu_s() - t0) * 1e9); };
-    t_pin.join();
-    vector<unsigned char> lane_state;   // BSX_P1_EXACT in a lane: the planner state at the lane's first read (the parent's composition)
-    if (lane.index >= 0) {   // every lane is ready: the mapping phases start together (the index build / upload is not part of them)
-        const bool x1 = getenv("BSX_P1_EXACT") && atoi(getenv("BSX_P1_EXACT")) != 0;
-        if (!x1) {
-            char c = 'r';
-            ssize_t r = write(lane.ready_fd, &c, 1); ::close(lane.ready_fd);
-            r = read(lane.go_fd, &c, 1); (void)r; ::close(lane.go_fd);
-        } else {
-            // the effect of this lane's range on the planner state (see fork_lanes): the pre-pass alone over every batch of the range, from a state of marker words
-            vector<unsigned char> st(BSX_LEAK_STATE_BYTES, 0xFF);
-            {
-                Reader qa, qb;
-                ReadOpts roa = ro, rob = ro; roa.start_offset = lane.off_a; rob.start_offset = lane.off_b;
-                qa.open(o.a_file, roa);
-                if (pe) qb.open(o.b_file, rob);
-                ReadSet A, B;
-                bsx_batch *bt = batches[0];
-                bsx_batch_set_leak_exact(bt, 1);
-                for (;;) {
-                    size_t n2 = 0;
-                    thread tb;
-                    if (pe) tb = thread([&] { n2 = load_reads(qb, B, o.batch, ro, 2); });
-                    const size_t n1 = load_reads(qa, A, o.batch, ro, pe ? 1 : 0);
-                    if (pe) tb.join();
-                    const size_t n = pe ? min(n1, n2) : n1;
-                    if (n == 0) break;
-                    int r;
-                    if (!pe) r = bsx_batch_upload_se(bt, (uint32_t)n, A.seq.data(), A.soff.data(), qa.format != 1 ? A.upload_qual() : nullptr, A.first_index);
-                    else { const bool q = qa.format != 1 && qb.format != 1;
-                           r = bsx_batch_upload_pe(bt, (uint32_t)n, A.seq.data(), A.soff.data(), q ? A.upload_qual() : nullptr, B.seq.data(), B.soff.data(), q ? B.upload_qual() : nullptr, A.first_index); }
-                    if (!r) r = bsx_batch_set_leak_state(bt, st.data(), st.size());
-                    if (!r) r = bsx_batch_get_leak_state(bt, st.data(), st.size());
-                    if (r) die(r, "sweeping the lane's range for its planner-state effect");
-                    if (n < o.batch) break;
-                }
-                (void)bsx_batch_set_leak_state(bt, nullptr, 0);
+
+    // 8.
+    void print_parameters()
+    {
+        const bsx_params &p = o.p;
+        cout << "max mismatches: " << p.max_snp_num << "\tmax multi-hits: " << p.max_num_hits << "\tmax Ns: " << p.max_ns << "\tseed size: " << p.seed_size
+             << "\tindex interval: " << p.index_interval << endl;
+        cout << "quality cutoff: " << p.qual_threshold << "\tbase quality char: '" << (char)p.zero_qual << "'" << endl;
+        cout << "min fragment size:" << p.min_insert << "\tmax fragemt size:" << p.max_insert << endl;
+        cout << "start from read #" << o.read_start << "\tend at read #" << o.read_end << endl;
+        cout << "additional alignment: " << (char)toupper(p.read_nt) << " in reads => " << (char)toupper(p.ref_nt) << " in reference" << endl;
+        if (o.a_file.empty()) { cerr << "missing query file(s)\n"; exit(1); }
+    }
+
+    // 9. output files are written with pwrite at running offsets: the chunks of a batch go out in parallel
+    void open_outputs()
+    {
+        out.fout = ::open(o.out_file.c_str(), O_RDWR | O_CREAT | O_TRUNC, 0644);   // (read access: a shared mapping of the file needs it)
+        if (out.fout < 0) out.fout = ::open(o.out_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (out.fout < 0) { cerr << "failed to open output file (check -o option): " << o.out_file << endl; exit(1); }
+        sh.map_out = use_map(out.fout, kn);
+        if (sh.map_out) {
+            // the input files are memory-mapped too (bsx_reads.h): only a fault inside a range map_write has mapped is the output's
+            bsx_textout::install_sigbus_handler();
+        }
+        const bool first_file = lane.index <= 0 || o.lane_files;   // (lanes behind the first: the joined file has one header)
+        if (o.out_sam) {
+            Text h;
+            h.put("@HD\tVN:1.0\n");
+            for (size_t c = 0; c < rv.names.size(); c++) { h.put("@SQ\tSN:"); h.put(rv.names[c]); h.put("\tLN:"); h.put_u(rv.chr_size[c]); h.put('\n'); }
+            h.put("@PG\tID:BSMAP_"); h.put(version); h.put('\n');
+            if (sh.bam_out) out.bam.open(o.out_file, string(h.s.data(), h.s.size()), rv.names, rv.chr_size);
+            else if (first_file) {
+                write_all(out.fout, h.s.data(), h.s.size(), 0);
+                out.off_out = (off_t)h.s.size();
             }
-            vector<unsigned char> msg(1 + BSX_LEAK_STATE_BYTES);
-            msg[0] = (unsigned char)lane.index; memcpy(msg.data() + 1, st.data(), BSX_LEAK_STATE_BYTES);
-            ssize_t r = write(lane.ready_fd, msg.data(), msg.size()); ::close(lane.ready_fd);
-            lane_state.assign(BSX_LEAK_STATE_BYTES, 0);
-            size_t got = 0;
-            while (got < lane_state.size()) { r = read(lane.state_fd, lane_state.data() + got, lane_state.size() - got); if (r <= 0) break; got += (size_t)r; }
-            ::close(lane.state_fd);
-            if (got != lane_state.size()) { cerr << "bsx: lane " << lane.index << ": no planner state from the parent\n"; fatal_exit(); }
-            char c; r = read(lane.go_fd, &c, 1); (void)r; ::close(lane.go_fd);
+        } else if (sh.pe) {
+            out.fout_unpair = ::open(o.out_unpair.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (out.fout_unpair < 0) { cerr << "failed to open output file for unpaired hits (check -2 option): " << o.out_unpair << endl; exit(1); }
+        }
+        if (sh.all_on) {
+            out.fout_all = ::open(o.all_hits.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (out.fout_all < 0) { cerr << "failed to open the --all-hits file: " << o.all_hits << endl; exit(1); }
+            if (first_file) { static const char hd[] = BSX_ALL_HITS_HEADER; write_all(out.fout_all, hd, sizeof hd - 1, 0); out.off_all = (off_t)(sizeof hd - 1); }
         }
     }
-    const double t_map0 = now_s();
-    struct rusage ru0; getrusage(RUSAGE_SELF, &ru0);
 
-    // BSX_P1_EXACT=1: reproduce the single-threaded reference also for the reads whose planner state leaks from earlier
-    // reads (bsx_batch_set_leak_exact, DESIGN.md §4).  The state is handed from batch to batch as a value: batch k starts from the state
-    // behind the last read of batch k-1 (bsx_batch_get_leak_state -> set), whichever device batch or GPU ran that one — it depends on the
-    // reads only, so it is computed right after the upload and the alignment of consecutive batches still overlaps.
-    const bool p1_exact = getenv("BSX_P1_EXACT") && atoi(getenv("BSX_P1_EXACT")) != 0;
-    if (p1_exact) for (int g = 0; g < NG; g++) bsx_batch_set_leak_exact(batches[g], 1);
-    struct LeakChain { mutex mu; condition_variable cv; long have = -1; vector<unsigned char> state; } chain;  // state behind batch `have`
-    chain.state.assign(BSX_LEAK_STATE_BYTES, 0);
-    if (!lane_state.empty()) chain.state = lane_state;   // (a lane: not a fresh object, the state the reads before its range leave)
-    thread t_parse([&] {
+    // 10. GPU-stage thread g drives device batch g: batches k = g, g+NG, ... of the input; thread g works on GPU g % ND, so
+    // consecutive batches go to different GPUs (the reference's worker pool, main.cpp:74-84,116-131, with GPUs for threads)
+    void create_batches()
+    {
+        for (int g = 0; g < sh.NG; g++) {
+            int rc = bsx_batch_create(refs[g % sh.ND], o.batch, sh.pe ? 1 : 0, &batches[g]);
+            if (rc) die(rc, "creating the batch");
+            // nothing the command line prints depends on the work counters (the reference has none): the scan kernels skip the classification
+            // that only they need (include/bsx.h; BSX_WORK_COUNTERS=1 keeps them, for diagnostics)
+            if (!kn.work_counters) bsx_batch_set_work_counters(batches[g], 0);
+            if (sh.all_on) {   // (BSX_ALL_HITS_POOL: starting pool in words — test hook for the grow-and-run-again path)
+                const uint64_t words = kn.all_hits_pool ? (uint64_t)kn.all_hits_pool : max<uint64_t>(16384, (uint64_t)o.batch * BSX_ALL_HITS_WORDS_X100 / 100);
+                if ((rc = bsx_batch_set_all_hits(batches[g], words))) die(rc, "attaching the all-hits pool");
+            }
+        }
+        ro.read_start = o.read_start; ro.read_end = o.read_end; ro.max_readlen = o.p.max_readlen; ro.zero_qual = o.p.zero_qual;
+        open_readers(ra, rb);
+        string dl;
+        for (int d = 0; d < sh.ND; d++) dl += (d ? "," : "") + to_string(o.devices[d]);
+        if (sh.pe) cout << "Pair-end alignment(GPU " << dl << ")\n"; else cout << "Single read alignment(GPU " << dl << ")\n";
+    }
+    void open_readers(Reader &a, Reader &b)
+    {
+        ReadOpts roa = ro, rob = ro;
+        roa.start_offset = lane.off_a; rob.start_offset = lane.off_b;   // a lane starts at the byte its first read begins at
+        a.open(o.a_file, roa);
+        if (sh.pe) b.open(o.b_file, rob);
+    }
+
+    // the reads of a batch go up: n single reads of A, or n pairs of A and B (qualities only where the files have them)
+    int upload(bsx_batch *bt, ReadSet &A, ReadSet &B, uint32_t n)
+    {
+        if (!sh.pe) return bsx_batch_upload_se(bt, n, A.seq.data(), A.soff.data(), ra.format != 1 ? A.upload_qual() : nullptr, A.first_index);
+        const bool q = ra.format != 1 && rb.format != 1;
+        return bsx_batch_upload_pe(bt, n, A.seq.data(), A.soff.data(), q ? A.upload_qual() : nullptr, B.seq.data(), B.soff.data(), q ? B.upload_qual() : nullptr, A.first_index);
+    }
+
+    // BSX_P1_EXACT in a lane: the effect of this lane's range on the planner state (see compose_lane_states): the pre-pass alone over every batch of the range,
+    // from a state of marker words
+    vector<unsigned char> sweep_lane_effect()
+    {
+        vector<unsigned char> st(BSX_LEAK_STATE_BYTES, 0xFF);
+        const bool pe = sh.pe;
+        Reader qa, qb;
+        open_readers(qa, qb);
+        ReadSet A, B;
+        bsx_batch *bt = batches[0];
+        bsx_batch_set_leak_exact(bt, 1);
+        for (;;) {
+            size_t n2 = 0;
+            thread tb;
+            if (pe) tb = thread([&] { n2 = load_reads(qb, B, o.batch, ro, 2); });
+            const size_t n1 = load_reads(qa, A, o.batch, ro, pe ? 1 : 0);
+            if (pe) tb.join();
+            const size_t n = pe ? min(n1, n2) : n1;
+            if (n == 0) break;
+            int r = upload(bt, A, B, (uint32_t)n);
+            if (!r) r = bsx_batch_set_leak_state(bt, st.data(), st.size());
+            if (!r) r = bsx_batch_get_leak_state(bt, st.data(), st.size());
+            if (r) die(r, "sweeping the lane's range for its planner-state effect");
+            if (n < o.batch) break;
+        }
+        (void)bsx_batch_set_leak_state(bt, nullptr, 0);
+        return st;
+    }
+
+    // 11. a lane: every lane is ready, the mapping phases start together (the index build / upload is not part of them).  Exact mode: the lane sends its
+    // range's effect and starts from the state the parent composes — not a fresh object's, the one the reads before its range leave
+    void lane_rendezvous()
+    {
+        chain.value.assign(BSX_LEAK_STATE_BYTES, 0);
+        if (lane.index < 0) return;
+        char c = 'r';
+        ssize_t r;
+        if (!sh.p1_exact) { r = write(lane.ready_fd, &c, 1); ::close(lane.ready_fd); }
+        else {
+            vector<unsigned char> msg(1 + BSX_LEAK_STATE_BYTES);
+            const vector<unsigned char> st = sweep_lane_effect();
+            msg[0] = (unsigned char)lane.index; memcpy(msg.data() + 1, st.data(), BSX_LEAK_STATE_BYTES);
+            r = write(lane.ready_fd, msg.data(), msg.size()); ::close(lane.ready_fd);
+            size_t got = 0;
+            while (got < chain.value.size()) { r = read(lane.state_fd, chain.value.data() + got, chain.value.size() - got); if (r <= 0) break; got += (size_t)r; }
+            ::close(lane.state_fd);
+            if (got != chain.value.size()) { cerr << "bsx: lane " << lane.index << ": no planner state from the parent\n"; fatal_exit(); }
+        }
+        r = read(lane.go_fd, &c, 1); (void)r; ::close(lane.go_fd);
+    }
+
+    // ---- the stages ----
+    void parse_stage()
+    {
+        const bool pe = sh.pe;
         long k = 0;
         for (;; k++) {
             ring.acquire(k, 0);
@@ -1105,13 +1247,13 @@ int main(int argc, char **argv)
             Slot &s = ring.at(k);
             size_t n2 = 0;
             thread tb;
-            if (pe) tb = thread([&] { const double c0 = thread_cpu_s(); n2 = load_reads(rb, s.B, o.batch, ro, 2); add_cpu(0, c0); });
+            if (pe) tb = thread([this, &s, &n2] { const double c0 = thread_cpu_s(); n2 = load_reads(rb, s.B, o.batch, ro, 2); stats.add_cpu(0, c0); });
             const double c0 = thread_cpu_s();
             const size_t n1 = load_reads(ra, s.A, o.batch, ro, pe ? 1 : 0);
-            add_cpu(0, c0);
+            stats.add_cpu(0, c0);
             if (pe) tb.join();
-            busy[0] += now_s() - t;
-            log_ev(k, 0, t, now_s());
+            stats.busy[0] += now_s() - t;
+            stats.log_ev(k, 0, t, now_s());
             if (!n1) break;
             s.n = n1;
             s.total_after = ra.index - o.read_start + 1;
@@ -1130,32 +1272,24 @@ int main(int argc, char **argv)
             ring.release(k, 1);
         }
         ring.finish(k);
-    });
-    mutex mu_busy;
-    auto chain_state = [&](bsx_batch *batch, long k) {   // exact mode, after the upload of batch k
-        vector<unsigned char> st(BSX_LEAK_STATE_BYTES);
-        { unique_lock<mutex> lk(chain.mu); chain.cv.wait(lk, [&] { return chain.have == k - 1; }); st = chain.state; }
+    }
+
+    // BSX_P1_EXACT=1: reproduce the single-threaded reference also for the reads whose planner state leaks from earlier
+    // reads (bsx_batch_set_leak_exact, DESIGN.md §4).  The state is handed from batch to batch as a value: batch k starts from the state
+    // behind the last read of batch k-1 (bsx_batch_get_leak_state -> set), whichever device batch or GPU ran that one — it depends on the
+    // reads only, so it is computed right after the upload and the alignment of consecutive batches still overlaps.
+    void chain_state(bsx_batch *batch, long k)
+    {
+        vector<unsigned char> st = chain.take(k);
         int r = bsx_batch_set_leak_state(batch, st.data(), st.size());
         if (!r) r = bsx_batch_get_leak_state(batch, st.data(), st.size());
         if (r) die(r, "chaining the planner state");
-        { lock_guard<mutex> lk(chain.mu); chain.state = st; chain.have = k; }
-        chain.cv.notify_all();
-    };
-    // compute slots per GPU, granted in batch order (a later batch never overtakes an earlier one: results are consumed in input order)
-    struct Gate { mutex mu; condition_variable cv; int free_slots; long next; };
-    vector<Gate> gates(ND);
-    for (int d = 0; d < ND; d++) { gates[d].free_slots = NC; gates[d].next = d; }   // GPU d runs the batches k with (k % NG) % ND == d ...
-    auto run_gated = [&](int g, long k, bsx_batch *batch) {
-        Gate &G = gates[g % ND];
-        if (NC < NB) { unique_lock<mutex> lk(G.mu); G.cv.wait(lk, [&] { return G.free_slots > 0 && G.next == k; }); G.free_slots--; G.next = k + ND; lk.unlock(); G.cv.notify_all(); }
-        int r = bsx_batch_run(batch);
-        if (!r) r = bsx_batch_sync(batch);
-        if (NC < NB) { { lock_guard<mutex> lk(G.mu); G.free_slots++; } G.cv.notify_all(); }
-        return r;
-    };
+        chain.put(k, std::move(st));
+    }
     // --all-hits: spans and pool words of the batch just run; a batch whose lists did not fit is run again with the pool it asked for
     // (results are a function of the reads — and of the planner state the batch already holds in exact mode —, so that run drops nothing)
-    auto fetch_all_hits = [&](bsx_batch *batch, long k, Slot &s) {
+    void fetch_all_hits(bsx_batch *batch, long k, Slot &s)
+    {
         uint64_t need = 0, used = 0;
         uint32_t dropped = 0;
         int r = bsx_batch_all_hits_need(batch, &need, &dropped);
@@ -1173,198 +1307,232 @@ int main(int argc, char **argv)
         s.ah_words.resize((size_t)used);
         if (!r && used) r = bsx_batch_all_hits_fetch(batch, s.ah_words.data(), used, nullptr);
         if (r) die(r, "reading the all-hits lists");
-    };
-    auto gpu_stage = [&](int g) {
+    }
+    // upload -> chain state (exact mode) -> gated run + sync -> results -> all-hits fetch -> release
+    void gpu_stage(int g)
+    {
         bsx_batch *batch = batches[g];
-        for (long k = g; ring.acquire(k, 1); k += NG) {
+        bsx_ring::Gate &gate = gates[g % sh.ND];
+        for (long k = g; ring.acquire(k, 1); k += sh.NG) {
             const double t = now_s(), c0 = thread_cpu_s();
-            double t1 = t, t2 = t;
             Slot &s = ring.at(k);
             const uint32_t n = (uint32_t)s.n;
-            int r;
-            if (!pe) {
-                r = bsx_batch_upload_se(batch, n, s.A.seq.data(), s.A.soff.data(), ra.format != 1 ? s.A.upload_qual() : nullptr, s.A.first_index);
-                if (r) die(r, "uploading reads");
-                if (p1_exact) chain_state(batch, k);
-                t1 = now_s();
-                if ((r = run_gated(g, k, batch))) die(r, "aligning");
-                t2 = now_s();
-                s.hits.resize(n); s.cca.resize(n);
-                if ((r = bsx_batch_results_se(batch, s.hits.data(), s.cca.data()))) die(r, "reading results");
-            } else {
-                const bool q = ra.format != 1 && rb.format != 1;
-                r = bsx_batch_upload_pe(batch, n, s.A.seq.data(), s.A.soff.data(), q ? s.A.upload_qual() : nullptr, s.B.seq.data(), s.B.soff.data(),
-                                        q ? s.B.upload_qual() : nullptr, s.A.first_index);
-                if (r) die(r, "uploading reads");
-                if (p1_exact) chain_state(batch, k);
-                t1 = now_s();
-                if ((r = run_gated(g, k, batch))) die(r, "aligning");
-                t2 = now_s();
-                s.pairs.resize(n); s.cca.resize(n); s.ccb.resize(n);
-                if ((r = bsx_batch_results_pe(batch, s.pairs.data(), s.cca.data(), s.ccb.data(), nullptr))) die(r, "reading results");
-            }
-            if (all_on) fetch_all_hits(batch, k, s);
-            add_cpu(1, c0);
-            { const double t3 = now_s(); lock_guard<mutex> lk(mu_busy); busy[1] += t3 - t; gpu_part[0] += t1 - t; gpu_part[1] += t2 - t1; gpu_part[2] += t3 - t2;
-              log_ev(k, 1, t, t1); log_ev(k, 2, t1, t2); log_ev(k, 3, t2, t3); }
+            int r = upload(batch, s.A, s.B, n);
+            if (r) die(r, "uploading reads");
+            if (sh.p1_exact) chain_state(batch, k);
+            const double t1 = now_s();
+            gate.enter(k);
+            r = bsx_batch_run(batch);
+            if (!r) r = bsx_batch_sync(batch);
+            gate.leave();
+            if (r) die(r, "aligning");
+            const double t2 = now_s();
+            if (!sh.pe) { s.hits.resize(n); s.cca.resize(n); r = bsx_batch_results_se(batch, s.hits.data(), s.cca.data()); }
+            else { s.pairs.resize(n); s.cca.resize(n); s.ccb.resize(n); r = bsx_batch_results_pe(batch, s.pairs.data(), s.cca.data(), s.ccb.data(), nullptr); }
+            if (r) die(r, "reading results");
+            if (sh.all_on) fetch_all_hits(batch, k, s);
+            stats.add_cpu(1, c0);
+            stats.add_gpu(k, t, t1, t2, now_s());
             ring.release(k, 2);
         }
-    };
-    vector<thread> t_gpu;
-    for (int g = 0; g < NG; g++) t_gpu.emplace_back(gpu_stage, g);
-    thread t_format([&] {
+    }
+
+    // worker w of W formats its share of the slot's units
+    void format_range(Slot &s, int w, int W, Formatter &fmt)
+    {
+        const bool pe = sh.pe, all_on = sh.all_on;
+        const bsx_params &p = o.p;
+        const double c0 = thread_cpu_s();
+        const size_t lo = s.n * w / W, hi = s.n * (w + 1) / W;
+        Text &os = s.out[w], &os_unpair = s.out_unpair[w];
+        os.s.reserve((hi - lo) * (pe ? 900 : 450));
+        Rd a, b;
+        for (size_t i = lo; i < hi; i++) {
+            os.need(g_rec_max); os_unpair.need(g_rec_max);
+            a.load(s.A, i);
+            const bsx_span *sp = all_on ? &s.spans[i * 3] : nullptr;
+            if (!pe) {
+                const bsx_hit &h = s.hits[i];
+                apply_trim(a, h, o);
+                if (sp && sp[0].n) fmt.all_hits_read(a.name, a.nlen, 0, s.ah_words.data() + sp[0].off, sp[0].n, sp[0].n_fwd, h.best_class, s.out_all[w]);
+                if (h.flags & BSX_F_FILTERED) { if (p.report_repeat_hits) fmt.out_hit(a, 0, 0, -1, 0, 0, 0, 0, 0, nullptr, os); }
+                else fmt.out_hit(a, 0, (h.flags & BSX_F_CHAIN) ? 1 : 0, h.n_best, h.best_class < 0 ? h.max_snp + 1 : h.best_class, h.chr, h.loc, 0, h.max_snp, &s.cca[i], os);
+            } else {
+                b.load(s.B, i);
+                const bsx_pair &pp = s.pairs[i];
+                apply_trim(a, pp.a, o); apply_trim(b, pp.b, o);
+                if (o.out_sam) fix_pair_name(a, b);
+                if (sp) {   // (before the formatters below cut the mates of a read-through pair: the lists are cut with the lengths the reads have here)
+                    if (sp[0].n) fmt.all_hits_read(a.name, a.nlen, 1, s.ah_words.data() + sp[0].off, sp[0].n, sp[0].n_fwd, pp.a.best_class, s.out_all[w]);
+                    if (sp[1].n) fmt.all_hits_read(b.name, b.nlen, 2, s.ah_words.data() + sp[1].off, sp[1].n, sp[1].n_fwd, pp.b.best_class, s.out_all[w]);
+                    if (sp[2].n) fmt.all_hits_pairs(a.name, a.nlen, s.ah_words.data() + sp[2].off, sp[2].n, a.slen, b.slen, s.out_all[w]);
+                }
+                if (!pp.unpaired_out) fmt.out_pair(a, b, pp, &s.cca[i], &s.ccb[i], os);
+                else {
+                    Text &dst = o.out_sam ? os : os_unpair;
+                    fmt.out_unpair(a, 0, pp.a, pp.b, &s.cca[i], dst);
+                    fmt.out_unpair(b, 1, pp.b, pp.a, &s.ccb[i], dst);
+                }
+            }
+        }
+        stats.add_cpu(2, c0);
+    }
+    void format_stage()
+    {
         for (long k = 0; ring.acquire(k, 2); k++) {
             const double t = now_s();
             Slot &s = ring.at(k);
-            const int W = (int)min<size_t>((size_t)workers, max<size_t>(1, s.n / 1024));
+            const int W = (int)min<size_t>((size_t)sh.workers, max<size_t>(1, s.n / 1024));
             // the slot's text buffers keep their capacity from batch to batch (a fresh 0.7 GB per batch would be page-faulted in again)
             if ((int)s.out.size() != W) { s.out.clear(); s.out_unpair.clear(); s.out.resize(W); s.out_unpair.resize(W); }
             else for (int w = 0; w < W; w++) { s.out[w].s.clear(); s.out_unpair[w].s.clear(); }
-            if (all_on) { if ((int)s.out_all.size() != W) { s.out_all.clear(); s.out_all.resize(W); } else for (Text &x : s.out_all) x.s.clear(); }
+            if (sh.all_on) { if ((int)s.out_all.size() != W) { s.out_all.clear(); s.out_all.resize(W); } else for (Text &x : s.out_all) x.s.clear(); }
             vector<Formatter> fm(W, Formatter(o, rv));
-            auto work = [&](int w) {
-                const double c0 = thread_cpu_s();
-                const size_t lo = s.n * w / W, hi = s.n * (w + 1) / W;
-                Text &os = s.out[w], &os_unpair = s.out_unpair[w];
-                os.s.reserve((hi - lo) * (pe ? 900 : 450));
-                Formatter &fmt = fm[w];
-                Rd a, b;
-                for (size_t i = lo; i < hi; i++) {
-                    os.need(g_rec_max); os_unpair.need(g_rec_max);
-                    a.load(s.A, i);
-                    const bsx_span *sp = all_on ? &s.spans[i * 3] : nullptr;
-                    if (!pe) {
-                        const bsx_hit &h = s.hits[i];
-                        apply_trim(a, h, o);
-                        if (sp && sp[0].n) fmt.all_hits_read(a.name, a.nlen, 0, s.ah_words.data() + sp[0].off, sp[0].n, sp[0].n_fwd, h.best_class, s.out_all[w]);
-                        if (h.flags & BSX_F_FILTERED) { if (p.report_repeat_hits) fmt.out_hit(a, 0, 0, -1, 0, 0, 0, 0, 0, nullptr, os); }
-                        else fmt.out_hit(a, 0, (h.flags & BSX_F_CHAIN) ? 1 : 0, h.n_best, h.best_class < 0 ? h.max_snp + 1 : h.best_class, h.chr, h.loc, 0, h.max_snp, &s.cca[i], os);
-                    } else {
-                        b.load(s.B, i);
-                        const bsx_pair &pp = s.pairs[i];
-                        apply_trim(a, pp.a, o); apply_trim(b, pp.b, o);
-                        if (o.out_sam) fix_pair_name(a, b);
-                        if (sp) {   // (before the formatters below cut the mates of a read-through pair: the lists are cut with the lengths the reads have here)
-                            if (sp[0].n) fmt.all_hits_read(a.name, a.nlen, 1, s.ah_words.data() + sp[0].off, sp[0].n, sp[0].n_fwd, pp.a.best_class, s.out_all[w]);
-                            if (sp[1].n) fmt.all_hits_read(b.name, b.nlen, 2, s.ah_words.data() + sp[1].off, sp[1].n, sp[1].n_fwd, pp.b.best_class, s.out_all[w]);
-                            if (sp[2].n) fmt.all_hits_pairs(a.name, a.nlen, s.ah_words.data() + sp[2].off, sp[2].n, a.slen, b.slen, s.out_all[w]);
-                        }
-                        if (!pp.unpaired_out) fmt.out_pair(a, b, pp, &s.cca[i], &s.ccb[i], os);
-                        else {
-                            Text &dst = o.out_sam ? os : os_unpair;
-                            fmt.out_unpair(a, 0, pp.a, pp.b, &s.cca[i], dst);
-                            fmt.out_unpair(b, 1, pp.b, pp.a, &s.ccb[i], dst);
-                        }
-                    }
-                }
-                add_cpu(2, c0);
-            };
             vector<thread> th;
-            for (int w = 1; w < W; w++) th.emplace_back(work, w);
-            work(0);
+            for (int w = 1; w < W; w++) th.emplace_back([this, &s, &fm, w, W] { format_range(s, w, W, fm[w]); });
+            format_range(s, 0, W, fm[0]);
             for (thread &x : th) x.join();
             for (const Formatter &f : fm) { totals.n_aligned += f.n_aligned; totals.n_aligned_pairs += f.n_aligned_pairs; totals.n_aligned_a += f.n_aligned_a; totals.n_aligned_b += f.n_aligned_b; }
-            busy[2] += now_s() - t;
-            log_ev(k, 4, t, now_s());
+            stats.busy[2] += now_s() - t;
+            stats.log_ev(k, 4, t, now_s());
             ring.release(k, 3);
         }
-    });
-    for (long k = 0; ring.acquire(k, 3); k++) {  // write stage on the main thread
-        const double t = now_s();
-        Slot &s = ring.at(k);
-        if (bam_out) {
-            for (const Text &x : s.out) bam.add_text(x.s.data(), x.s.size());  // records are sorted and written at the end
-        } else {
-            vector<thread> wt;
-            bool mapped = false;
-            if (map_out) {
-                vector<pair<const char *, size_t>> pieces;
-                size_t tot = 0;
-                for (const Text &x : s.out) if (!x.s.empty()) { pieces.emplace_back(x.s.data(), x.s.size()); tot += x.s.size(); }
-                const double c0 = thread_cpu_s();
-                mapped = map_write(fout, pieces, off_out, map_threads);
-                add_cpu(3, c0);   // (the helper threads' CPU time is not in this figure)
-                if (mapped) off_out += (off_t)tot;
-            }
-            if (!mapped) for (const Text &x : s.out) {
-                if (x.s.empty()) continue;
-                const off_t at = off_out;
-                off_out += (off_t)x.s.size();
-                wt.emplace_back([&write_all, &add_cpu, &x, at, fout] { const double c0 = thread_cpu_s(); write_all(fout, x.s.data(), x.s.size(), at); add_cpu(3, c0); });
-            }
-            if (fout_unpair >= 0)
-                for (const Text &x : s.out_unpair) {
-                    if (x.s.empty()) continue;
-                    const off_t at = off_unpair;
-                    off_unpair += (off_t)x.s.size();
-                    wt.emplace_back([&write_all, &add_cpu, &x, at, fout_unpair] { const double c0 = thread_cpu_s(); write_all(fout_unpair, x.s.data(), x.s.size(), at); add_cpu(3, c0); });
-                }
-            for (thread &t : wt) t.join();
+    }
+
+    // the non-empty texts of a batch go to fd behind `off`, each by a writer thread of its own at its own offset
+    void write_pieces(int fd, const vector<Text> &texts, off_t &off, vector<thread> &wt)
+    {
+        for (const Text &x : texts) {
+            if (x.s.empty()) continue;
+            const off_t at = off;
+            off += (off_t)x.s.size();
+            wt.emplace_back([this, &x, at, fd] { const double c0 = thread_cpu_s(); write_all(fd, x.s.data(), x.s.size(), at); stats.add_cpu(3, c0); });
         }
-        if (all_on) for (const Text &x : s.out_all) { if (x.s.empty()) continue; write_all(fout_all, x.s.data(), x.s.size(), off_all); off_all += (off_t)x.s.size(); }
-        total = s.total_after;
-        busy[3] += now_s() - t;
-        log_ev(k, 5, t, now_s());
-        cout << total << " reads finished. " << time(NULL) - t_begin << " secs passed" << endl;
-        ring.release(k, 0);
     }
-    t_parse.join();
-    for (thread &t : t_gpu) t.join();
-    t_format.join();
-    ::close(fout);
-    if (fout_unpair >= 0) ::close(fout_unpair);
-    if (fout_all >= 0) ::close(fout_all);
-    if (bam_out) {
-        cout << "Converting SAM to BAM ...\nSorting BAM ...\nIndexing BAM ...\n";  // sam2bam.sh's progress lines
-        bam.finish();
+    void write_stage()   // on the main thread
+    {
+        for (long k = 0; ring.acquire(k, 3); k++) {
+            const double t = now_s();
+            Slot &s = ring.at(k);
+            if (sh.bam_out) {
+                for (const Text &x : s.out) out.bam.add_text(x.s.data(), x.s.size());  // records are sorted and written at the end
+            } else {
+                vector<thread> wt;
+                bool mapped = false;
+                if (sh.map_out) {
+                    vector<pair<const char *, size_t>> pieces;
+                    size_t tot = 0;
+                    for (const Text &x : s.out) if (!x.s.empty()) { pieces.emplace_back(x.s.data(), x.s.size()); tot += x.s.size(); }
+                    const double c0 = thread_cpu_s();
+                    mapped = bsx_textout::map_write(out.fout, pieces, out.off_out, sh.map_threads);
+                    stats.add_cpu(3, c0);   // (the helper threads' CPU time is not in this figure)
+                    if (mapped) out.off_out += (off_t)tot;
+                }
+                if (!mapped) write_pieces(out.fout, s.out, out.off_out, wt);
+                if (out.fout_unpair >= 0) write_pieces(out.fout_unpair, s.out_unpair, out.off_unpair, wt);
+                for (thread &t : wt) t.join();
+            }
+            if (sh.all_on) for (const Text &x : s.out_all) { if (x.s.empty()) continue; write_all(out.fout_all, x.s.data(), x.s.size(), out.off_all); out.off_all += (off_t)x.s.size(); }
+            run.total = s.total_after;
+            stats.busy[3] += now_s() - t;
+            stats.log_ev(k, 5, t, now_s());
+            cout << run.total << " reads finished. " << time(NULL) - t_begin << " secs passed" << endl;
+            ring.release(k, 0);
+        }
     }
-    const double t_map1 = now_s();
-    struct rusage ru1; getrusage(RUSAGE_SELF, &ru1);
-    const double ru_user = (ru1.ru_utime.tv_sec - ru0.ru_utime.tv_sec) + 1e-6 * (ru1.ru_utime.tv_usec - ru0.ru_utime.tv_usec),
-                 ru_sys = (ru1.ru_stime.tv_sec - ru0.ru_stime.tv_sec) + 1e-6 * (ru1.ru_stime.tv_usec - ru0.ru_stime.tv_usec);
-    const Formatter &fmt = totals;
-    if (lane.index >= 0) {   // a lane reports to the parent, which prints the run's summary
-        LaneStats st; memset(&st, 0, sizeof st);
-        st.total = total; st.n_aligned = fmt.n_aligned; st.n_pairs = fmt.n_aligned_pairs; st.n_a = fmt.n_aligned_a; st.n_b = fmt.n_aligned_b;
-        st.load_s = t_loaded - t0; st.index_s = t_indexed - t_loaded; st.mapping_s = t_map1 - t_map0; st.t_map0 = t_map0; st.t_map1 = t_map1; st.cpu_user = ru_user; st.cpu_sys = ru_sys; st.workers = workers;
-        for (int k = 0; k < 4; k++) { st.stage_cpu[k] = cpu_ns[k] * 1e-9; st.busy[k] = busy[k]; }
-        for (int k = 0; k < 3; k++) st.gpu_part[k] = gpu_part[k];
-        for (int g = 0; g < NG; g++) bsx_batch_destroy(batches[g]);
+
+    // 12. one parse thread, NG GPU threads, one format thread; the write stage on this thread
+    void run_stages()
+    {
+        run.t_map0 = now_s();
+        getrusage(RUSAGE_SELF, &ru0);
+        if (sh.p1_exact) for (bsx_batch *b : batches) bsx_batch_set_leak_exact(b, 1);
+        for (int d = 0; d < sh.ND; d++) gates[d].init(sh.NC, sh.NB, d, sh.ND);   // GPU d runs the batches k with (k % NG) % ND == d ...
+        thread t_parse([this] { parse_stage(); });
+        vector<thread> t_gpu;
+        for (int g = 0; g < sh.NG; g++) t_gpu.emplace_back([this, g] { gpu_stage(g); });
+        thread t_format([this] { format_stage(); });
+        write_stage();
+        t_parse.join();
+        for (thread &t : t_gpu) t.join();
+        t_format.join();
+    }
+
+    // 13.
+    void close_outputs()
+    {
+        ::close(out.fout);
+        if (out.fout_unpair >= 0) ::close(out.fout_unpair);
+        if (out.fout_all >= 0) ::close(out.fout_all);
+        if (sh.bam_out) {
+            cout << "Converting SAM to BAM ...\nSorting BAM ...\nIndexing BAM ...\n";  // sam2bam.sh's progress lines
+            out.bam.finish();
+        }
+    }
+
+    void destroy_device_objects()
+    {
+        for (bsx_batch *b : batches) bsx_batch_destroy(b);
         for (bsx_ref *r : refs) bsx_ref_destroy(r);
-        const ssize_t w = write(lane.stats_fd, &st, sizeof st);
-        ::close(lane.stats_fd);
-        cout.flush();
-        _exit(w == (ssize_t)sizeof st ? 0 : 1);
     }
-    char pct[64];
-    if (pe) {
-        cout << "Total number of aligned reads: \n";
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * fmt.n_aligned_pairs / total : 0.0);
-        cout << "pairs:       " << fmt.n_aligned_pairs << " (" << pct << "%)\n";
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * fmt.n_aligned_a / total : 0.0);
-        cout << "single a:    " << fmt.n_aligned_a << " (" << pct << "%)\n";
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * fmt.n_aligned_b / total : 0.0);
-        cout << "single b:    " << fmt.n_aligned_b << " (" << pct << "%)\n";
-    } else {
-        snprintf(pct, sizeof(pct), "%.2g", total ? 100.0 * fmt.n_aligned / total : 0.0);
-        cout << "Total number of aligned reads: " << fmt.n_aligned << " (" << pct << "%)\n";
+    // 14. the run's LaneStats: a lane sends them to the parent, which prints the run's summary; the single pipeline prints its own
+    int report()
+    {
+        run.t_map1 = now_s();
+        struct rusage ru1; getrusage(RUSAGE_SELF, &ru1);
+        run.cpu_user = (ru1.ru_utime.tv_sec - ru0.ru_utime.tv_sec) + 1e-6 * (ru1.ru_utime.tv_usec - ru0.ru_utime.tv_usec);
+        run.cpu_sys = (ru1.ru_stime.tv_sec - ru0.ru_stime.tv_sec) + 1e-6 * (ru1.ru_stime.tv_usec - ru0.ru_stime.tv_usec);
+        run.mapping_s = run.t_map1 - run.t_map0;
+        run.n_aligned = totals.n_aligned; run.n_pairs = totals.n_aligned_pairs; run.n_a = totals.n_aligned_a; run.n_b = totals.n_aligned_b;
+        for (int k = 0; k < 4; k++) { run.stage_cpu[k] = stats.cpu_ns[k] * 1e-9; run.busy[k] = stats.busy[k]; }
+        for (int k = 0; k < 3; k++) run.gpu_part[k] = stats.gpu_part[k];
+        if (lane.index >= 0) {
+            destroy_device_objects();
+            const ssize_t w = write(lane.stats_fd, &run, sizeof run);
+            ::close(lane.stats_fd);
+            cout.flush();
+            _exit(w == (ssize_t)sizeof run ? 0 : 1);
+        }
+        print_summary(sh.pe, run, t_begin);
+        if (kn.timing) print_timing_json(sh.pe, run, sh.ncpu);
+        if (sh.ev_on) {
+            fprintf(stderr, "{\"events\": [");
+            for (size_t i = 0; i < stats.events.size(); i++)
+                fprintf(stderr, "%s[%ld, %d, %.4f, %.4f]", i ? ", " : "", stats.events[i].k, stats.events[i].stage, stats.events[i].t0 - run.t_map0, stats.events[i].t1 - run.t_map0);
+            fprintf(stderr, "]}\n");
+        }
+        destroy_device_objects();
+        return 0;
     }
-    cout << "Done.\n";
-    time_t t_end = time(NULL);
-    cout << "Finished at " << ctime(&t_end);
-    cout << "Total time consumed:  " << t_end - t_begin << " secs\n";
-    if (getenv("BSX_TIMING"))  // machine-readable phase times (extension; stderr so that stdout keeps the reference's lines)
-        fprintf(stderr, "{\"load_reference_s\": %.3f, \"index_build_s\": %.3f, \"mapping_s\": %.3f, \"units\": %u, \"reads\": %u, \"workers\": %d, \"usable_cpus\": %u, "
-                        "\"mapping_cpu_s\": {\"user\": %.2f, \"sys\": %.2f, \"parse_threads\": %.2f, \"gpu_driver_threads\": %.2f, \"format_workers\": %.2f, \"write_threads\": %.2f}, "
-                        "\"stage_busy_s\": {\"parse\": %.3f, \"gpu\": %.3f, \"format\": %.3f, \"write\": %.3f, \"gpu_upload\": %.3f, \"gpu_align\": %.3f, \"gpu_readback\": %.3f}}\n",
-                t_loaded - t0, t_indexed - t_loaded, t_map1 - t_map0, total, pe ? 2 * total : total, workers, ncpu, ru_user, ru_sys, cpu_ns[0] * 1e-9, cpu_ns[1] * 1e-9, cpu_ns[2] * 1e-9, cpu_ns[3] * 1e-9, busy[0], busy[1], busy[2], busy[3], gpu_part[0], gpu_part[1], gpu_part[2]);
-    if (ev_on) {
-        fprintf(stderr, "{\"events\": [");
-        for (size_t i = 0; i < events.size(); i++)
-            fprintf(stderr, "%s[%ld, %d, %.4f, %.4f]", i ? ", " : "", events[i].k, events[i].stage, events[i].t0 - t_map0, events[i].t1 - t_map0);
-        fprintf(stderr, "]}\n");
-    }
-    for (int g = 0; g < NG; g++) bsx_batch_destroy(batches[g]);
-    for (bsx_ref *r : refs) bsx_ref_destroy(r);
-    return 0;
+};
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    cout << "\nBSMAP v" << version << endl;
+    if (argc == 1) usage();
+    const time_t t_begin = time(NULL);
+    const double t0 = now_s();
+    cout << "Start at:  " << ctime(&t_begin) << endl;
+    const Knobs kn;
+    Opts o;
+    finish_options(argc, argv, o, kn);                        // 1
+    // --lanes: from here on a lane process sees its own range of reads, its GPU and its output file; the parent does not come back
+    LaneInfo lane;
+    fork_lanes(o, lane, kn, t_begin);                         // 2
+    const RunShape sh = choose_shape(o, lane, kn);            // 3
+    Pipeline &P = *new Pipeline(o, kn, lane, sh, t_begin);    // never freed: error paths exit() while side threads may still touch it (its ring above all)
+    P.pin_cpus();                                             // 4
+    thread t_pin([&P] { P.pretouch_buffers(); });             // 5
+    P.load_replicas(t0);                                      // 6
+    P.fill_ref_view();                                        // 7
+    P.print_parameters();                                     // 8
+    P.open_outputs();                                         // 9
+    P.create_batches();                                       // 10 (and the readers)
+    t_pin.join();
+    P.lane_rendezvous();                                      // 11
+    P.run_stages();                                           // 12
+    P.close_outputs();                                        // 13
+    return P.report();                                        // 14
 }
